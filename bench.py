@@ -15,8 +15,12 @@ Multi-GPU: replicas shard across ranks, no data-path collective; launched by the
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`.  BASELINE's metric reads "1024 replicas at 1/2/4/8
 GPUs"; `value` is the WEAK-scaling reading (1024 replicas on every GPU: the per-GPU work that fills the machine — the diagonal
 launch runs 4 workgroups of 4 waves per CU, i.e. exactly 1024 replicas on 256 CUs; fewer replicas per GPU leave CUs idle), and
-for N > 1 the line also carries the STRONG-scaling reading (1024 replicas in total, 1024/N per GPU) under `strong_scaling`,
-measured in the same invocation.
+with --full for N > 1 the line also carries the STRONG-scaling reading (1024 replicas in total, 1024/N per GPU) under
+`strong_scaling`, measured in the same invocation.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the outputs of --dump-outputs DIR, the
+result line.  --full adds the measurements that take runs of their own: `cpu_baseline` (the C oracle on the host's cores) and
+the strong-scaling reading.
 """
 import argparse
 import json
@@ -124,6 +128,32 @@ def timed_run(g, steps, warmup, beta, flags, dist, torch):
     return time.perf_counter() - t0
 
 
+def dump_outputs(g, out_dir, energy, seed, budget=64 << 20):
+    """--dump-outputs: what a caller of the timed path holds after its last step, one DIR/<name>.npy per array: p = 0 spins
+    (float32), op counts n, cutoffs M, the accumulators of the timed steps and the energy per replica from them, and the
+    op-strings up to the largest cutoff of the sample, zero-padded (float64: op words pass 2^24, and every u32 / u64 counter
+    is exact below 2^53).  Where all replicas do not fit the budget, the spins and op-strings cover a sample of replicas
+    drawn from the run's seed, whose indices are written too; everything else covers every replica."""
+    import numpy as np
+    R, cut = g.nreplicas, g.get_cutoff()
+    order = np.random.default_rng(seed).permutation(R)
+    rows_state = np.sort(order[:max(1, min(R, (budget // 2) // (4 * g.nvars)))])
+    rows_ops = np.sort(order[:max(1, min(R, 16, (budget // 3) // (8 * int(cut.max()))))])
+    width = int(cut[rows_ops].max())
+    ops = np.zeros((len(rows_ops), width), dtype=np.float64)
+    for i, r in enumerate(rows_ops):
+        w = g.export_ops(int(r))
+        ops[i, :len(w)] = w
+    arrays = {"state": g.state_ref()[rows_state].astype(np.float32), "state_replicas": rows_state.astype(np.float64),
+              "n": g.get_n().astype(np.float64), "cutoff": cut.astype(np.float64),
+              "accumulators": g.accumulators().astype(np.float64), "energy": np.asarray(energy, dtype=np.float64),
+              "ops": ops, "ops_replicas": rows_ops.astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= budget
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -146,6 +176,11 @@ def main():
                          "Gamma=1, h=0.1, one disorder realisation per replica; use with --beta 4 --replicas 512")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE run (profiles/README.md)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (unless --no-cpu-baseline) and, "
+                         "with N > 1 ranks, the strong-scaling reading")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     import numpy as np
@@ -225,9 +260,11 @@ def main():
         slots_all = slots
     launch_info = g.launch_info()
     energy = -(acc[:, 0] / np.maximum(acc[:, 1], 1)) / beta + g.get_offsets()
-    # ---- strong-scaling reading of the same metric (N > 1): 1024 replicas in total, R/N per GPU ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(g, args.dump_outputs, energy, args.seed)
+    # ---- strong-scaling reading of the same metric (N > 1, --full): 1024 replicas in total, R/N per GPU ----
     strong = None
-    if world > 1 and not args.pmj3d and not args.rvb and R % world == 0:
+    if args.full and world > 1 and not args.pmj3d and not args.rvb and R % world == 0:
         del g
         Rs = R // world
         gs = im.QmcIsingGraph(edges, 1.0, 0.0, L * L, args.seed, nreplicas=Rs, capacity=cap, replica_offset=rank * Rs,
@@ -326,7 +363,7 @@ def main():
         }
         if strong is not None:
             out["strong_scaling"] = strong
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(L, beta, flags, args.seed, budget_s=25.0 if (args.rvb or args.pmj3d) else 20.0,
                                                pmj3d=args.pmj3d, couplings=couplings_cpu if args.pmj3d else None)
         print(json.dumps(out))

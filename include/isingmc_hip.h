@@ -53,12 +53,7 @@ extern "C" {
                                         ISINGMC_CFG_NO_LDS_TABLES or non-uniform couplings; slots_per_lane 1 or 4; no RVB updates. */
 #define ISINGMC_CFG_NO_FAST_DIAG 16u /* run the diagonal pass through the general kernel even where the instruction-trimmed one
                                         (csrc/sse_fast.hip.h: uniform |J|, N <= 4096, 4 waves per replica) applies (testing / A-B timing) */
-#define ISINGMC_CFG_FAST_LABEL 32u /* experimental: the trimmed diagonal kernel also labels the worldline segments and hands them to the
-                                      cluster update of the same timestep, which then only runs the union-find (same results; on MI355X the
-                                      diagonal launch loses more than the cluster update gains, see DESIGN.md, so it is off by default) */
-#define ISINGMC_CFG_COMPACT 64u /* experimental: the trimmed diagonal kernel also writes the occupied slots as a dense list and the cluster
-                                   update of the same timestep scans that list (n instead of M elements; same results; on MI355X the two
-                                   launches trade 0.1 ms for 0.1 ms, see DESIGN.md, so it is off by default) */
+/* bits 32 and 64 are retired (two experimental diagonal-to-cluster hand-overs): isingmc_create ignores them; do not reuse them */
 #define ISINGMC_CFG_RVB_SERIAL_GROWTH 128u /* RVB sweeps grow the clusters of their attempts one at a time instead of a batch of them side by
                                             side on the waves of the workgroup (testing: the results are the same either way) */
 #define ISINGMC_CFG_NO_LEAN_CLUSTER 256u /* run cluster updates through the general kernel even where the dedicated one (csrc/sse_cluster.hip.h:
@@ -294,11 +289,10 @@ int isingmc_set_steps_per_launch(isingmc_batch *b, uint64_t steps);
 /* build/launch configuration actually in use: out[0]=waves per replica, out[1]=dynamic LDS bytes,
  * out[2]=union-find ids that fit in LDS, out[3]=state words per replica, out[4]=slots per lane,
  * out[5]=1 if the edge table is staged in LDS, out[6]=bit 0: timesteps are issued as two launches (diagonal, rest); bit 1: per-variable
- * tables live in HBM (ISINGMC_CFG_GLOBAL_TABLES path); bit 2: the diagonal-pass launch is the trimmed kernel of sse_fast.hip.h; bit 3: ... and it labels the segments for the cluster
- * update of the same timestep; bit 4: ... or hands it the dense list of occupied slots; bit 5: the most recent cluster launch was the
- * dedicated kernel; bit 6: the most recent RVB sweep ran as growth + main launches (bits 16-23: waves per replica of that main
- * launch); bits 8-15: waves per replica of the most recent off-diagonal launch,
- * out[7]=dynamic LDS bytes of the diagonal-pass launch */
+ * tables live in HBM (ISINGMC_CFG_GLOBAL_TABLES path); bit 2: the diagonal-pass launch is the trimmed kernel of sse_fast.hip.h; bits 3-4:
+ * reserved (always 0); bit 5: the most recent cluster launch was the dedicated kernel; bit 6: the most recent RVB sweep ran as
+ * growth + main launches (bits 16-23: waves per replica of that main launch); bits 8-15: waves per replica of the most recent
+ * off-diagonal launch, out[7]=dynamic LDS bytes of the diagonal-pass launch */
 int isingmc_get_launch_info(const isingmc_batch *b, uint32_t out[8]);
 /* Host-only: the chunk grid and op-string row stride isingmc_create derives for `capacity` slots and kernels of W (diagonal
  * launches) / up to Wmax (off-diagonal launches) wave64s per replica at K slots per lane: out = {chunk size, chunks, row stride in

@@ -33,9 +33,7 @@ struct isingmc_batch {
     float last_ms = 0.f;
     uint32_t last_launches = 0;
     bool fast_diag = false;             // the diagonal-pass launch uses sse_fast.hip.h (headline geometry: LDS edge tables, 4 waves, N <= 4096)
-    size_t lds_bytes_fast = 0, lds_bytes_fast_label = 0;
-    bool compact = false;               // ... and it writes the dense op list for the cluster update that follows in the same timestep
-    bool lite = false;                  // ... or (experimental) labels the segments for the cluster update that follows in the same timestep
+    size_t lds_bytes_fast = 0;
     bool fused_launch = false;          // ISINGMC_CFG_FUSED_LAUNCH: whole timesteps in one kernel (no diagonal-only launches)
     size_t lds_bytes_pm_diag = 0;       // +-J decode: LDS of the diagonal launch with its per-wave spin bytes in LDS (0 = they do not fit: mode 4 there too)
     bool lean_cluster = false;          // cluster (+ free spins + sampling) launches use sse_cluster.hip.h when their ids fit its LDS union-find
@@ -244,9 +242,9 @@ static size_t lds_fixed_words(uint32_t W, uint32_t N, uint32_t nwords, uint32_t 
     return (size_t)nwords * 2 + ((size_t)N + 3) / 4 + 4 * W + 16 + 2 * SSE_MAX_CHUNKS + ledges + ((size_t)W * N + 1) / 2 + ((size_t)W * N + 3) / 4;
 }
 // dynamic LDS of the fast diagonal-pass launch (mirrors Lds<4>::carve up to o_cur, then FastLds: sse_fast.hip.h fast_carve)
-static size_t fast_lds_bytes(uint32_t N, uint32_t nwords, uint32_t E, uint32_t Nb, bool label) {
+static size_t fast_lds_bytes(uint32_t N, uint32_t nwords, uint32_t E, uint32_t Nb) {
     const size_t o_edges = (size_t)nwords * 2 + ((size_t)N + 3) / 4 + 4 * 4 + 16 + 2 * SSE_MAX_CHUNKS;
-    size_t words = ((o_edges + 3) & ~(size_t)3) + 16 + Nb + N + 64 + (label ? 4 * (size_t)N + ((size_t)N + 3) / 4 : 0);
+    size_t words = ((o_edges + 3) & ~(size_t)3) + 16 + Nb + N + 64;
     if (words < o_edges + E) words = o_edges + E; // the directed loop behind the pass stages the compact edge table there
     return (4 * words + 7) & ~(size_t)7;
 }
@@ -552,12 +550,8 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         ld.W = b->W;
         ld.passes = SSE_PASSES_DIAG;
         const bool use_fast = b->fast_diag && !(A.domask & SSE_DO_HEATBATH);
-        // the cluster update of the same timestep takes the segment labelling from the diagonal launch (nothing but the
-        // directed loop may sit in between: it changes no op's position or bond)
-        const bool use_label = use_fast && b->lite && (A.domask & SSE_DO_CLUSTER) && !(A.domask & SSE_DO_RVB);
-        const bool use_compact = use_fast && !use_label && b->compact && (A.domask & SSE_DO_CLUSTER) && !(A.domask & SSE_DO_RVB);
         // the diagonal launch needs the fixed regions up to the per-wave tables, which it uses as [W][N] bytes
-        ld.lds_bytes = use_fast ? (use_label ? b->lds_bytes_fast_label : b->lds_bytes_fast) : diag_lds_bytes(b);
+        ld.lds_bytes = use_fast ? b->lds_bytes_fast : diag_lds_bytes(b);
         if (is_pm(b) && b->lds_bytes_pm_diag) { ld.mode = SSE_MODE_PM_LDS_TABLES; ld.lds_bytes = b->lds_bytes_pm_diag; } // (the cluster tables stay in HBM)
         const uint32_t rest = A.domask & ~diag_bits;
         constexpr size_t MAX_TIMED = 256;
@@ -573,7 +567,7 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
             }
             const bool timed = done < MAX_TIMED;
             SweepArgs a1 = A;
-            a1.domask = (A.domask & diag_bits) | (use_label ? SSE_DO_LABEL : 0u) | (use_compact ? SSE_DO_COMPACT : 0u); a1.nsteps = 1; a1.step0 = done; a1.sampling_freq = 0; a1.out_u32 = nullptr;
+            a1.domask = A.domask & diag_bits; a1.nsteps = 1; a1.step0 = done; a1.sampling_freq = 0; a1.out_u32 = nullptr;
             if (b->pending) { // (every step of a run after the first: the cluster update of the step before left flip bytes)
                 if (use_fast && b->defer) { a1.defer_flips = 1u; b->pending = false; }
                 else { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
@@ -878,18 +872,12 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
         D.CH = geo[0]; D.nchunks = geo[1]; D.stride = geo[2];
     }
     b->lds_fixed_words_ = fixed; b->lds_total_words = total_words; b->uf_ids_limit = cfg->lds_uf_ids_limit;
-    b->lds_bytes_fast = fast_lds_bytes(D.N, D.nwords, D.E, D.Nb, false);
+    b->lds_bytes_fast = fast_lds_bytes(D.N, D.nwords, D.E, D.Nb);
     b->fast_diag = CL && !TG && W == 4 && (K == 4 || K == 2) && D.N <= SSE_FAST_MAX_VARS && !b->fused_launch &&
                    !(cfg->flags & ISINGMC_CFG_NO_FAST_DIAG) && b->lds_bytes_fast <= 40 * 1024; // 4 workgroups per CU
-    // ... and labels the segments for the cluster update of the same timestep (h = 0: no frozen segments to track)
     // the cluster update of that geometry has its own kernel too (16 waves, packed tables; sse_cluster.hip.h)
     b->lean_cluster = CL && !TG && !generic && D.N <= 4095u && !b->fused_launch && !cfg->waves_offdiag && !cfg->waves_per_replica &&
                       !(cfg->flags & ISINGMC_CFG_NO_LEAN_CLUSTER);
-    b->lds_bytes_fast_label = fast_lds_bytes(D.N, D.nwords, D.E, D.Nb, true);
-    // (opt-in as well: the diagonal launch pays for the two extra stores per op what the shorter scan gains)
-    b->compact = b->fast_diag && (cfg->flags & ISINGMC_CFG_COMPACT) && !(cfg->flags & ISINGMC_CFG_FAST_LABEL);
-    // (opt-in: measured on MI355X the labelling costs the diagonal launch more than it saves the cluster update)
-    b->lite = b->fast_diag && !has_long && (cfg->flags & ISINGMC_CFG_FAST_LABEL) && b->lds_bytes_fast_label <= 40 * 1024;
     { // the RVB pass reuses everything from the scan tables on: launches that run it get enough LDS for its scratch
       // and constant-op table (other launches keep the smaller footprint, which decides workgroups per CU)
         const size_t o_cur = TG ? fixed : fixed - ((size_t)W * D.N + 1) / 2 - ((size_t)W * D.N + 3) / 4;
@@ -986,21 +974,6 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
     }
     const size_t ufstride = ids_max + 2 * ((ids_max + 31) / 32);
     if ((rc = dalloc(b, &D.uf_scratch, (size_t)D.R * ufstride, false))) return fail(rc);
-    if (b->compact) {
-        if ((rc = dalloc(b, &D.cops, (size_t)D.R * D.stride, false))) return fail(rc);
-        if ((rc = dalloc(b, &D.cpos, (size_t)D.R * D.stride, false))) return fail(rc);
-        if ((rc = dalloc(b, &D.cops_epoch, D.R, false))) return fail(rc);
-        if (hipMemset(D.cops_epoch, 0xFF, sizeof(uint64_t) * D.R) != hipSuccess) { b->err = "hipMemset failed"; return fail(ISINGMC_ENODEVICE); }
-    }
-    if (b->lite) {
-        D.lite = 1u;
-        if ((rc = dalloc(b, &D.pairs, (size_t)D.R * D.stride, false))) return fail(rc);
-        if ((rc = dalloc(b, &D.pcount, (size_t)D.R * 4))) return fail(rc);
-        if ((rc = dalloc(b, &D.lastrank, (size_t)D.R * D.N))) return fail(rc);
-        if ((rc = dalloc(b, &D.touchbits, (size_t)D.R * D.nwords))) return fail(rc);
-        if ((rc = dalloc(b, &D.lite_epoch, D.R, false))) return fail(rc);
-        if (hipMemset(D.lite_epoch, 0xFF, sizeof(uint64_t) * D.R) != hipSuccess) { b->err = "hipMemset failed"; return fail(ISINGMC_ENODEVICE); }
-    }
     if (TG) {
         D.tbl_stride = (uint32_t)((((size_t)Wmax * D.N * 4 + D.N) + 15) & ~(size_t)15); // 4-byte scan records per (wave, variable)
         if ((rc = dalloc(b, &D.tbl, (size_t)D.R * D.tbl_stride))) return fail(rc);
@@ -1395,7 +1368,7 @@ int isingmc_last_rvb_ms(isingmc_batch *b, float *ms, uint32_t *launches) {
 int isingmc_get_launch_info(const isingmc_batch *b, uint32_t out[8]) {
     if (!b || !out) return ISINGMC_EINVAL;
     out[0] = b->W; out[1] = (uint32_t)b->lds_bytes; out[2] = b->dev.lds_ufcap; out[3] = b->dev.nwords;
-    out[4] = b->K; out[5] = b->mode == SSE_MODE_LDS_EDGES ? 1u : 0u; out[6] = (b->fused_launch ? 0u : 1u) | (b->last_W_off << 8) | (is_tg(b) ? 2u : 0u) | (b->fast_diag ? 4u : 0u) | (b->lite ? 8u : 0u) | (b->compact ? 16u : 0u) | (b->last_lean ? 32u : 0u) | (b->last_rvb_split ? 64u : 0u) | ((b->last_rvb_split ? b->rvb_main_W : 0u) << 16); out[7] = (uint32_t)diag_lds_bytes(b);
+    out[4] = b->K; out[5] = b->mode == SSE_MODE_LDS_EDGES ? 1u : 0u; out[6] = (b->fused_launch ? 0u : 1u) | (b->last_W_off << 8) | (is_tg(b) ? 2u : 0u) | (b->fast_diag ? 4u : 0u) | (b->last_lean ? 32u : 0u) | (b->last_rvb_split ? 64u : 0u) | ((b->last_rvb_split ? b->rvb_main_W : 0u) << 16); out[7] = (uint32_t)diag_lds_bytes(b);
     return ISINGMC_OK;
 }
 
@@ -1483,8 +1456,6 @@ __global__ void pt_unpack_kernel(DevBatch B, uint32_t *rid, const uint32_t *item
     if (threadIdx.x == 0) {
         B.n[r] = o[0]; B.ntrans[r] = o[1]; B.cutoff[r] = o[2]; B.err[r] = o[3];
         B.epoch[r] = (uint64_t)o[4] | ((uint64_t)o[5] << 32); rid[r] = o[6];
-        if (B.lite) B.lite_epoch[r] = ~0ull;
-        if (B.cops) B.cops_epoch[r] = ~0ull;
     }
     for (uint32_t i = threadIdx.x; i < B.nwords; i += blockDim.x) B.state[(size_t)r * B.nwords + i] = o[PT_HDR + i];
     for (uint32_t i = threadIdx.x; i < 2 * SSE_MAX_CHUNKS; i += blockDim.x) B.chunks[(size_t)r * 2 * SSE_MAX_CHUNKS + i] = o[PT_HDR + B.nwords + i];

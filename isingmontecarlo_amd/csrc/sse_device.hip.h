@@ -61,19 +61,8 @@ struct DevBatch {
     uint32_t *chunks;     // [R][2*SSE_MAX_CHUNKS]: per chunk of CH slots: occupied count, transverse-op count
     uint32_t CH, nchunks; // chunk size (multiple of 256 slots) and number of chunks covering cap
     uint32_t *uf_scratch; // [R][W*N+cap (+bit arrays)] union-find fallback in HBM
-    // hand-over from the trimmed diagonal kernel (sse_fast.hip.h) to the cluster update that follows it in the same timestep:
-    // the segment labelling rides on the diagonal pass (segs above is written there), the cluster update only unions
-    uint32_t lite;        // 1 = the arrays below exist
-    uint32_t *pairs;      // [R][stride]: segment-id pairs (lo | hi << 16) of the two-site ops, appended per wave: wave q of the
-                          // diagonal launch owns [q*stride/4, (q+1)*stride/4)
-    uint32_t *pcount;     // [R][4] pairs appended by each wave
-    uint16_t *lastrank;   // [R][N] 1 + dense index of the last cut on each worldline (0 = none): the wrap-around joins
-    uint32_t *touchbits;  // [R][nwords] variables that carry an op
-    uint64_t *lite_epoch; // [R] the update counter at which segs / pairs describe the op-string (any other primitive in between
-                          // moves the counter on and the cluster update falls back to its own scan)
-    // ... or, instead, the dense list of the occupied slots in p order (the cluster update scans n instead of M elements)
-    uint32_t *cops, *cpos; // [R][stride] op words / their slots; null = not allocated
-    uint64_t *cops_epoch;  // [R] the update counter at which the list describes the op-string
+    uint64_t kernarg_pad; // unused: keeps the fields below at their offsets modulo 64.  The register allocation of the general kernels
+                          // depends on where these kernel arguments fall: without this word a dozen of them gain scalar or vector spills
     uint8_t *tbl;         // [R][tbl_stride] per-variable tables in HBM/L2 for models whose tables exceed LDS (MODE 2, see Tab)
     uint32_t tbl_stride;  // bytes per replica: Wmax*N*4 (scan records {rank, marker, touched} / spin bytes of the diagonal pass) + N, rounded up to 16
     uint32_t seed_lo, seed_hi, replica_offset;
@@ -120,8 +109,6 @@ struct DevBatch {
 #define SSE_DO_GROW 16u
 #define SSE_DO_HEATBATH 32u
 #define SSE_DO_RVB 64u
-#define SSE_DO_COMPACT 256u // trimmed diagonal launch only: write the dense op list for the cluster update of the same timestep
-#define SSE_DO_LABEL 128u // trimmed diagonal launch only: label the segments for the cluster update of the same timestep
 
 struct SweepArgs {
     const double *beta; // [R]
@@ -913,14 +900,9 @@ __device__ __forceinline__ void uf_union_wave(const UFA<G> &uf, uint32_t a, uint
 //   [N+C, N+C+(W-1)N)     P(w,v): "whatever segment v is in when wave w's range begins" — artificial ids, larger
 //                                 than every real id so they are never roots; joined to the real segments after
 //                                 the scan (cluster_pass).
-// COMPACT: the scan reads the dense list of occupied slots that the trimmed diagonal kernel of this timestep wrote (B.cops /
-// B.cpos) instead of the padded op-string: the same p-ordered stream without its empty slots (a third of all slots at
-// M = 1.5 n), every lane of every row useful.  Ranges are still bounded by chunks of the padded string — their occupied counts
-// (o_chn) give the corresponding ranges of the list — and the segment ids still land at the ops' slots (segs[cpos]).
-template <int W, int K, bool CL, bool APPLY, bool G, bool TG, bool COMPACT = false, bool PM = false>
+template <int W, int K, bool CL, bool APPLY, bool G, bool TG, bool PM = false>
 __device__ __forceinline__ void cluster_scan(const DevBatch &B, const Lds<W> &L, uint32_t r, uint32_t M, const UFA<G> &uf,
                                              uint32_t C) {
-    static_assert(!COMPACT || (!APPLY && !G && !TG), "the dense list feeds the build scan of the LDS union-find path");
     constexpr int NT = W * 64;
     const Tab<TG> T = make_tab<TG, W>(B, L, r);
     constexpr uint32_t TS = 64 * K; // slots per wave-tile
@@ -943,36 +925,27 @@ __device__ __forceinline__ void cluster_scan(const DevBatch &B, const Lds<W> &L,
     for (uint32_t c = lane; c < c0; c += 64) cutbase += LDSW(L.o_chtr, c);
     for (int off = 32; off > 0; off >>= 1) cutbase += __shfl_xor(cutbase, off);
     cutbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)cutbase);
-    uint32_t pbeg = c0 * B.CH, pend = min(c1 * B.CH, M);
-    const uint32_t *src = ops;                      // the stream this wave scans: the padded string, or the dense list
-    const uint32_t *cpos = nullptr;
-    if constexpr (COMPACT) {
-        uint32_t nb = 0, ne = 0;                    // ops in front of the range / up to its end
-        for (uint32_t c = lane; c < c1; c += 64) { const uint32_t x = LDSW(L.o_chn, c); ne += x; nb += c < c0 ? x : 0u; }
-        for (int off = 32; off > 0; off >>= 1) { nb += __shfl_xor(nb, off); ne += __shfl_xor(ne, off); }
-        pbeg = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb); pend = (uint32_t)__builtin_amdgcn_readfirstlane((int)ne);
-        src = B.cops + (size_t)r * B.stride; cpos = B.cpos + (size_t)r * B.stride;
-    }
+    const uint32_t pbeg = c0 * B.CH, pend = min(c1 * B.CH, M);
     const uint32_t my_placeholder_base = wave == 0 ? 0u : N + C + (uint32_t)(wave - 1) * N;
     const uint32_t idbase = N + cutbase - 1u; // id of the cut with local rank+1 == x is idbase + x
     if (lane == 0) LDSW(L.o_chg, wave) = idbase; // read back by cluster_pass when it joins the ranges
     uint32_t nlocal = 0;                      // cuts seen so far in this wave's range
     // branch-free prefetch (see diagonal_pass): ranges are whole tiles except at the end of the string, where the
     // padded row holds zeros; past the range end the last tile is simply read again
-    uint32_t wnext[K], posn[K];
+    uint32_t wnext[K];
 #pragma unroll
-    for (int j = 0; j < K; ++j) { wnext[j] = row_ld(src, pbeg + j * 64 + lane); if constexpr (COMPACT) posn[j] = row_ld(cpos, pbeg + j * 64 + lane); }
+    for (int j = 0; j < K; ++j) wnext[j] = row_ld(ops, pbeg + j * 64 + lane);
     for (uint32_t p0 = pbeg; p0 < pend; p0 += TS) {
 #ifdef SSE_GEN_ROTATE
         sse_set_prio(p0 / TS / SSE_GEN_ROTATE + blockIdx.x);
 #endif
         uint32_t word[K], pos[K];
 #pragma unroll
-        for (int j = 0; j < K; ++j) { word[j] = (p0 + j * 64 + lane < pend) ? wnext[j] : 0u; pos[j] = COMPACT ? posn[j] : p0 + j * 64 + lane; }
+        for (int j = 0; j < K; ++j) { word[j] = (p0 + j * 64 + lane < pend) ? wnext[j] : 0u; pos[j] = p0 + j * 64 + lane; }
         {
             const uint32_t pn0 = p0 + TS < pend ? p0 + TS : p0;
 #pragma unroll
-            for (int j = 0; j < K; ++j) { wnext[j] = row_ld(src, pn0 + j * 64 + lane); if constexpr (COMPACT) posn[j] = row_ld(cpos, pn0 + j * 64 + lane); }
+            for (int j = 0; j < K; ++j) wnext[j] = row_ld(ops, pn0 + j * 64 + lane);
         }
         uint32_t ua[K], uc[K]; // the tile's unions, issued together after the K sub-rounds (unions commute)
         bool utwo[K];
@@ -1057,8 +1030,7 @@ __device__ __forceinline__ void cluster_scan(const DevBatch &B, const Lds<W> &L,
                 if (B.has_long) if (nonempty & (kind == SSE_BOND_LONGITUDINAL)) uf.frozen_or(seg_a >> 5, 1u << (seg_a & 31));
                 if constexpr (!G) { // ids fit 16 bits on this path: remember them for the apply pass
                     const uint32_t hi = iscut ? id_own : (two ? seg_c : seg_a);
-                    if constexpr (COMPACT) { if (nonempty) row_st(segs_row, pos[j], seg_a | (hi << 16)); } // (lanes past the range end hold no slot)
-                    else row_st(segs_row, pos[j], seg_a | (hi << 16));
+                    row_st(segs_row, pos[j], seg_a | (hi << 16));
                 } else if (B.segs2) { // 32-bit ids: two words per slot, so that the apply pass need not repeat the ordered scan
                     const uint32_t hi = iscut ? id_own : (two ? seg_c : seg_a);
                     row_st(segs_row, pos[j], seg_a);
@@ -1175,11 +1147,10 @@ __device__ __forceinline__ void cluster_apply_cached(const DevBatch &B, const Ld
 
 // Cluster update.  Reference: ClusterUpdater::flip_each_cluster_rng (qmc_traits/cluster.rs:36-172) with the
 // longitudinal weight function of qmc_ising.rs:759-775.  Returns the number of clusters.
-template <int W, int K, bool CL, bool UF_GLOBAL, bool TG, bool LITE = false, bool COMPACT = false, bool PM = false>
+template <int W, int K, bool CL, bool UF_GLOBAL, bool TG, bool PM = false>
 __device__ __forceinline__ uint32_t cluster_pass(const DevBatch &B, const Lds<W> &L, uint32_t r, const Rng &rng, double prob,
                                                  uint32_t M, int n, int ntrans, uint32_t &gr, uint32_t &err) {
     static_assert(UF_GLOBAL || !TG, "tables in HBM imply the HBM union-find");
-    static_assert(!LITE || (!UF_GLOBAL && !TG && CL), "the hand-over from the trimmed diagonal kernel uses the LDS union-find");
     constexpr int NT = W * 64;
     const Tab<TG> T = make_tab<TG, W>(B, L, r);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1197,7 +1168,6 @@ __device__ __forceinline__ uint32_t cluster_pass(const DevBatch &B, const Lds<W>
     if (tid == 0) { LDSW(L.o_misc, MISC_NCLUST) = 0u; LDSW(L.o_misc, MISC_ANYFROZEN) = 0u; }
     if (n == 0) { __syncthreads(); return 0u; } // cluster.rs:46-48
     SSE_STAMP_INIT;
-    if constexpr (!LITE)
     { // the scan stores 16-bit cut ranks per wave range: every range must hold fewer than 65535 cuts
         const uint32_t used = (M + B.CH - 1) / B.CH, q = (used + W - 1) / W;
         uint32_t bad = 0;
@@ -1209,39 +1179,14 @@ __device__ __forceinline__ uint32_t cluster_pass(const DevBatch &B, const Lds<W>
         if (bad) { err = 8u; return 0u; }
     }
     const uint32_t C = (uint32_t)ntrans;            // one id per cut (transverse op)
-    const uint32_t S = LITE ? N + C : N + C + (uint32_t)(W - 1) * N; // + artificial range-boundary placeholders
-    if constexpr (LITE) {
-        // The diagonal pass of this timestep has already labelled every leg (B.segs) and listed the segment pairs that the
-        // two-site ops join (B.pairs): what is left of the build is the union-find itself.  Ids: [0,N) initial segments,
-        // N + k the segment opened by the k-th cut — no range placeholders, the labelling was done in one p-ordered stream.
-        for (uint32_t i = tid; i < S; i += NT) uf.set(i, i);
-        for (uint32_t i = tid; i < nwords; i += NT) LDSW(L.o_touch, i) = B.touchbits[(size_t)r * nwords + i];
-        __syncthreads();
-        const uint32_t *pairs = B.pairs + (size_t)r * B.stride;
-        const uint32_t reg = B.stride / 4u;
-        for (uint32_t q = 0; q < 4u; ++q) {
-            const uint32_t cnt = B.pcount[(size_t)r * 4 + q];
-            const uint32_t *pq = pairs + (size_t)q * reg;
-            for (uint32_t i0 = 0; i0 < cnt; i0 += 4 * NT) { // four independent loads in flight per thread
-                uint32_t pr[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { const uint32_t i = i0 + (uint32_t)(u * NT + tid); pr[u] = i < cnt ? pq[i] : 0u; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) if (pr[u]) uf_union(uf, pr[u] & 0xFFFFu, pr[u] >> 16); // (a pair never has two equal ids, so 0 = none)
-            }
-        }
-        // worldlines are cyclic in imaginary time (cluster.rs:223-242): the segment behind the last cut on v is the one v starts in
-        const uint16_t *lastrank = B.lastrank + (size_t)r * N;
-        for (uint32_t v = tid; v < N; v += NT) { const uint32_t lr = lastrank[v]; if (lr) uf_union(uf, N + lr - 1u, v); }
-        __syncthreads();
-    } else {
+    const uint32_t S = N + C + (uint32_t)(W - 1) * N; // + artificial range-boundary placeholders
     for (uint32_t i = tid; i < N; i += NT) uf.set(i, i);
     for (uint32_t i = tid; i < (uint32_t)(W - 1) * N; i += NT) uf.set(N + C + i, N + C + i);
     if (B.has_long) for (uint32_t i = tid; i < (S + 31) / 32; i += NT) uf.bits_clear(i);
     __syncthreads();
     // ---- build: label legs with segment ids, union through non-boundary ops ----
     SSE_STAMP(0);
-    cluster_scan<W, K, CL, false, UF_GLOBAL, TG, COMPACT, PM>(B, L, r, M, uf, C);
+    cluster_scan<W, K, CL, false, UF_GLOBAL, TG, PM>(B, L, r, M, uf, C);
     // touched bytes -> bits (read by the coins, the p=0 state update and the free-spin pass, all behind later barriers)
     for (uint32_t i = tid; i < nwords; i += NT) {
         uint32_t bits = 0;
@@ -1270,7 +1215,6 @@ __device__ __forceinline__ uint32_t cluster_pass(const DevBatch &B, const Lds<W>
         if (seg_end != nxt) uf_union(uf, seg_end, nxt);
     }
     __syncthreads();
-    } // !LITE
     SSE_STAMP(2);
     // ---- flatten: parent[i] := exact root (no union runs any more), frozen marks move to roots ----
     for (uint32_t i = tid; i < S; i += NT) {
@@ -1369,7 +1313,7 @@ __device__ __forceinline__ uint32_t cluster_pass(const DevBatch &B, const Lds<W>
     if constexpr (UF_GLOBAL) {
         if (lds_flips) cluster_apply_cached<W, K, CL, true, PM, true>(B, L, r, M, uf);
         else if (B.segs2) cluster_apply_cached<W, K, CL, true, PM>(B, L, r, M, uf); // both ids of every slot were stored by the build scan
-        else cluster_scan<W, K, CL, true, UF_GLOBAL, TG, false, PM>(B, L, r, M, uf, C);  // (a replica that outgrew the LDS union-find before the host planned for it)
+        else cluster_scan<W, K, CL, true, UF_GLOBAL, TG, PM>(B, L, r, M, uf, C);  // (a replica that outgrew the LDS union-find before the host planned for it)
     } else cluster_apply_cached<W, K, CL, false, PM>(B, L, r, M, uf);
     SSE_STAMP(5);
     // p=0 state follows the placeholder segment of each touched variable
@@ -1695,24 +1639,7 @@ __global__ __launch_bounds__(W * 64, (sse_waves_per_simd<W, PASSES>())) void swe
         if (A.domask & SSE_DO_CLUSTER) {
             const Rng rng = make_rng(B, r, epoch);
             const uint32_t S_ids = (uint32_t)W * B.N + (uint32_t)ntrans;
-            bool lite_done = false;
-            if constexpr (CL && !TG) {
-                // the trimmed diagonal kernel labelled the string for exactly this update (same update counter, nothing in between)
-                const uint32_t S_lite = B.N + (uint32_t)ntrans;
-                if (B.lite && B.lite_epoch[r] == epoch && S_lite <= B.lds_ufcap && S_lite <= 65535u) {
-                    last_out = cluster_pass<W, K, CL, false, false, true>(B, L, r, rng, A.prob, M, n, ntrans, gr, err);
-                    lite_done = true;
-                }
-            }
-            if constexpr (CL && !TG) {
-                // ... or wrote the dense list of occupied slots for it
-                if (!lite_done && B.cops && B.cops_epoch[r] == epoch && S_ids <= B.lds_ufcap && S_ids <= 65535u) {
-                    last_out = cluster_pass<W, K, CL, false, false, false, true>(B, L, r, rng, A.prob, M, n, ntrans, gr, err);
-                    lite_done = true;
-                }
-            }
-            if (lite_done) {}
-            else if constexpr (TG) last_out = cluster_pass<W, K, CL, true, true, false, false, PM>(B, L, r, rng, A.prob, M, n, ntrans, gr, err);
+            if constexpr (TG) last_out = cluster_pass<W, K, CL, true, true, PM>(B, L, r, rng, A.prob, M, n, ntrans, gr, err);
             else if (S_ids <= B.lds_ufcap && S_ids <= 65535u) last_out = cluster_pass<W, K, CL, false, false>(B, L, r, rng, A.prob, M, n, ntrans, gr, err);
             else last_out = cluster_pass<W, K, CL, true, false>(B, L, r, rng, A.prob, M, n, ntrans, gr, err);
             epoch++;

@@ -114,16 +114,13 @@ def test_loop_update_matches(oracle, waves, k, cfgf):
     assert g.verify().all()
 
 
-# cfgf 2 = fused launches; 0 at the default geometry = trimmed diagonal kernel; 16 = general diagonal kernel;
-# experimental hand-overs to the cluster update: 64 = dense op list, 32 = segment labelling
-@pytest.mark.parametrize("waves,k,cfgf", [(8, 4, 0), (16, 4, 0), (8, 4, 1), (4, 4, 2), (8, 2, 3), (0, 0, 0), (0, 0, 64), (0, 0, 16), (4, 2, 0), (0, 0, 32)])
-def test_medium_lattice_many_replicas(oracle, waves, k, cfgf):
+def run_medium_lattice(oracle, waves, k, cfgf):
+    """16x16 ferromagnet, 16 replicas: 30 timesteps, then 10 with a directed loop between the diagonal launch and the cluster
+    update, bit-exact against the oracle.  Returns launch_info() as it was before the run."""
     edges = lat.two_d_ferro(16)
     R = 16
     g, m, reps = make_pair(oracle, edges, 1.0, 0.0, 256, 1 << 15, 2024, R, waves=waves, k=k, cfg_flags=cfgf)
     info = g.launch_info()
-    if waves == 0:
-        assert info["fast_diagonal"] == (cfgf != 16) and info["compact_list"] == (cfgf == 64) and info["fast_label"] == (cfgf == 32)
     g.run(30, 4.0)
     oracle.batch_timesteps(reps, 30, [4.0] * R)
     assert_same(g, reps, "16x16")
@@ -131,6 +128,21 @@ def test_medium_lattice_many_replicas(oracle, waves, k, cfgf):
     oracle.batch_timesteps(reps, 10, [4.0] * R, 1, 1)
     assert_same(g, reps, "16x16 + loop")
     assert g.verify().all()
+    return info
+
+
+# cfgf 1 = bond table in HBM, 2 = fused launches
+@pytest.mark.parametrize("waves,k,cfgf", [(8, 4, 0), (16, 4, 0), (8, 4, 1), (4, 4, 2), (8, 2, 3), (4, 2, 0)])
+def test_medium_lattice_many_replicas(oracle, waves, k, cfgf):
+    run_medium_lattice(oracle, waves, k, cfgf)
+
+
+# the default geometry: 0 = trimmed diagonal kernel; 16 = general diagonal kernel; 32 and 64 are retired flags (former
+# hand-overs to the cluster update) that must change nothing
+@pytest.mark.parametrize("cfgf", [0, 16, 32, 64])
+def test_medium_lattice_default_geometry(oracle, cfgf):
+    info = run_medium_lattice(oracle, 0, 0, cfgf)
+    assert info["fast_diagonal"] == (cfgf != 16)
 
 
 def test_many_replicas_stress(oracle):
@@ -721,21 +733,19 @@ def test_cubic_32_full_size_runs_on_the_global_tables_path(oracle):
 
 
 @pytest.mark.parametrize("k,flags", [(0, 0), (0, 1), (2, 0), (4, 1)])
-def test_segment_labelling_on_the_diagonal_kernel(oracle, k, flags):
-    """ISINGMC_CFG_FAST_LABEL (experimental): the trimmed diagonal kernel labels the worldline segments one tile late and
-    the cluster update of the same timestep only runs the union-find over the handed-over segment pairs.  Same Markov
-    chain as every other path: bit-exact against the oracle, with and without a directed loop in between, and when a
-    primitive is called out of band (the hand-over must then be ignored, not used stale)."""
-    import isingmontecarlo_amd as im
+def test_trimmed_diagonal_then_cluster_with_out_of_band_primitives(oracle, k, flags):
+    """The trimmed diagonal kernel (k = 0: default geometry; 2 and 4 slots per lane) and the cluster update after it:
+    bit-exact against the oracle, with and without a directed loop in between, with sampling, and in whole timesteps
+    that follow single primitives called out of band."""
     edges = lat.two_d_ferro(16)
     R, beta = 12, 4.0
-    g, m, reps = make_pair(oracle, edges, 1.0, 0.0, 256, 1 << 15, 4711, R, waves=4 if k else 0, k=k, cfg_flags=im.CFG_FAST_LABEL)
+    g, m, reps = make_pair(oracle, edges, 1.0, 0.0, 256, 1 << 15, 4711, R, waves=4 if k else 0, k=k)
     info = g.launch_info()
-    assert info["fast_diagonal"] and info["fast_label"]
+    assert info["fast_diagonal"]
     g.run(25, beta, sampling_freq=2, flags=flags)
     oracle.batch_timesteps(reps, 25, [beta] * R, 2, flags)
-    assert_same(g, reps, "label hand-over")
-    g.single_diagonal_step(beta)   # out of band: labels nothing that a later cluster update may use
+    assert_same(g, reps, "trimmed diagonal + cluster")
+    g.single_diagonal_step(beta)   # out of band
     nc = g.single_cluster_step(flip_free=True)
     for r, rep in enumerate(reps):
         rep.diagonal_update(beta)
@@ -746,7 +756,7 @@ def test_segment_labelling_on_the_diagonal_kernel(oracle, k, flags):
         rep.flip_free_spins()
     g.run(6, beta, flags=flags)
     oracle.batch_timesteps(reps, 6, [beta] * R, 1, flags)
-    assert_same(g, reps, "label hand-over after out-of-band primitives")
+    assert_same(g, reps, "trimmed diagonal + cluster after out-of-band primitives")
     acc = g.accumulators()
     for r, rep in enumerate(reps):
         assert np.array_equal(acc[r, :7], rep.accumulators()[:7])

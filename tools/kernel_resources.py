@@ -99,7 +99,7 @@ def is_prep_symbol(pretty):
     m = re.match(r"sse::sweep_kernel<(\d+), (\d+), (\d+), (\d+), (\d+)>", pretty)
     if m:
         return m.group(4) == "1"
-    m = re.match(r"sse::sweep_fast_kernel<(\d+), (\d+),", pretty)
+    m = re.match(r"sse::sweep_fast_kernel<(\d+), (\d+)[,>]", pretty)
     if m:
         return m.group(2) == "1"
     m = re.match(r"sse::cluster_kernel<(\d+), (\w+), (\d+)>", pretty)

@@ -299,6 +299,12 @@ int isingmc_get_launch_info(const isingmc_batch *b, uint32_t out[8]);
  * words, tile = slots of the widest whole-tile access}.  Exposed so that the bounds every kernel relies on (whole-tile loads and
  * stores, the prefetch of an empty chunk range, cached-id rows) can be asserted on a CPU box. */
 int isingmc_plan_geometry(uint32_t capacity, uint32_t W, uint32_t K, uint32_t Wmax, uint32_t out[4]);
+/* Host-only: the LDS layout of the dedicated cluster kernel (16 waves) for N variables (nwords state words, Nb bonds), a 16-bit
+ * parent table of ufcap ids, has_long != 0 when the model has a longitudinal field, and a replica with S ids (16 N + cuts):
+ * out = {word offsets o_tab, o_state, o_touch, o_misc, o_chn, o_chtr, o_ent (per-wave tables, after the joins: S flip bits, then
+ * the u16 root list), o_frozen, o_froot, o_parent; dynamic LDS words of the launch; 1 if the replica is the kernel's case (else
+ * it is left to the general kernel); entries of the root list}.  Exposed so that the layout can be asserted on a CPU box. */
+int isingmc_plan_cluster_lds(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t has_long, uint32_t ufcap, uint32_t S, uint32_t out[13]);
 
 #ifdef __cplusplus
 }

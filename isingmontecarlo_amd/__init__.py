@@ -132,6 +132,7 @@ SYMBOLS = {
     "isingmc_get_launch_info": (C.c_int, [_vp, _P(_u32)]),
     "isingmc_last_rvb_ms": (C.c_int, [_vp, _P(C.c_float), _P(_u32)]),
     "isingmc_plan_geometry": (C.c_int, [_u32, _u32, _u32, _u32, _P(_u32)]),
+    "isingmc_plan_cluster_lds": (C.c_int, [_u32, _u32, _u32, _u32, _u32, _u32, _P(_u32)]),
 }
 
 _LIB = None

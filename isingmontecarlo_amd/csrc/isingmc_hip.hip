@@ -286,18 +286,19 @@ static void size_lds(isingmc_batch *b) {
 }
 
 // LDS plan of the dedicated cluster kernel (sse_cluster.hip.h): 16 waves, packed per-wave tables, 16-bit parents for
-// 16 N + (transverse ops seen so far + headroom) ids.  ok = false: the ids do not fit (the general kernel takes the launch).
+// 16 N + (transverse ops seen so far + headroom) ids.  ok = false: the ids do not fit (the general kernel takes the launch);
+// also when the largest id count the kernel would accept under that cap (want - 1) is not its case (cl_ids_fit: few
+// variables and many cuts, whose flip bits would overrun the per-wave tables).
 struct LeanPlan { bool ok; uint32_t ufcap; size_t lds_bytes; };
 static LeanPlan plan_lean(const isingmc_batch *b) {
     const DevBatch &D = b->dev;
     LeanPlan p{false, 0u, 0};
     if (!b->lean_cluster) return p;
-    const size_t fixed = cluster_fixed_words(D.N, D.nwords, D.Nb);
     const size_t ids_max = (size_t)16 * D.N + D.cap;
     size_t want = (size_t)16 * D.N + b->max_ntrans + b->max_ntrans / 16 + 384;
     if (want > ids_max) want = ids_max;
-    if (want > 65535) return p;
-    const size_t words = fixed + (want + 1) / 2 + (D.has_long ? 2 * ((want + 31) / 32) : 0);
+    if (want > 65535 || !cluster_ids_fit(D.N, (uint32_t)want - 1u, (uint32_t)want)) return p;
+    const size_t words = cluster_lds_words(D.N, D.nwords, D.Nb, (uint32_t)want, D.has_long != 0u);
     if (words > b->lds_total_words) return p;
     p.ok = true; p.ufcap = (uint32_t)want; p.lds_bytes = (4 * words + 7) & ~(size_t)7;
     return p;

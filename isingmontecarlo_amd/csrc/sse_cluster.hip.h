@@ -59,7 +59,7 @@ struct ClLds { // word offsets into lds_raw
     uint32_t o_ent;    // [16][N + 1] per (wave, variable): id | marker << 16 | touched << 24; after the joins: root list + flip bits
     uint32_t o_frozen, o_froot; // [ufwords] (h != 0)
     uint32_t o_parent; // [ufcap] u16
-    __device__ __forceinline__ void carve(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) {
+    __host__ __device__ __forceinline__ void carve(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) {
         uint32_t base = 0;
         o_tab = base; base += Nb + 1u;
         o_state = base; base += nwords;
@@ -76,6 +76,22 @@ struct ClLds { // word offsets into lds_raw
 // words in front of the parent table (host: LDS planning)
 static inline __host__ __device__ size_t cl_fixed_words(uint32_t N, uint32_t nwords, uint32_t Nb) {
     return (size_t)Nb + 1 + 2 * (size_t)nwords + 16 + 2 * SSE_MAX_CHUNKS + (size_t)SSE_CLW * (N + 1);
+}
+// whole dynamic LDS of a launch whose parent table holds ufcap ids (host: LDS planning)
+static inline __host__ __device__ size_t cl_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) {
+    return cl_fixed_words(N, nwords, Nb) + ((size_t)ufcap + 1) / 2 + (has_long ? 2 * (((size_t)ufcap + 31) / 32) : 0);
+}
+// Is a replica with N variables and S ids (16 N + C: initial segments and placeholders, cuts) this kernel's case?  The 16-bit
+// parent table must hold S + 1 entries (id S is the null id of empty slots) below the 16-bit limit, and after the joins the S flip
+// bits reuse the per-wave tables o_ent (16 (N + 1) words): with few variables and many cuts they would run into the tables behind.
+// The one test of the kernel (replicas outside it are flagged for the general kernel), of plan_lean() and of the host audit.
+static inline __host__ __device__ bool cl_ids_fit(uint32_t N, uint32_t S, uint32_t ufcap) {
+    return S < ufcap && S < 65535u && ((size_t)S + 31) / 32 <= (size_t)SSE_CLW * (N + 1);
+}
+// u16 entries of the root list behind the flip bits in the dead per-wave tables (0 when the bits fill them)
+static inline __host__ __device__ uint32_t cl_list_cap(uint32_t N, uint32_t S) {
+    const size_t tab = (size_t)SSE_CLW * (N + 1), bits = ((size_t)S + 31) / 32;
+    return bits < tab ? (uint32_t)(2 * (tab - bits)) : 0u;
 }
 
 __device__ __forceinline__ uint32_t cl_entry(const DevBatch &B, uint32_t b, uint32_t ce) {
@@ -123,7 +139,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     const uint32_t C = B.ntrans[r], M = B.cutoff[r], err = B.err[r];
     if (err) return;                                  // sticky error: the general kernel would not touch the replica either
     const uint32_t S = N + C + (uint32_t)(W - 1) * N; // ids: initial segments, cuts, range-boundary placeholders
-    if (n == 0 || C == 0u || S >= B.lds_ufcap || S >= 65535u) { // not this kernel's case: the general one follows up (id S itself is the
+    if (n == 0 || C == 0u || !cl_ids_fit(N, S, B.lds_ufcap)) { // not this kernel's case: the general one follows up (id S itself is the
                                                                // null id of empty slots: a table entry of its own, its flip bit stays 0)
         if (tid == 0) B.aux[r] = 1u;
         return;
@@ -346,7 +362,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     }
     // the per-wave tables are dead: their words now hold the flip bits (S bits) and, behind them, the list of roots (u16)
     const uint32_t o_bits = L.o_ent, o_list = L.o_ent + (S + 31u) / 32u;
-    const uint32_t list_cap = 2u * ((uint32_t)W * (N + 1u) - (S + 31u) / 32u);
+    const uint32_t list_cap = cl_list_cap(N, S);
     for (uint32_t i = tid; i < (S + 31u) / 32u; i += NT) LDSW(o_bits, i) = 0u;
     __syncthreads();
     SSE_STAMP(3);

@@ -1692,7 +1692,8 @@ hipError_t launch_sweep_w8(const LaunchCfg &c, const DevBatch &B, const SweepArg
 hipError_t launch_sweep_w16(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
 hipError_t launch_sweep_fast(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A); // sweep_fast.hip: sse_fast.hip.h, W = 4
 hipError_t launch_cluster(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);    // sweep_cluster.hip: sse_cluster.hip.h, W = 16
-size_t cluster_fixed_words(uint32_t N, uint32_t nwords, uint32_t Nb);                    // LDS words of that kernel in front of its parent table
+size_t cluster_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long); // dynamic LDS words of that kernel
+bool cluster_ids_fit(uint32_t N, uint32_t S, uint32_t ufcap);                          // ... and its gate on the ids of a replica
 // sweep_rvb.hip (sse_rvb_split.hip.h): the RVB sweep as a growth launch (16 waves) and a main launch (c.W = 4, 8 or 16 waves)
 hipError_t launch_rvb_grow(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
 hipError_t launch_rvb_main(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);

@@ -276,3 +276,62 @@ def test_row_stride_covers_every_whole_tile_access():
                                 last = max(last, pbeg + ((pend - pbeg + 64 * K - 1) // (64 * K)) * 64 * K - 1)
                             assert last < stride, (cap, W, Wmax, K, Wk, M, w, last, stride)
                             assert (last >> 1) + 64 < stride  # 16-bit ids of the dedicated cluster kernel (K >= 2): dword (p0 >> 1) + 32 j + lane
+
+
+def test_dedicated_cluster_kernel_lds_layout_and_gate():
+    """Bounds audit of the dedicated cluster kernel's LDS (csrc/sse_cluster.hip.h, through isingmc_plan_cluster_lds: ClLds::carve,
+    the launch's words, the kernel's gate cl_ids_fit and its root-list capacity).  After the joins the kernel reuses its per-wave
+    tables o_ent (16 (N + 1) words) for S flip bits (S = 16 N + cuts) and, behind them, a u16 list of roots.  Wherever the gate
+    accepts a replica:
+      * the flip bits end at or before o_frozen (= o_parent without a longitudinal field), the tables that follow o_ent;
+      * the root list fits behind the bits (no wrapped capacity);
+      * the 16-bit parent table holds S + 1 entries (id S is the null id of empty slots) inside the launch's LDS.
+    The gate must accept every replica that fits (it costs nothing at the headline size) and reject the few-variable, long-string
+    models whose flip-bit words (S + 31) / 32 the oracle measured beyond 16 (N + 1)."""
+    import isingmontecarlo_amd as im
+    lib = im.load_library()
+    out = (C.c_uint32 * 13)()
+
+    def plan(N, has_long, ufcap, S, Nb=None):
+        assert lib.isingmc_plan_cluster_lds(N, (N + 31) // 32, 4 * N if Nb is None else Nb, has_long, ufcap, S, out) == 0
+        return [int(x) for x in out]
+
+    rng = np.random.default_rng(11)
+    Ns = sorted(set(range(1, 257)) | set(range(257, 4096, 37)) | {511, 512, 1023, 1024, 1025, 2047, 2048, 4094, 4095})
+    accepted = rejected_by_bits = 0
+    for N in Ns:
+        tab = 16 * (N + 1)
+        bound = 32 * tab  # largest S whose flip bits fill the tables exactly
+        edges = [16 * N, 16 * N + 1, bound - 32, bound - 1, bound, bound + 1, 65534, 65535, 65536]
+        ufcaps = {65535, min(65535, 16 * N + 384), min(65535, bound + 1), min(65535, bound), min(65535, 16 * N + 3000 + 3000 // 16 + 384)}
+        for has_long in (0, 1):
+            for ufcap in sorted(ufcaps):
+                Ss = set(edges) | {ufcap - 1, ufcap, ufcap + 1} | {int(x) for x in rng.integers(16 * N, 70000, 4)}
+                for S in sorted(Ss):
+                    (o_tab, o_state, o_touch, o_misc, o_chn, o_chtr, o_ent, o_frozen, o_froot, o_parent,
+                     words, ok, list_cap) = plan(N, has_long, ufcap, S)
+                    fits = S < ufcap and S < 65535 and (S + 31) // 32 <= tab
+                    # the carve itself: regions in order, the per-wave tables directly in front of the frozen / parent tables
+                    assert o_tab == 0 and o_state == 4 * N + 1 and o_ent + tab == o_frozen <= o_froot <= o_parent
+                    if has_long:
+                        assert o_froot - o_frozen == o_parent - o_froot == (ufcap + 31) // 32
+                    assert o_parent + (ufcap + 1) // 2 <= words
+                    if ok:
+                        accepted += 1
+                        bits = (S + 31) // 32
+                        assert o_ent + bits <= o_frozen and o_ent + bits <= o_parent, (N, S, bits, tab)
+                        assert 0 <= list_cap <= 2 * tab and 2 * (o_ent + bits) + list_cap <= 2 * (o_ent + tab), (N, S, list_cap)
+                        assert 2 * o_parent + S + 1 <= 2 * words and o_parent + S // 2 < words  # parent[0..S] (the init writes words 0..S/2)
+                    else:
+                        rejected_by_bits += S < ufcap and S < 65535
+                    assert bool(ok) == fits, (N, has_long, ufcap, S, ok)  # and nothing that fits is refused
+    assert accepted > 5000 and rejected_by_bits > 500
+    # the headline size never meets the flip-bit bound: every S the 16-bit ids allow is accepted at N = 1024
+    assert all(plan(1024, 0, 65535, S)[11] for S in (16 * 1024, 40000, 65534))
+    # (S + 31) / 32 as the oracle measured it (60 timesteps, 4 replicas, Gamma = 1) on models that reach the bound: rejected
+    for N, words_lo, words_hi in [(8, 245, 256), (4, 104, 107), (2, 96, 97), (6, 136, 140)]:
+        for w in range(words_lo, words_hi + 1):
+            for S in (32 * w - 31, 32 * w):
+                assert plan(N, 0, 65535, S)[11] == 0 and plan(N, 1, 65535, S)[11] == 0, (N, S)
+    for w in range(85, 92):  # the control row (ring of 8 at beta = 200) stays with the kernel
+        assert plan(8, 0, 65535, 32 * w)[11] == 1

@@ -285,3 +285,67 @@ def test_cpp_example_host_side_builds_with_sanitizers(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-I" + os.path.join(root, "include"),
                            os.path.join(root, "examples", "small_qmc.cpp"), "-L" + libdir, "-lisingmc_hip", "-Wl,-rpath," + libdir,
                            "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-o", str(tmp_path / "small_qmc_san")])
+
+
+# ---- low temperature: few sites, long operator strings (the regime of tests/test_gpu_dense_end.py) ----
+# ED in the test itself (numpy eigh, at most 2^6 states) through the generator of the golden file
+def _ed_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_ed_golden", os.path.join(HERE, "golden", "make_ed_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_RING5 = [(0, 1, 0.7), (1, 2, -1.3), (2, 3, 1.9), (3, 4, -0.6), (4, 0, 1.1)]
+LOW_T = [  # name, sites, edges (a, b, J), gamma, h, beta
+    ("single_bond_b64", 2, [(0, 1, 1.0)], 1.0, 0.0, 64.0),
+    ("ring4_afm_b32", 4, [(i, (i + 1) % 4, 1.0) for i in range(4)], 1.0, 0.0, 32.0),
+    ("ring6_fm_long_b32", 6, [(i, (i + 1) % 6, -1.0) for i in range(6)], 1.0, 0.3, 32.0),
+    ("ring5_rand_b32", 5, _RING5, 1.2, 0.0, 32.0),
+]
+LOW_T_FLAGS = [0, O.FLAG_HEATBATH, O.FLAG_LOOP, O.FLAG_RVB]
+_LOW_T_Z = {}
+
+
+def _low_t_z(case, flags):
+    """z = (oracle - ED) / standard error of the mean over 16 replicas, for E, |m|, m^2 and sigma_x (cached per point)."""
+    key = (case[0], flags)
+    if key not in _LOW_T_Z:
+        name, n, edges, gamma, h, beta = case
+        ex = _ed_module().thermal(n, edges, gamma, h, beta)
+        m = O.Model(n, [[a, b] for a, b, _ in edges], [j for _, _, j in edges], gamma, h)
+        R = 16
+        reps = [O.Replica(m, 1 << 14, n, 555 + flags, r) for r in range(R)]
+        O.batch_timesteps(reps, 1000, [beta] * R, 1, flags)
+        for r in reps:
+            r.reset_accumulators()
+        O.batch_timesteps(reps, 8000, [beta] * R, 1, flags)
+        assert all(r.verify() for r in reps)
+        acc = np.array([r.accumulators() for r in reps], dtype=np.float64)
+        obs = {
+            "energy": -(acc[:, 0] / acc[:, 1]) / beta + m.offset,
+            "abs_m": acc[:, 2] / acc[:, 1] / n,
+            "m2": acc[:, 3] / acc[:, 1] / n ** 2,
+            "sx": acc[:, 6] / acc[:, 1] / (beta * gamma * n) - 1.0,
+        }
+        _LOW_T_Z[key] = {k: (x.mean() - ex[k]) / (x.std(ddof=1) / np.sqrt(R)) for k, x in obs.items()}
+    return _LOW_T_Z[key]
+
+
+@pytest.mark.parametrize("flags", LOW_T_FLAGS)
+@pytest.mark.parametrize("case", LOW_T, ids=[c[0] for c in LOW_T])
+def test_oracle_matches_exact_diagonalisation_at_low_temperature(case, flags):
+    """beta * Gamma of 32 to 64 on 2 to 6 sites: each op-string holds hundreds of ops per site.  Every observable within 4 sigma
+    of ED (fixed seeds: deterministic)."""
+    z = _low_t_z(case, flags)
+    for k, v in z.items():
+        assert abs(v) < 4.0, f"{case[0]} flags={flags} {k}: z = {v:+.2f}"
+
+
+def test_oracle_low_temperature_points_show_no_common_lean():
+    """Over all low-temperature points, per observable: |sum z| / sqrt(points) < 3 (a lean shared by the updates would pass
+    every single point and fail here)."""
+    for k in ("energy", "abs_m", "m2", "sx"):
+        zs = [_low_t_z(c, f)[k] for c in LOW_T for f in LOW_T_FLAGS]
+        assert abs(sum(zs)) / np.sqrt(len(zs)) < 3.0, f"{k}: {np.round(zs, 2)}"

@@ -50,7 +50,8 @@ extern "C" {
 #define ISINGMC_CFG_GLOBAL_TABLES 8u /* keep the per-variable scan tables (spins, cut ranks) in a per-replica HBM scratch instead of
                                         LDS.  Chosen automatically for models whose tables exceed LDS (N >~ 10^4 variables, e.g. a
                                         32^3 lattice); this flag forces the path on any model (testing).  Needs
-                                        ISINGMC_CFG_NO_LDS_TABLES or non-uniform couplings; slots_per_lane 1 or 4; no RVB updates. */
+                                        ISINGMC_CFG_NO_LDS_TABLES or non-uniform couplings; slots_per_lane 1 or 4; RVB updates only with
+                                        ISINGMC_CFG_RVB_GLOBAL_TABLES (without it they return ISINGMC_ENOTIMPL). */
 #define ISINGMC_CFG_NO_FAST_DIAG 16u /* run the diagonal pass through the general kernel even where the instruction-trimmed one
                                         (csrc/sse_fast.hip.h: uniform |J|, N <= 4096, 4 waves per replica) applies (testing / A-B timing) */
 /* bits 32 and 64 are retired (two experimental diagonal-to-cluster hand-overs): isingmc_create ignores them; do not reuse them */
@@ -65,6 +66,12 @@ extern "C" {
                                           table + per-replica sign bits (testing / A-B timing) */
 #define ISINGMC_CFG_RVB_FUSED 2048u /* run RVB sweeps through the fused kernel (growth and attempts in one launch, one replica per CU) even where
                                        the two-launch form applies (csrc/sse_rvb_split.hip.h); same results (testing / measurements) */
+#define ISINGMC_CFG_RVB_GLOBAL_TABLES 4096u /* RVB sweeps keep their per-variable tables (constant-op starts and positions, variables without
+                                             constant ops, variable -> sub-variable, edge -> boundary-bond entry) in a per-replica HBM scratch
+                                             (about 4 (2.5 N + E/2 + capacity) bytes per replica, allocated on the first such sweep) instead of LDS, on
+                                             any model: models whose scan tables live in HBM (ISINGMC_CFG_GLOBAL_TABLES) and models with more constant
+                                             ops than LDS holds.  Every RVB sweep then runs as a launch of its own (16 waves per replica), also inside
+                                             timesteps and with ISINGMC_CFG_FUSED_LAUNCH; never as growth + main launches.  Same results. */
 #define ISINGMC_CFG_FUSED_LAUNCH 2u  /* run whole timesteps inside one kernel launch instead of a diagonal-pass launch
                                         followed by an off-diagonal launch per timestep (same results, lower occupancy) */
 
@@ -291,7 +298,8 @@ int isingmc_set_steps_per_launch(isingmc_batch *b, uint64_t steps);
  * out[5]=1 if the edge table is staged in LDS, out[6]=bit 0: timesteps are issued as two launches (diagonal, rest); bit 1: per-variable
  * tables live in HBM (ISINGMC_CFG_GLOBAL_TABLES path); bit 2: the diagonal-pass launch is the trimmed kernel of sse_fast.hip.h; bits 3-4:
  * reserved (always 0); bit 5: the most recent cluster launch was the dedicated kernel; bit 6: the most recent RVB sweep ran as
- * growth + main launches (bits 16-23: waves per replica of that main launch); bits 8-15: waves per replica of the most recent
+ * growth + main launches (bits 16-23: waves per replica of that main launch); bit 7: the most recent RVB sweep kept its per-variable
+ * tables in HBM (ISINGMC_CFG_RVB_GLOBAL_TABLES); bits 8-15: waves per replica of the most recent
  * off-diagonal launch, out[7]=dynamic LDS bytes of the diagonal-pass launch */
 int isingmc_get_launch_info(const isingmc_batch *b, uint32_t out[8]);
 /* Host-only: the chunk grid and op-string row stride isingmc_create derives for `capacity` slots and kernels of W (diagonal

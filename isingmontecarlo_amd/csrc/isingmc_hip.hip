@@ -44,6 +44,8 @@ struct isingmc_batch {
     bool rvb_split = false;             // RVB sweeps run as a growth launch + a main launch (sse_rvb_split.hip.h) instead of the fused kernel
     uint32_t rvb_main_W = 4;            // waves per replica of that main launch
     bool last_rvb_split = false;        // ... and the last RVB sweep did
+    bool rvb_global = false;            // ISINGMC_CFG_RVB_GLOBAL_TABLES: every RVB sweep is a launch of its own with the tables in HBM (SSE_PASSES_RVB_G)
+    bool last_rvb_global = false;       // ... and the last RVB sweep was one
     std::vector<hipEvent_t> evpool;     // per-launch events of the split path (bounded, see run())
     float pass_ms[3] = {0.f, 0.f, 0.f}; // [0] diagonal-only launches, [1] all other launches of the last run, [2] of those: the RVB-sweep launches
     uint32_t pass_launches[3] = {0, 0, 0};
@@ -360,7 +362,26 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
     }
     if ((domask & SSE_DO_RVB) && b->generic) { b->err = "RVB updates are Ising-specific: not available with generic interactions"; return ISINGMC_ENOTIMPL; }
     if ((domask & SSE_DO_CLUSTER) && b->generic && !b->generic_sym) { b->err = "Cannot perform cluster updates on graphs that break ising symmetry."; return ISINGMC_ENOTIMPL; } // qmc_runner.rs:224-226
-    if ((domask & SSE_DO_RVB) && is_tg(b)) { b->err = "RVB updates keep their working set in LDS: not available for models whose per-variable tables live in HBM"; return ISINGMC_ENOTIMPL; }
+    if ((domask & SSE_DO_RVB) && is_tg(b) && !b->rvb_global) { b->err = "RVB updates keep their working set in LDS: not available for models whose per-variable tables live in HBM (set ISINGMC_CFG_RVB_GLOBAL_TABLES)"; return ISINGMC_ENOTIMPL; }
+    const bool rvb_g = (domask & SSE_DO_RVB) && b->rvb_global;
+    if (rvb_g && !b->dev.rvb_tbl) { // the per-replica table scratch of RVB_G launches, on the first one (no fall-back when it cannot be had)
+        const size_t words = rvb_tbl_words(b->dev.N, b->dev.E, b->dev.cap);
+        if (words > 0xFFFFFFFFull) { b->err = "RVB table scratch: more than 2^32 words per replica"; return ISINGMC_ECAPACITY; }
+        void *q = nullptr;
+        if (hipMalloc(&q, (size_t)b->dev.R * words * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            char buf[160];
+            snprintf(buf, sizeof buf, "RVB table scratch (ISINGMC_CFG_RVB_GLOBAL_TABLES): hipMalloc of %zu bytes failed", (size_t)b->dev.R * words * sizeof(uint32_t));
+            b->err = buf;
+            return ISINGMC_ENODEVICE;
+        }
+        b->dev.rvb_tbl = (uint32_t *)q;
+    }
+    if (rvb_g && rvb_global_lds_words(b->dev.N, b->dev.nwords, b->mode == SSE_MODE_LDS_EDGES ? b->dev.E : 0u, 0) > b->lds_total_words) {
+        b->err = "RVB scratch (ISINGMC_CFG_RVB_GLOBAL_TABLES): the spin-state bit arrays and the fixed RVB regions exceed LDS";
+        return ISINGMC_ENOTIMPL;
+    }
+    if (domask & SSE_DO_RVB) b->last_rvb_global = false;
     // Pending cluster flips: only a call whose first launch is the trimmed diagonal kernel may start on the un-flipped strings
     {
         const bool first_is_fast_diag = !b->fused_launch && (domask & SSE_DO_DIAG) && b->fast_diag && !(domask & SSE_DO_HEATBATH) && b->defer;
@@ -500,6 +521,19 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
     auto launch_rvb = [&](const LaunchCfg &lfused, const DevBatch &dfused, const SweepArgs &a) -> hipError_t {
         const uint32_t updates = a.rvb_updates ? a.rvb_updates : (b->dev.N + 1u) / 2u;
         b->last_rvb_split = false;
+        if (b->rvb_global) { // the tables in HBM (sweep_rvb_global.hip): 16 waves, the LDS scratch without the per-variable tables + one small growth area per wave
+            LaunchCfg lg = lfused;
+            lg.W = 16; lg.K = 4; lg.passes = SSE_PASSES_RVB_G;
+            lg.mode = b->mode == SSE_MODE_LDS_EDGES ? SSE_MODE_LDS_EDGES : SSE_MODE_GENERAL;
+            const uint32_t ledges = b->mode == SSE_MODE_LDS_EDGES ? b->dev.E : 0u;
+            size_t words = rvb_global_lds_words(b->dev.N, b->dev.nwords, ledges, 16);
+            if (words > b->lds_total_words) words = b->lds_total_words; // (fewer small growth areas; the large one always fits)
+            lg.lds_bytes = (4 * words) & ~(size_t)7;
+            DevBatch dg = b->dev;
+            dg.lds_words = (uint32_t)(lg.lds_bytes / 4);
+            b->last_rvb_global = true;
+            return launch_rvb_global(lg, dg, a);
+        }
         const size_t pstride = rvb_split_prod_stride(b->dev.Nb);
         if (b->rvb_split && a.nsteps == 1 && updates && pstride) {
             if (b->dev.rvb_prod_cap < updates) { // records of a sweep's attempts (grown on demand; no room -> the fused kernel)
@@ -532,7 +566,31 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         return launch_dev(lfused, dfused, a);
     };
     HIP_TRY(b, hipEventRecord(b->ev0, b->stream));
-    if (!split) {
+    if (!split && rvb_g && !rvb_only) {
+        // whole timesteps in one launch (ISINGMC_CFG_FUSED_LAUNCH) around an RVB sweep with its tables in HBM, which needs a launch of its
+        // own: per step, the passes in front of the sweep, the sweep, the passes behind it (the kernel's order: same epochs, same results)
+        const uint32_t pre = A.domask & (SSE_DO_DIAG | SSE_DO_HEATBATH | SSE_DO_GROW), post = A.domask & ~(pre | SSE_DO_RVB);
+        for (uint64_t done = 0; done < nsteps; ++done) {
+            SweepArgs a1 = A;
+            a1.nsteps = 1; a1.step0 = done; a1.sampling_freq = 0; a1.out_u32 = nullptr;
+            hipError_t e = hipSuccess;
+            if (pre & SSE_DO_DIAG) {
+                a1.domask = pre;
+                if ((e = launch_dev(lc, b->dev, a1)) != hipSuccess) return fail_launch(e);
+                launches++;
+            }
+            a1.domask = SSE_DO_RVB;
+            if ((e = launch_rvb(lc, b->dev, a1)) != hipSuccess) return fail_launch(e);
+            launches++;
+            if (post || (freq && (done + 1) % freq == 0)) {
+                SweepArgs a2 = A;
+                a2.domask = post; a2.nsteps = 1; a2.step0 = done;
+                if ((e = launch_dev(lc, b->dev, a2)) != hipSuccess) return fail_launch(e);
+                launches++;
+            }
+        }
+        b->pass_launches[1] = launches;
+    } else if (!split) {
         const uint64_t per = b->steps_per_launch ? b->steps_per_launch : nsteps;
         for (uint64_t done = 0; done < nsteps; done += per) {
             A.step0 = done;
@@ -580,7 +638,7 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
             if (timed) HIP_TRY(b, hipEventRecord(b->evpool[4 * done + 1], b->stream));
             const bool sample = freq && (done + 1) % freq == 0;
             uint32_t rest2 = rest;
-            if ((rest & SSE_DO_RVB) && !(rest & SSE_DO_LOOP)) {
+            if ((rest & SSE_DO_RVB) && (!(rest & SSE_DO_LOOP) || b->rvb_global)) {
                 // the RVB sweep as its own launch (register budget of its own: the all-passes kernel spills to scratch), then the
                 // cluster / free-spin launch in its usual geometry
                 SweepArgs ar = A;
@@ -596,7 +654,8 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
             if (rest2 || sample) {
                 SweepArgs a2 = A;
                 a2.domask = rest2; a2.nsteps = 1; a2.step0 = done;
-                if (rest2 != rest) { // behind an RVB launch: the plain off-diagonal kernel and geometry
+                if (rest2 != rest && !(rest2 & SSE_DO_LOOP)) { // behind an RVB launch: the plain off-diagonal kernel and geometry
+                    // (with a directed loop — only behind an RVB_G launch — the kernel of every pass below, as without the RVB launch)
                     LaunchCfg lo = lc;
                     lo.passes = SSE_PASSES_OFFDIAG;
                     const LdsPlan po = plan_lds(b, lc.W);
@@ -885,7 +944,8 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
         const size_t want = 4 * (o_cur + 2 + rvb_fixed_words(D.N, D.E) + (size_t)D.cap);
         b->lds_bytes_rvb = (want < (size_t)max_lds ? want : (size_t)max_lds) & ~(size_t)7;
     }
-    b->rvb_split = !generic && !TG && !is_pm(b) && !b->fused_launch && !(cfg->flags & ISINGMC_CFG_RVB_FUSED);
+    b->rvb_global = (cfg->flags & ISINGMC_CFG_RVB_GLOBAL_TABLES) != 0; // (the two-launch form keeps its tables in LDS: never with this flag)
+    b->rvb_split = !generic && !TG && !is_pm(b) && !b->fused_launch && !(cfg->flags & ISINGMC_CFG_RVB_FUSED) && !b->rvb_global;
     { // waves of the RVB main launch: as many as keep about 16 waves on a CU (its LDS footprint decides how many replicas share one)
         const size_t w4 = 4 * rvb_split_main_words(4, D.N, D.nwords, CL ? D.E : 0u, D.E, D.Nb);
         const size_t per_cu = w4 ? (size_t)max_lds / w4 : 0;
@@ -1013,6 +1073,7 @@ void isingmc_destroy(isingmc_batch *b) {
     pt_free(b);
     for (void *p : b->allocs) (void)hipFree(p);
     if (b->dev.rvb_prod) (void)hipFree(b->dev.rvb_prod);
+    if (b->dev.rvb_tbl) (void)hipFree(b->dev.rvb_tbl);
     for (hipEvent_t ev : b->evpool) (void)hipEventDestroy(ev);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
@@ -1369,7 +1430,7 @@ int isingmc_last_rvb_ms(isingmc_batch *b, float *ms, uint32_t *launches) {
 int isingmc_get_launch_info(const isingmc_batch *b, uint32_t out[8]) {
     if (!b || !out) return ISINGMC_EINVAL;
     out[0] = b->W; out[1] = (uint32_t)b->lds_bytes; out[2] = b->dev.lds_ufcap; out[3] = b->dev.nwords;
-    out[4] = b->K; out[5] = b->mode == SSE_MODE_LDS_EDGES ? 1u : 0u; out[6] = (b->fused_launch ? 0u : 1u) | (b->last_W_off << 8) | (is_tg(b) ? 2u : 0u) | (b->fast_diag ? 4u : 0u) | (b->last_lean ? 32u : 0u) | (b->last_rvb_split ? 64u : 0u) | ((b->last_rvb_split ? b->rvb_main_W : 0u) << 16); out[7] = (uint32_t)diag_lds_bytes(b);
+    out[4] = b->K; out[5] = b->mode == SSE_MODE_LDS_EDGES ? 1u : 0u; out[6] = (b->fused_launch ? 0u : 1u) | (b->last_W_off << 8) | (is_tg(b) ? 2u : 0u) | (b->fast_diag ? 4u : 0u) | (b->last_lean ? 32u : 0u) | (b->last_rvb_split ? 64u : 0u) | (b->last_rvb_global ? 128u : 0u) | ((b->last_rvb_split ? b->rvb_main_W : 0u) << 16); out[7] = (uint32_t)diag_lds_bytes(b);
     return ISINGMC_OK;
 }
 

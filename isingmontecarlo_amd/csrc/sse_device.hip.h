@@ -61,8 +61,11 @@ struct DevBatch {
     uint32_t *chunks;     // [R][2*SSE_MAX_CHUNKS]: per chunk of CH slots: occupied count, transverse-op count
     uint32_t CH, nchunks; // chunk size (multiple of 256 slots) and number of chunks covering cap
     uint32_t *uf_scratch; // [R][W*N+cap (+bit arrays)] union-find fallback in HBM
-    uint64_t kernarg_pad; // unused: keeps the fields below at their offsets modulo 64.  The register allocation of the general kernels
-                          // depends on where these kernel arguments fall: without this word a dozen of them gain scalar or vector spills
+    uint32_t *rvb_tbl;    // [R][rvb_tbl_words(N, E, cap)] the per-variable tables of RVB sweeps kept in HBM (SSE_PASSES_RVB_G, ISINGMC_CFG_RVB_GLOBAL_TABLES;
+                          // null until the first such sweep).  This 8-byte slot used to be an unused pad word, and it still keeps the fields below
+                          // at their offsets modulo 64: the register allocation of the general kernels depends on where these kernel arguments
+                          // fall (without the word a dozen of them gain scalar or vector spills), and a field at the end would grow the
+                          // workgroup-private copy of this struct that some kernels keep in scratch
     uint8_t *tbl;         // [R][tbl_stride] per-variable tables in HBM/L2 for models whose tables exceed LDS (MODE 2, see Tab)
     uint32_t tbl_stride;  // bytes per replica: Wmax*N*4 (scan records {rank, marker, touched} / spin bytes of the diagonal pass) + N, rounded up to 16
     uint32_t seed_lo, seed_hi, replica_offset;
@@ -1570,7 +1573,9 @@ namespace sse {
 #ifndef SSE_MIN_WAVES_PER_SIMD
 #define SSE_MIN_WAVES_PER_SIMD 1
 #endif
-enum { SSE_PASSES_ALL = 0, SSE_PASSES_DIAG = 1, SSE_PASSES_OFFDIAG = 2, SSE_PASSES_RVB = 3 }; // DIAG: diagonal pass + directed loop; OFFDIAG: cluster + free spins + sampling; RVB: the RVB sweep alone (its own register budget)
+enum { SSE_PASSES_ALL = 0, SSE_PASSES_DIAG = 1, SSE_PASSES_OFFDIAG = 2, SSE_PASSES_RVB = 3, SSE_PASSES_RVB_G = 4 }; // DIAG: diagonal pass + directed loop; OFFDIAG: cluster + free spins + sampling; RVB: the RVB sweep alone (its own register budget)
+// RVB_G: the RVB sweep alone with its per-variable tables in HBM (DevBatch::rvb_tbl) on any model: only the bit arrays of the Lds carve (as MODE 2) and the fixed
+// RVB scratch stay in LDS (sweep_rvb_global.hip: W = 16, K = 4, MODE 1 or 0 = the LDS edge table or the general bond records)
 template <int W, int PASSES>
 constexpr int sse_waves_per_simd() {
     if (PASSES == SSE_PASSES_DIAG) return W <= 4 ? 4 : (W <= 8 ? 2 : 1);
@@ -1581,9 +1586,11 @@ __global__ __launch_bounds__(W * 64, (sse_waves_per_simd<W, PASSES>())) void swe
     constexpr int NT = W * 64;
     constexpr bool CL = MODE == SSE_MODE_LDS_EDGES, TG = MODE == SSE_MODE_GLOBAL_TABLES || MODE == SSE_MODE_PM_GLOBAL_TABLES;
     constexpr bool PM = MODE == SSE_MODE_PM_LDS_TABLES || MODE == SSE_MODE_PM_GLOBAL_TABLES;
+    constexpr bool RG = PASSES == SSE_PASSES_RVB_G, RVB_ONLY = PASSES == SSE_PASSES_RVB || RG;
     static_assert(MODE != SSE_MODE_PM_LDS_TABLES || PASSES == SSE_PASSES_DIAG, "mode 3 is the diagonal launch of large +-J models");
+    static_assert(!RG || (!TG && !PM), "RVB_G decodes bonds through the LDS edge table or the general records");
     Lds<W> L;
-    L.carve(B.N, B.nwords, B.lds_ufcap, CL ? B.E : 0u, B.has_long, TG, PM ? B.pm_words : 0u, MODE == SSE_MODE_PM_LDS_TABLES);
+    L.carve(B.N, B.nwords, B.lds_ufcap, CL ? B.E : 0u, B.has_long, TG || RG, PM ? B.pm_words : 0u, MODE == SSE_MODE_PM_LDS_TABLES);
     const int tid = threadIdx.x;
     const uint32_t r = blockIdx.x;
     if (A.only_flagged && !B.aux[r]) return; // (uniform per workgroup; the flag is cleared at the end, behind the barriers below)
@@ -1606,7 +1613,7 @@ __global__ __launch_bounds__(W * 64, (sse_waves_per_simd<W, PASSES>())) void swe
     uint64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0;
     for (uint64_t step = 0; step < A.nsteps; ++step) {
         if (err) break;
-        if constexpr (PASSES != SSE_PASSES_OFFDIAG && PASSES != SSE_PASSES_RVB)
+        if constexpr (PASSES != SSE_PASSES_OFFDIAG && !RVB_ONLY)
         if (A.domask & SSE_DO_DIAG) {
             const Rng rng = make_rng(B, r, epoch);
             if (A.domask & SSE_DO_HEATBATH) diagonal_pass<W, K, CL, true, TG, PM>(B, L, r, rng, beta, M, n, ntrans, gr);
@@ -1618,16 +1625,16 @@ __global__ __launch_bounds__(W * 64, (sse_waves_per_simd<W, PASSES>())) void swe
                 if (want > M) { if (want > B.cap) { err = 1u; break; } M = want; }
             }
         }
-        if constexpr ((PASSES == SSE_PASSES_ALL || PASSES == SSE_PASSES_RVB) && !TG && !PM) // (RVB keeps its working set in LDS: refused by the host for MODE 2 models)
+        if constexpr (((PASSES == SSE_PASSES_ALL || PASSES == SSE_PASSES_RVB) && !TG && !PM) || RG) // (RVB keeps its working set in LDS except under RVB_G: refused by the host for MODE 2 models without it)
         if (A.domask & SSE_DO_RVB) { // qmc_ising.rs:705-752
             const uint32_t updates = A.rvb_updates ? A.rvb_updates : (B.N + 1u) / 2u;
-            last_out = rvb_pass<W, CL>(B, L, r, epoch, M, updates, gr, err);
+            last_out = rvb_pass<W, CL, RG>(B, L, r, epoch, M, updates, gr, err);
             epoch++;
             a4 += updates;
             if (err) break;
         }
         // the directed loop is one sequential walk: it runs in the small geometry of the diagonal launch
-        if constexpr (PASSES != SSE_PASSES_OFFDIAG && PASSES != SSE_PASSES_RVB)
+        if constexpr (PASSES != SSE_PASSES_OFFDIAG && !RVB_ONLY)
         if (A.domask & SSE_DO_LOOP) {
             const Rng rng = make_rng(B, r, epoch);
             last_out = loop_pass<W, CL, PM>(B, L, r, rng, M, n, gr, err);
@@ -1635,7 +1642,7 @@ __global__ __launch_bounds__(W * 64, (sse_waves_per_simd<W, PASSES>())) void swe
             a4 += last_out;
             if (err) break;
         }
-        if constexpr (PASSES != SSE_PASSES_DIAG && PASSES != SSE_PASSES_RVB) {
+        if constexpr (PASSES != SSE_PASSES_DIAG && !RVB_ONLY) {
         if (A.domask & SSE_DO_CLUSTER) {
             const Rng rng = make_rng(B, r, epoch);
             const uint32_t S_ids = (uint32_t)W * B.N + (uint32_t)ntrans;
@@ -1700,6 +1707,9 @@ hipError_t launch_rvb_main(const LaunchCfg &c, const DevBatch &B, const SweepArg
 size_t rvb_split_grow_fixed_words(uint32_t N, uint32_t nwords, uint32_t ledges);           // LDS words of the growth launch in front of the constant-op table
 size_t rvb_split_main_words(uint32_t W, uint32_t N, uint32_t nwords, uint32_t ledges, uint32_t E, uint32_t Nb); // LDS words of the main launch
 size_t rvb_split_prod_stride(uint32_t Nb);                                                // words per attempt in DevBatch::rvb_prod; 0 = the model is too large for the two-launch form
+// sweep_rvb_global.hip: the RVB sweep alone with its per-variable tables in HBM (SSE_PASSES_RVB_G; c.W = 16, c.K = 4; B.rvb_tbl allocated)
+hipError_t launch_rvb_global(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
+size_t rvb_global_lds_words(uint32_t N, uint32_t nwords, uint32_t ledges, uint32_t areas); // LDS words of that launch with `areas` small growth areas
 
 template <int W, int K, int CL, int PHASE, int PASSES>
 hipError_t launch_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {

@@ -61,12 +61,25 @@ struct RvbLds { // word offsets into lds_raw
     uint32_t gcap;      // entries of each gathered-op list (>= one wave's share of a gather step)
     uint32_t o_bm;      // [ceil(Nb/32)] bit per bond: it touches a sub-variable of the current attempt (two-launch form only: BM scans)
     uint32_t o_sadj, o_adjb; // [nsub+1] ranges into [..] the edges at each sub-variable, when the attempt's record carries them (0 = bonds_for_var in HBM)
+    uint32_t *tg;       // tables in HBM (rvb_pass<.., G = true>): this replica's DevBatch::rvb_tbl row; o_vstart, o_zero, o_v2s, o_bix, o_cps index it
+    uint32_t o_free;    // ... and the first free LDS word behind the scratch (the small growth areas start there)
 };
+
+// The five tables that scale with N, E or the op count — o_vstart, o_zero, o_v2s, o_bix, o_cps — are read and written through these
+// alone, in code with a template flag G in scope.  G = false: LDS (word offsets into lds_raw).  G = true: the replica's row of
+// DevBatch::rvb_tbl (word offsets into R.tg), with ordinary vector loads and stores and workgroup-scope atomics.  Only this replica's
+// workgroup touches its row: the hand-offs between waves are the __syncthreads() the LDS form has anyway, and those between lanes of
+// one wave the SSE_WAVE_FENCE()s (a fence without an address space: it orders global memory too).
+// (Macros rather than functions: with G a constant the compiler emits only the live arm, so the LDS form is the very expression it
+// always was — inlined helpers reorder the address arithmetic and shift the register allocation of the existing kernels.)
+#define RVB_TW(R, off, i) (G ? (R).tg[(off) + (i)] : LDSW(off, i))                                        // u32 element (lvalue)
+#define RVB_TH(tg, off, i) (G ? reinterpret_cast<uint16_t *>(tg)[2u * (off) + (i)] : LDSH(off, i))   // u16 element (lvalue)
+#define RVB_TADD(R, off, i, v) (G ? __hip_atomic_fetch_add((R).tg + (off) + (i), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : atomicAdd(&LDSW(off, i), v))
 // gathered-op info word: sub-variable of the first / second leg (SSE_GI_NONE = not a sub-variable), bond kind, two-site bit
 #define SSE_GI_NONE 0x3FFu
 #define SSE_GI_KIND_SHIFT 20
 #define SSE_GI_TWO (1u << 22)
-enum { RC_NSUB = 0, RC_NWIN = 1, RC_ACCEPT = 2, RC_GLEN = 3, RC_NEXTP = 4, RC_ERR = 5, RC_NZERO = 6, RC_SKIP = 7, RC_BROKE = 10, RC_NEXTA = 11 };
+enum { RC_NSUB = 0, RC_NWIN = 1, RC_ACCEPT = 2, RC_GLEN = 3, RC_NEXTP = 4, RC_ERR = 5, RC_NZERO = 6, RC_SKIP = 7, RC_BROKE = 10, RC_NEXTA = 11, RC_C = 12 };
 
 __device__ __forceinline__ double &ldsd(uint32_t off, uint32_t i) { return reinterpret_cast<double *>(lds_raw)[(off >> 1) + i]; }
 
@@ -78,8 +91,53 @@ __host__ __device__ inline uint32_t rvb_fixed_words(uint32_t N, uint32_t E) {
            6 * SSE_RVB_MAXCL + 2 * SSE_RVB_MAXWIN + SSE_RVB_BONDCAP + 3 * SSE_RVB_GCAP + (E + 1) / 2 + 16 + 8;
 }
 
-template <int W>
-__device__ __forceinline__ void rvb_carve(RvbLds &R, const Lds<W> &L, const DevBatch &B) {
+// words of RVB scratch in LDS with the five per-variable tables in HBM (rvb_carve<.., G = true>), in front of the small growth areas
+__host__ __device__ constexpr uint32_t rvb_global_fixed_words() {
+    return 2u + 4 * SSE_RVB_BONDCAP + 3 * SSE_RVB_MAXSUB + 6 * SSE_RVB_MAXCL + 2 * SSE_RVB_MAXWIN + SSE_RVB_BONDCAP + 3 * SSE_RVB_GCAP + 16 + 8;
+}
+// words per replica of DevBatch::rvb_tbl: vstart [N+1], zero [N], v2s [N] u16, bix [E] u16, cps [cap] (a sweep holds at most cutoff <= cap
+// constant ops, so the table cannot overflow), rounded up to 64 bytes
+__host__ __device__ inline size_t rvb_tbl_words(uint32_t N, uint32_t E, uint32_t cap) {
+    return ((size_t)(N + 1) + N + (N + 1) / 2 + (E + 1) / 2 + cap + 15) & ~(size_t)15;
+}
+
+template <int W, bool G = false>
+__device__ __forceinline__ void rvb_carve(RvbLds &R, const Lds<W> &L, const DevBatch &B, uint32_t r = 0) {
+    if constexpr (G) { // the five per-variable tables in this replica's row of B.rvb_tbl, everything else in LDS as below
+        const size_t words = rvb_tbl_words(B.N, B.E, B.cap);
+        R.tg = B.rvb_tbl + (size_t)r * words;
+        uint32_t t = 0;
+        R.o_vstart = t; t += B.N + 1;
+        R.o_zero = t; t += B.N;
+        R.o_v2s = t; t += (B.N + 1) / 2;
+        R.o_bix = t; t += (B.E + 1) / 2;
+        R.o_cps = t;
+        R.cps_cap = (uint32_t)(words - t);
+        uint32_t base = (L.o_cur + 1u) & ~1u;
+        R.o_bwb = base; base += 2 * SSE_RVB_BONDCAP;
+        R.o_bwa = base; base += 2 * SSE_RVB_BONDCAP;
+        R.adj_lds = 0u; R.o_adjs = R.o_adj = base;
+        R.o_sub = base; base += SSE_RVB_MAXSUB;
+        R.o_sfl = base; base += SSE_RVB_MAXSUB;
+        R.o_last = base; base += SSE_RVB_MAXSUB;
+        R.o_clv = base; base += SSE_RVB_MAXCL;
+        R.o_clf = base; base += SSE_RVB_MAXCL;
+        R.o_tog = base; base += 2 * SSE_RVB_MAXCL;
+        R.o_togs = base; base += 2 * SSE_RVB_MAXCL;
+        R.o_wfrom = base; base += SSE_RVB_MAXWIN;
+        R.o_wuntil = base; base += SSE_RVB_MAXWIN;
+        R.o_bk = base; base += SSE_RVB_BONDCAP;
+        base = (base + 1u) & ~1u;
+        R.o_bfw = base; R.o_bnw = base + 2 * SSE_RVB_SETCAP; R.o_bfk = base + 4 * SSE_RVB_SETCAP; R.o_bfv = base + 5 * SSE_RVB_SETCAP; R.o_bnk = base + 6 * SSE_RVB_SETCAP;
+        R.gcap = SSE_RVB_GCAP; R.o_bm = 0u; R.o_sadj = R.o_adjb = 0u;
+        R.o_glp = base; base += SSE_RVB_GCAP;
+        R.o_glw = base; base += SSE_RVB_GCAP;
+        R.o_gli = base; base += SSE_RVB_GCAP;
+        R.o_ctl = base; base += 16;
+        R.o_gout = base; base += 8;
+        R.o_free = (base + 1u) & ~1u;
+        return;
+    }
     uint32_t base = (L.o_cur + 1u) & ~1u; // even: doubles are 8-byte aligned
     R.o_bwb = base; base += 2 * SSE_RVB_BONDCAP;
     R.o_bwa = base; base += 2 * SSE_RVB_BONDCAP;
@@ -368,7 +426,8 @@ struct BSet {
     }
 };
 
-__device__ __forceinline__ uint32_t v2s_get(const RvbLds &R, uint32_t v) { return (uint32_t)LDSH(R.o_v2s, v); }
+template <bool G = false>
+__device__ __forceinline__ uint32_t v2s_get(const RvbLds &R, uint32_t v) { return (uint32_t)RVB_TH(R.tg, R.o_v2s, v); }
 
 // two-site diagonal weight of edge b for spins (sa, sb) (qmc_ising.rs:382-385 -> :863-875)
 template <bool CL, int W>
@@ -380,9 +439,9 @@ __device__ __forceinline__ double rvb_edge_w(const DevBatch &B, const Lds<W> &L,
 }
 
 // the "Now update bonds" block of calculate_flip_prob (rvb.rs:901-934) and mutate_graph (:560-592) for one variable
-template <bool CL, int W>
+template <bool CL, int W, bool G = false>
 __device__ __forceinline__ bool rvb_update_bonds(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t v, BSet &bs, bool with_after) {
-    const uint32_t sv = v2s_get(R, v);
+    const uint32_t sv = v2s_get<G>(R, v);
     if (sv == 0xFFFFu) return true;
     uint32_t i0, i1;
     sadj_range(R, B, v, sv, i0, i1);
@@ -390,13 +449,13 @@ __device__ __forceinline__ bool rvb_update_bonds(const DevBatch &B, const Lds<W>
         const uint32_t b = sadj_at(R, B, i);
         const Bd d = decode_bond<CL, W>(B, L, b);
         const uint32_t ov = d.a == v ? d.c : d.a;
-        const uint32_t so = v2s_get(R, ov);
+        const uint32_t so = v2s_get<G>(R, ov);
         if (so == 0xFFFFu) continue;
         const uint32_t fv = LDSW(R.o_sfl, sv), fo = LDSW(R.o_sfl, so);
         if (((fv ^ fo) & 2u) == 0u) {
             bs.remove(b);
         } else {
-            const uint32_t sa = v2s_get(R, d.a), sb = v2s_get(R, d.c);
+            const uint32_t sa = v2s_get<G>(R, d.a), sb = v2s_get<G>(R, d.c);
             uint32_t ba = (LDSW(R.o_sfl, sa) >> 2) & 1u, bb = (LDSW(R.o_sfl, sb) >> 2) & 1u;
             const uint32_t s0 = ba | (bb << 1);
             const double wbef = bond_weight(d, s0, s0);
@@ -414,7 +473,7 @@ __device__ __forceinline__ bool rvb_update_bonds(const DevBatch &B, const Lds<W>
 }
 
 // set_initial_bonds (rvb.rs:617-645) / the initial fill of mutate_graph (:366-380)
-template <bool CL, int W>
+template <bool CL, int W, bool G = false>
 __device__ __forceinline__ bool rvb_initial_bonds(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t nsub, BSet &bs, bool with_after) {
     for (uint32_t s = 0; s < nsub; ++s) {
         if (!(LDSW(R.o_sfl, s) & 2u)) continue;
@@ -425,9 +484,9 @@ __device__ __forceinline__ bool rvb_initial_bonds(const DevBatch &B, const Lds<W
             const uint32_t b = sadj_at(R, B, i);
             const Bd d = decode_bond<CL, W>(B, L, b);
             const uint32_t ov = d.a == v ? d.c : d.a;
-            const uint32_t so = v2s_get(R, ov);
+            const uint32_t so = v2s_get<G>(R, ov);
             if (so == 0xFFFFu || (LDSW(R.o_sfl, so) & 2u)) continue;
-            const uint32_t sa = v2s_get(R, d.a), sb = v2s_get(R, d.c);
+            const uint32_t sa = v2s_get<G>(R, d.a), sb = v2s_get<G>(R, d.c);
             uint32_t ba = (LDSW(R.o_sfl, sa) >> 2) & 1u, bb = (LDSW(R.o_sfl, sb) >> 2) & 1u;
             const uint32_t s0 = ba | (bb << 1);
             const double wbef = bond_weight(d, s0, s0);
@@ -444,12 +503,14 @@ __device__ __forceinline__ bool rvb_initial_bonds(const DevBatch &B, const Lds<W
 }
 
 // boundary-bond set run by a whole wave (probability pass): the entries of BSet, found through the edge -> entry table
+template <bool G = false>
 struct BSetW {
     uint32_t o_key, o_wb, o_wa, o_ix;
+    uint32_t *tg; // G: the row o_ix indexes (RVB_TH)
     uint32_t n;
     double tb, ta;
     __device__ __forceinline__ bool insert(uint32_t key, double wb, double wa) {
-        const uint32_t i = (uint32_t)LDSH(o_ix, key);
+        const uint32_t i = (uint32_t)RVB_TH(tg, o_ix, key);
         if (i != 0xFFFFu) {
             const double ob = ldsd(o_wb, i), oa = ldsd(o_wa, i);
             tb += wb - ob; ldsd(o_wb, i) = wb;
@@ -458,20 +519,20 @@ struct BSetW {
         }
         if (n >= SSE_RVB_BONDCAP) return false;
         LDSW(o_key, n) = key; ldsd(o_wb, n) = wb; ldsd(o_wa, n) = wa;
-        LDSH(o_ix, key) = (uint16_t)n;
+        RVB_TH(tg, o_ix, key) = (uint16_t)n;
         tb += wb; ta += wa;
         n++;
         return true;
     }
     __device__ __forceinline__ void remove(uint32_t key) {
-        const uint32_t i = (uint32_t)LDSH(o_ix, key);
+        const uint32_t i = (uint32_t)RVB_TH(tg, o_ix, key);
         if (i == 0xFFFFu) return;
         const uint32_t last = n - 1;
         const double wb = ldsd(o_wb, i), wa = ldsd(o_wa, i), wbl = ldsd(o_wb, last), wal = ldsd(o_wa, last);
         const uint32_t kl = LDSW(o_key, last);
         LDSW(o_key, i) = kl; ldsd(o_wb, i) = wbl; ldsd(o_wa, i) = wal;
-        LDSH(o_ix, kl) = (uint16_t)i;
-        LDSH(o_ix, key) = (uint16_t)0xFFFFu; // after the line above: the removed entry may be the last one itself
+        RVB_TH(tg, o_ix, kl) = (uint16_t)i;
+        RVB_TH(tg, o_ix, key) = (uint16_t)0xFFFFu; // after the line above: the removed entry may be the last one itself
         n--;
         tb -= wb; if (tb < 0.0) tb = 0.0;
         ta -= wa; if (ta < 0.0) ta = 0.0;
@@ -479,7 +540,7 @@ struct BSetW {
     __device__ __forceinline__ void clear(int lane) { // leave the table all-absent for the next attempt
         for (uint32_t base = 0; base < n; base += 64u) {
             const uint32_t i = base + (uint32_t)lane;
-            if (i < n) LDSH(o_ix, LDSW(o_key, i)) = (uint16_t)0xFFFFu;
+            if (i < n) RVB_TH(tg, o_ix, LDSW(o_key, i)) = (uint16_t)0xFFFFu;
         }
         n = 0; tb = 0.0; ta = 0.0;
     }
@@ -488,9 +549,9 @@ struct BSetW {
 // rvb_update_bonds / one variable of rvb_initial_bonds by a whole wave: lane k fetches neighbour k of v and works out what
 // happens to their bond; the set is then changed in neighbour order.  initial: only bonds from the cluster to outside it
 // are inserted (set_initial_bonds, rvb.rs:617-645), nothing is removed.
-template <bool CL, int W>
-__device__ __forceinline__ bool rvb_update_bonds_w(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t v, BSetW &bs, bool initial, int lane) {
-    const uint32_t sv = v2s_get(R, v);
+template <bool CL, int W, bool G = false>
+__device__ __forceinline__ bool rvb_update_bonds_w(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t v, BSetW<G> &bs, bool initial, int lane) {
+    const uint32_t sv = v2s_get<G>(R, v);
     if (sv == 0xFFFFu) return true;
     const uint32_t fv = LDSW(R.o_sfl, sv);
     uint32_t i0, i1;
@@ -501,7 +562,7 @@ __device__ __forceinline__ bool rvb_update_bonds_w(const DevBatch &B, const Lds<
         const uint32_t b = sadj_at(R, B, in ? i : i0);
         const Bd d = decode_bond<CL, W>(B, L, b);
         const uint32_t ov = d.a == v ? d.c : d.a;
-        const uint32_t so = v2s_get(R, ov);
+        const uint32_t so = v2s_get<G>(R, ov);
         const bool has = in & (so != 0xFFFFu);
         const uint32_t fo = LDSW(R.o_sfl, has ? so : 0u);
         const bool same = ((fv ^ fo) & 2u) == 0u;
@@ -529,24 +590,24 @@ __device__ __forceinline__ bool rvb_update_bonds_w(const DevBatch &B, const Lds<
 
 // find_overlapping_starts (rvb.rs:1125-1158) over cps[fp0 .. fp0+Lf) by a whole wave: the position lists are sorted, so the first entry >= p_start is a count, and the
 // run of overlapping segments ends at the first step whose test fails.  Calls f(index) for each overlapping segment, in order.
-template <typename F>
+template <bool G = false, typename F>
 __device__ __forceinline__ void rvb_overlaps_w(const RvbLds &R, uint32_t p_start, uint32_t p_end, uint32_t cutoff, uint32_t fp0, uint32_t Lf, int lane, F f) {
     uint32_t bin = 0;
     for (uint32_t base = 0; base < Lf; base += 64u) {
         const uint32_t i = base + (uint32_t)lane;
-        const uint32_t x = LDSW(R.o_cps, fp0 + (i < Lf ? i : 0u));
+        const uint32_t x = RVB_TW(R, R.o_cps, fp0 + (i < Lf ? i : 0u));
         bin += (uint32_t)popc64(sse_ballot((i < Lf) & (x < p_start)));
     }
     const uint32_t prev = wrap(bin + Lf - 1, Lf);
-    const uint32_t lowest = LDSW(R.o_cps, fp0 + prev);
+    const uint32_t lowest = RVB_TW(R, R.o_cps, fp0 + prev);
     const uint32_t off_start = wrap(p_start + cutoff - lowest, cutoff), off_end = wrap(p_end + cutoff - lowest, cutoff); // (positions are below the cutoff)
     uint32_t count = Lf;
     for (uint32_t base = 0; base < Lf; base += 64u) {
         const uint32_t step = base + (uint32_t)lane;
         const bool in = step < Lf;
         const uint32_t ip = wrap(prev + (in ? step : 0u), Lf);
-        const uint32_t p = LDSW(R.o_cps, fp0 + ip);
-        const uint32_t next_p = LDSW(R.o_cps, fp0 + wrap(ip + 1, Lf));
+        const uint32_t p = RVB_TW(R, R.o_cps, fp0 + ip);
+        const uint32_t next_p = RVB_TW(R, R.o_cps, fp0 + wrap(ip + 1, Lf));
         const uint32_t check_start = wrap(p + cutoff - lowest, cutoff), check_end = wrap(next_p + cutoff - lowest, cutoff);
         const bool has_overlap_start = check_start < off_start && off_start < check_end;
         const bool has_start_within = off_start < check_start && check_start < off_end;
@@ -562,13 +623,15 @@ __device__ __forceinline__ void rvb_overlaps_w(const RvbLds &R, uint32_t p_start
 
 // find_constants (rvb.rs:1160-1187): counting sort of the transverse-op positions by variable.
 // Returns C (number of constant ops) or 0xFFFFFFFF when the table does not fit in LDS.
-template <int W, bool CL>
+// (G: the tables in HBM; the counts and the fill go through workgroup-scope atomics on the replica's own row, whose order the
+// insertion sort at the end makes irrelevant)
+template <int W, bool CL, bool G = false>
 __device__ __forceinline__ uint32_t rvb_find_constants(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t r, uint32_t M) {
     constexpr int NT = W * 64;
     const int tid = threadIdx.x;
     const uint32_t N = B.N;
     const uint32_t *ops = B.ops + (size_t)r * B.stride;
-    for (uint32_t v = tid; v < N; v += NT) { LDSW(R.o_zero, v) = 0u; LDSH(R.o_v2s, v) = (uint16_t)0xFFFFu; }
+    for (uint32_t v = tid; v < N; v += NT) { RVB_TW(R, R.o_zero, v) = 0u; RVB_TH(R.tg, R.o_v2s, v) = (uint16_t)0xFFFFu; }
     if (R.adj_lds) {
         for (uint32_t v = tid; v <= N; v += NT) LDSH(R.o_adjs, v) = (uint16_t)B.adj_start[v];
         for (uint32_t i = tid; i < 2 * B.E; i += NT) LDSH(R.o_adj, i) = (uint16_t)B.adj[i];
@@ -579,7 +642,7 @@ __device__ __forceinline__ uint32_t rvb_find_constants(const DevBatch &B, const 
     for (uint32_t p = tid; p < M; p += NT) {
         const uint32_t wd = ops[p];
         const uint32_t v = (wd >> SSE_OP_BOND_SHIFT) - 1u - B.E; // (an empty slot wraps to a huge value)
-        if (v < N) atomicAdd(&LDSW(R.o_zero, v), 1u);
+        if (v < N) RVB_TADD(R, R.o_zero, v, 1u);
     }
     __syncthreads();
     // exclusive prefix over the variables, a block of NT at a time (wave scans + the waves' totals through o_tot); the counts array
@@ -590,7 +653,7 @@ __device__ __forceinline__ uint32_t rvb_find_constants(const DevBatch &B, const 
         uint32_t run = 0, nz = 0;
         for (uint32_t v0 = 0; v0 < N; v0 += NT) {
             const uint32_t v = v0 + (uint32_t)tid;
-            const uint32_t c = v < N ? LDSW(R.o_zero, v) : 0u;
+            const uint32_t c = v < N ? RVB_TW(R, R.o_zero, v) : 0u;
             const bool z = (v < N) & (c == 0u);
             uint32_t inc = c;
             for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= o) inc += y; }
@@ -605,40 +668,40 @@ __device__ __forceinline__ uint32_t rvb_find_constants(const DevBatch &B, const 
                 if (w2 < wave) { cbase += a; zbase += b; }
                 ctot += a; ztot += b;
             }
-            if (v < N) LDSW(R.o_vstart, v) = run + cbase + inc - c;
-            if (z) LDSW(R.o_zero, nz + zbase + (uint32_t)popc64(zm & lanemask_lt(lane))) = v;
+            if (v < N) RVB_TW(R, R.o_vstart, v) = run + cbase + inc - c;
+            if (z) RVB_TW(R, R.o_zero, nz + zbase + (uint32_t)popc64(zm & lanemask_lt(lane))) = v;
             run += ctot; nz += ztot;
             __syncthreads();
         }
-        if (tid == 0) { LDSW(R.o_vstart, N) = run; LDSW(R.o_ctl, RC_NZERO) = nz; }
+        if (tid == 0) { RVB_TW(R, R.o_vstart, N) = run; LDSW(R.o_ctl, RC_NZERO) = nz; if constexpr (G) LDSW(R.o_ctl, RC_C) = run; }
     }
     __syncthreads();
-    const uint32_t C = LDSW(R.o_vstart, N);
+    const uint32_t C = G ? LDSW(R.o_ctl, RC_C) : LDSW(R.o_vstart, N); // (G: through LDS, a uniform load of the HBM table could become a scalar load)
     if (C > R.cps_cap) return 0xFFFFFFFFu;
     // fill: vstart[v] doubles as the cursor and ends at the old vstart[v+1]; shift it back afterwards
     for (uint32_t p = tid; p < M; p += NT) {
         const uint32_t wd = ops[p];
         const uint32_t v = (wd >> SSE_OP_BOND_SHIFT) - 1u - B.E;
-        if (v < N) LDSW(R.o_cps, atomicAdd(&LDSW(R.o_vstart, v), 1u)) = p;
+        if (v < N) RVB_TW(R, R.o_cps, RVB_TADD(R, R.o_vstart, v, 1u)) = p;
     }
     __syncthreads();
     // vstart[v+1] := cursor[v], highest block first so that every element is read before it is overwritten
     for (int64_t v0 = (int64_t)((N - 1) / NT) * NT; v0 >= 0; v0 -= NT) {
         const uint32_t v = (uint32_t)v0 + tid;
-        const uint32_t x = v < N ? LDSW(R.o_vstart, v) : 0u;
+        const uint32_t x = v < N ? RVB_TW(R, R.o_vstart, v) : 0u;
         __syncthreads();
-        if (v < N) LDSW(R.o_vstart, v + 1) = x;
+        if (v < N) RVB_TW(R, R.o_vstart, v + 1) = x;
         __syncthreads();
     }
-    if (tid == 0) LDSW(R.o_vstart, 0) = 0u;
+    if (tid == 0) RVB_TW(R, R.o_vstart, 0) = 0u;
     __syncthreads();
     for (uint32_t v = tid; v < N; v += NT) { // insertion sort: the lists hold ~ beta*Gamma entries each
-        const uint32_t s = LDSW(R.o_vstart, v), e = LDSW(R.o_vstart, v + 1);
+        const uint32_t s = RVB_TW(R, R.o_vstart, v), e = RVB_TW(R, R.o_vstart, v + 1);
         for (uint32_t i = s + 1; i < e; ++i) {
-            const uint32_t x = LDSW(R.o_cps, i);
+            const uint32_t x = RVB_TW(R, R.o_cps, i);
             uint32_t j = i;
-            while (j > s && LDSW(R.o_cps, j - 1) > x) { LDSW(R.o_cps, j) = LDSW(R.o_cps, j - 1); j--; }
-            LDSW(R.o_cps, j) = x;
+            while (j > s && RVB_TW(R, R.o_cps, j - 1) > x) { RVB_TW(R, R.o_cps, j) = RVB_TW(R, R.o_cps, j - 1); j--; }
+            RVB_TW(R, R.o_cps, j) = x;
         }
     }
     __syncthreads();
@@ -670,29 +733,29 @@ __device__ __forceinline__ void load_rows(__amdgpu_buffer_rsrc_t rs, uint32_t p0
 }
 
 // info word of a gathered op (sub-variables of its legs, bond kind)
-template <int W, bool CL>
+template <int W, bool CL, bool G = false>
 __device__ __forceinline__ uint32_t rvb_info_word(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t wd) {
     const Bd d = decode_bond<CL, W>(B, L, wd ? sse_op_bond(wd) : 0u);
     const bool two = d.c != SSE_NO_VAR;
-    const uint32_t sa = v2s_get(R, d.a), sc = v2s_get(R, two ? d.c : d.a);
+    const uint32_t sa = v2s_get<G>(R, d.a), sc = v2s_get<G>(R, two ? d.c : d.a);
     const bool ma = sa != 0xFFFFu, mc = two & (sc != 0xFFFFu);
     return (ma ? sa : SSE_GI_NONE) | ((mc ? sc : SSE_GI_NONE) << 10) | (bd_kind(d) << SSE_GI_KIND_SHIFT) | (two ? SSE_GI_TWO : 0u);
 }
 // last-op search: one op at slot p
-template <int W, bool CL>
+template <int W, bool CL, bool G = false>
 __device__ __forceinline__ void rvb_last_op(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t p, uint32_t wd) {
     const Bd d = decode_bond<CL, W>(B, L, sse_op_bond(wd));
-    const uint32_t sa = v2s_get(R, d.a);
+    const uint32_t sa = v2s_get<G>(R, d.a);
     if (sa != 0xFFFFu) atomicMax(&LDSW(R.o_last, sa), ((p + 1u) << 1) | (sse_op_out(wd) & 1u));
     if (d.c != SSE_NO_VAR) {
-        const uint32_t sc = v2s_get(R, d.c);
+        const uint32_t sc = v2s_get<G>(R, d.c);
         if (sc != 0xFFFFu) atomicMax(&LDSW(R.o_last, sc), ((p + 1u) << 1) | ((sse_op_out(wd) >> 1) & 1u));
     }
 }
 // last-op search over the U rows a lane holds (row j = slot lo + wave*64*U + j*64 + lane; slots at or beyond the span's end arrive as 0) through the bond map: the wave
 // parks its hits in its own part of the (then idle) gathered-op lists and works them off densely; a wave with more hits than its
 // part holds takes them lane by lane.  lists_free = false: the lists are in use (the rare longer look-back of rvb_fetch).
-template <int W, bool CL, int U>
+template <int W, bool CL, int U, bool G = false>
 __device__ __forceinline__ void rvb_last_ops_bm(const DevBatch &B, const Lds<W> &L, const RvbLds &R, const uint32_t (&wl)[U], uint32_t lo, bool lists_free) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t p0 = lo + (uint32_t)(wave * 64 * U + lane);
@@ -718,13 +781,13 @@ __device__ __forceinline__ void rvb_last_ops_bm(const DevBatch &B, const Lds<W> 
         SSE_WAVE_FENCE();
         for (uint32_t base = 0; base < nh; base += 64u) {
             const uint32_t i = base + (uint32_t)lane;
-            if (i < nh) rvb_last_op<W, CL>(B, L, R, LDSW(R.o_glp, s0 + i), LDSW(R.o_glw, s0 + i));
+            if (i < nh) rvb_last_op<W, CL, G>(B, L, R, LDSW(R.o_glp, s0 + i), LDSW(R.o_glw, s0 + i));
         }
         SSE_WAVE_FENCE();
     } else {
 #pragma unroll
         for (int j = 0; j < U; ++j)
-            if ((hm[j] >> lane) & 1ull) rvb_last_op<W, CL>(B, L, R, p0 + (uint32_t)(j * 64), wl[j]);
+            if ((hm[j] >> lane) & 1ull) rvb_last_op<W, CL, G>(B, L, R, p0 + (uint32_t)(j * 64), wl[j]);
     }
 }
 
@@ -740,7 +803,7 @@ __device__ __forceinline__ void rvb_gather_rows(const DevBatch &B, uint32_t r, u
     const uint32_t end = M == 0u ? 0u : (until < M ? until + 1u : M); // slots [gp, end)
     load_rows<U>(ops_window(ops, end), gp + (uint32_t)(wave * 64 * U + lane), wd);
 }
-template <int W, bool CL, int U = 8, bool BM = false>
+template <int W, bool CL, int U = 8, bool BM = false, bool G = false>
 __device__ __forceinline__ void rvb_gather(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t r, uint32_t gp, uint32_t until,
                                            uint32_t M, uint32_t &gr, uint32_t (&wd)[U]) {
     constexpr int NT = W * 64;
@@ -759,7 +822,7 @@ __device__ __forceinline__ void rvb_gather(const DevBatch &B, const Lds<W> &L, c
         for (int j = 0; j < U; ++j) {
             if constexpr (BM) { info[j] = 0u; mm[j] = sse_ballot(bm_hit(R, wd[j])); } // (the info words follow once the list is complete)
             else {
-                info[j] = rvb_info_word<W, CL>(B, L, R, wd[j]);
+                info[j] = rvb_info_word<W, CL, G>(B, L, R, wd[j]);
                 mm[j] = sse_ballot((wd[j] != 0u) & (((info[j] & SSE_GI_NONE) != SSE_GI_NONE) | (((info[j] >> 10) & SSE_GI_NONE) != SSE_GI_NONE)));
             }
             cnt += popc64(mm[j]);
@@ -799,7 +862,7 @@ __device__ __forceinline__ void rvb_gather(const DevBatch &B, const Lds<W> &L, c
     }
     __syncthreads();
     if constexpr (BM)
-        for (uint32_t i = tid; i < glen; i += NT) LDSW(R.o_gli, i) = rvb_info_word<W, CL>(B, L, R, LDSW(R.o_glw, i));
+        for (uint32_t i = tid; i < glen; i += NT) LDSW(R.o_gli, i) = rvb_info_word<W, CL, G>(B, L, R, LDSW(R.o_glw, i));
     if (tid == 0) { LDSW(R.o_ctl, RC_GLEN) = glen; LDSW(R.o_ctl, RC_NEXTP) = (M == 0u || next > last) ? last + 1 : next; }
     __syncthreads();
 }
@@ -809,7 +872,7 @@ __device__ __forceinline__ void rvb_gather(const DevBatch &B, const Lds<W> &L, c
 // look-back chunk and the first window chunk are requested together, then one barrier publishes both.  o_last must be all
 // zero on entry and is left all zero.  RC_GLEN / RC_NEXTP as rvb_gather (a first chunk that overflows the list is left to
 // rvb_gather's smaller steps: RC_GLEN 0, RC_NEXTP = from).
-template <int W, bool CL, int UL = 4, int UG = 8, bool BM = false>
+template <int W, bool CL, int UL = 4, int UG = 8, bool BM = false, bool G = false>
 __device__ __forceinline__ void rvb_fetch(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t r, uint32_t from, uint32_t until,
                                           uint32_t M, uint32_t nsub, uint32_t &gr) {
     constexpr int NT = W * 64;
@@ -821,11 +884,11 @@ __device__ __forceinline__ void rvb_fetch(const DevBatch &B, const Lds<W> &L, co
     uint32_t wl[UL], wg[UG];
     load_rows<UL>(ops_window(ops, from), lo_b + (uint32_t)(wave * 64 * UL + lane), wl);
     load_rows<UG>(ops_window(ops, M == 0u ? 0u : last + 1u), from + (uint32_t)(wave * 64 * UG + lane), wg);
-    if constexpr (BM) rvb_last_ops_bm<W, CL, UL>(B, L, R, wl, lo_b, true);
+    if constexpr (BM) rvb_last_ops_bm<W, CL, UL, G>(B, L, R, wl, lo_b, true);
     else {
 #pragma unroll
         for (int j = 0; j < UL; ++j)
-            if (wl[j]) rvb_last_op<W, CL>(B, L, R, lo_b + (uint32_t)(wave * 64 * UL + j * 64 + lane), wl[j]);
+            if (wl[j]) rvb_last_op<W, CL, G>(B, L, R, lo_b + (uint32_t)(wave * 64 * UL + j * 64 + lane), wl[j]);
     }
     uint32_t info[UG];
     uint64_t mm[UG];
@@ -834,7 +897,7 @@ __device__ __forceinline__ void rvb_fetch(const DevBatch &B, const Lds<W> &L, co
     for (int j = 0; j < UG; ++j) {
         if constexpr (BM) { info[j] = 0u; mm[j] = sse_ballot(bm_hit(R, wg[j])); } // (the info words follow once the list is complete)
         else {
-            info[j] = rvb_info_word<W, CL>(B, L, R, wg[j]);
+            info[j] = rvb_info_word<W, CL, G>(B, L, R, wg[j]);
             mm[j] = sse_ballot((wg[j] != 0u) & (((info[j] & SSE_GI_NONE) != SSE_GI_NONE) | (((info[j] >> 10) & SSE_GI_NONE) != SSE_GI_NONE)));
         }
         cnt += popc64(mm[j]);
@@ -873,7 +936,7 @@ __device__ __forceinline__ void rvb_fetch(const DevBatch &B, const Lds<W> &L, co
     }
     __syncthreads();
     if constexpr (BM)
-        if (fits) for (uint32_t i = tid; i < total; i += NT) LDSW(R.o_gli, i) = rvb_info_word<W, CL>(B, L, R, LDSW(R.o_glw, i)); // (published by the barrier at the end)
+        if (fits) for (uint32_t i = tid; i < total; i += NT) LDSW(R.o_gli, i) = rvb_info_word<W, CL, G>(B, L, R, LDSW(R.o_glw, i)); // (published by the barrier at the end)
     SSE_STAMP(1);
     uint32_t hi = lo_b;
     while (LDSW(R.o_ctl, RC_SKIP)) { // (rare) the chunks before, one barrier round each, as rvb_state_at
@@ -883,11 +946,11 @@ __device__ __forceinline__ void rvb_fetch(const DevBatch &B, const Lds<W> &L, co
         const uint32_t lo = hi > span ? hi - span : 0u;
         uint32_t wx[UL];
         load_rows<UL>(ops_window(ops, hi), lo + (uint32_t)(wave * 64 * UL + lane), wx);
-        if constexpr (BM) rvb_last_ops_bm<W, CL, UL>(B, L, R, wx, lo, false);
+        if constexpr (BM) rvb_last_ops_bm<W, CL, UL, G>(B, L, R, wx, lo, false);
         else {
 #pragma unroll
             for (int j = 0; j < UL; ++j)
-                if (wx[j]) rvb_last_op<W, CL>(B, L, R, lo + (uint32_t)(wave * 64 * UL + j * 64 + lane), wx[j]);
+                if (wx[j]) rvb_last_op<W, CL, G>(B, L, R, lo + (uint32_t)(wave * 64 * UL + j * 64 + lane), wx[j]);
         }
         __syncthreads();
         hi = lo;
@@ -914,9 +977,9 @@ __device__ __forceinline__ void rvb_fetch(const DevBatch &B, const Lds<W> &L, co
 // change something — off-diagonal ops and the cluster's own toggles — are visited one by one; the diagonal ops between two
 // of them are counted (those sitting on a boundary bond) and checked (longitudinal ops inside the cluster) 64 at a time
 // against the boundary set as it stands.  Returns true when the product has dropped to zero (`broke`).
-template <int W, bool CL>
+template <int W, bool CL, bool G = false>
 __device__ __forceinline__ bool rvb_replay_prob(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t glen, uint32_t ntog, uint32_t &next_tog,
-                                                uint32_t &nb, double &mult, BSetW &bs, int lane) {
+                                                uint32_t &nb, double &mult, BSetW<G> &bs, int lane) {
     const double EPS = 2.220446049250313e-16;
     for (uint32_t base = 0; base < glen; base += 64u) {
         const uint32_t i = base + (uint32_t)lane;
@@ -931,7 +994,7 @@ __device__ __forceinline__ bool rvb_replay_prob(const DevBatch &B, const Lds<W> 
         const uint64_t evm0 = sse_ballot(valid & (offdiag | isb));
         uint32_t pos = 0;
         for (;;) {
-            const bool inb = valid & isedge & ((uint32_t)LDSH(R.o_bix, (valid & isedge) ? b : 0u) != 0xFFFFu);
+            const bool inb = valid & isedge & ((uint32_t)RVB_TH(R.tg, R.o_bix, (valid & isedge) ? b : 0u) != 0xFFFFu);
             const uint64_t inbm = sse_ballot(inb);
             const uint64_t ahead = ~lanemask_lt((int)pos) & (cnt < 64u ? lanemask_lt((int)cnt) : ~0ull);
             const uint64_t ev = evm0 & ~inbm & ahead;
@@ -972,8 +1035,8 @@ __device__ __forceinline__ bool rvb_replay_prob(const DevBatch &B, const Lds<W> 
             nb = 0;
             if (mult < EPS) return true;
             bool ok = true;
-            if (sae != SSE_GI_NONE) ok = rvb_update_bonds_w<CL, W>(B, L, R, LDSW(R.o_sub, sae), bs, false, lane);
-            if (ok && twoe && sce != SSE_GI_NONE) ok = rvb_update_bonds_w<CL, W>(B, L, R, LDSW(R.o_sub, sce), bs, false, lane);
+            if (sae != SSE_GI_NONE) ok = rvb_update_bonds_w<CL, W, G>(B, L, R, LDSW(R.o_sub, sae), bs, false, lane);
+            if (ok && twoe && sce != SSE_GI_NONE) ok = rvb_update_bonds_w<CL, W, G>(B, L, R, LDSW(R.o_sub, sce), bs, false, lane);
             if (!ok) { LDSW(R.o_ctl, RC_ERR) = 7u; return true; }
             SSE_WAVE_FENCE();
             pos = e + 1u;
@@ -985,7 +1048,7 @@ __device__ __forceinline__ bool rvb_replay_prob(const DevBatch &B, const Lds<W> 
 
 // get_propagated_substate_with_hint (fast_ops.rs:1027-1172): the spin of every sub-variable just before slot `from`
 // = the output bit of its last op in [0, from), else the p=0 state.  Cooperative backward search.
-template <int W, bool CL, int U = 4, bool BM = false>
+template <int W, bool CL, int U = 4, bool BM = false, bool G = false>
 __device__ __forceinline__ void rvb_state_at(const DevBatch &B, const Lds<W> &L, const RvbLds &R, uint32_t r, uint32_t from, uint32_t nsub,
                                              bool flip_by_cluster) {
     constexpr int NT = W * 64;
@@ -1000,11 +1063,11 @@ __device__ __forceinline__ void rvb_state_at(const DevBatch &B, const Lds<W> &L,
         const uint32_t lo = hi > span ? hi - span : 0u;
         uint32_t wx[U];
         load_rows<U>(ops_window(ops, hi), lo + (uint32_t)(wave * 64 * U + lane), wx);
-        if constexpr (BM) rvb_last_ops_bm<W, CL, U>(B, L, R, wx, lo, true); // (the gathered-op lists are idle: the gathers of this window come after)
+        if constexpr (BM) rvb_last_ops_bm<W, CL, U, G>(B, L, R, wx, lo, true); // (the gathered-op lists are idle: the gathers of this window come after)
         else {
 #pragma unroll
             for (int j = 0; j < U; ++j)
-                if (wx[j]) rvb_last_op<W, CL>(B, L, R, lo + (uint32_t)(wave * 64 * U + j * 64 + lane), wx[j]);
+                if (wx[j]) rvb_last_op<W, CL, G>(B, L, R, lo + (uint32_t)(wave * 64 * U + j * 64 + lane), wx[j]);
         }
         __syncthreads();
         // all found?
@@ -1091,7 +1154,7 @@ __device__ __forceinline__ GrowArea grow_area_large(const RvbLds &R) {
 }
 
 // start, cluster growth, sub-variables, windows of one attempt (rvb.rs:88-232, :1054-1123); run by a whole wave, uniform
-template <int W, bool CL, bool REG>
+template <int W, bool CL, bool REG, bool G = false>
 __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, const RvbLds &R, const GrowArea &A, RvbDraw g0, uint32_t C, uint32_t nzero,
                                          uint32_t M, int lane) {
     const uint32_t N = B.N;
@@ -1105,14 +1168,14 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
         uint32_t lo = 0, hi = N; // vstart[lo] <= choice < vstart[hi]
         while (hi - lo > 1u) {
             const uint32_t step = (hi - lo + 63u) / 64u, idx = lo + (uint32_t)lane * step;
-            const uint32_t x = LDSW(R.o_vstart, idx < hi ? idx : lo);
+            const uint32_t x = RVB_TW(R, R.o_vstart, idx < hi ? idx : lo);
             const uint32_t cnt = (uint32_t)popc64(sse_ballot((idx < hi) & (x <= choice))); // a prefix of the lanes (lane 0 always)
             const uint32_t nhi = lo + cnt * step;
             lo += (cnt - 1u) * step;
             hi = nhi < hi ? nhi : hi;
         }
         v0 = lo; f0 = choice;
-    } else { v0 = LDSW(R.o_zero, choice - C); f0 = SSE_NO_VAR; }
+    } else { v0 = RVB_TW(R, R.o_zero, choice - C); f0 = SSE_NO_VAR; }
     o = g.next(lane);
     unsigned long long bits = (unsigned long long)o.x | ((unsigned long long)o.y << 32);
     uint32_t csize = 1;
@@ -1141,7 +1204,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
         else { const uint32_t idx = bn.pick(u01(o.x), lane); v = bn.key_at(idx); flip = SSE_NO_VAR; bn.remove_at(idx); }
         if (cl.n >= cl.cap) { lerr = 7u; break; }
         cl.push(v, flip);
-        const uint32_t vs = LDSW(R.o_vstart, v), vl = LDSW(R.o_vstart, v + 1) - vs;
+        const uint32_t vs = RVB_TW(R, R.o_vstart, v), vl = RVB_TW(R, R.o_vstart, v + 1) - vs;
         if (flip != SSE_NO_VAR) {
             const uint32_t rel = flip - vs;
             push_adj(v, wrap(rel + vl - 1, vl) + vs, 1.0);
@@ -1155,7 +1218,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
             const bool nin = ni < i1;
             const Bd dl = decode_bond<CL, W>(B, L, adj_at(R, B, nin ? ni : i0));
             const uint32_t ovl = dl.a == v ? dl.c : dl.a;
-            const uint32_t osl = LDSW(R.o_vstart, ovl), oll = LDSW(R.o_vstart, ovl + 1) - osl;
+            const uint32_t osl = RVB_TW(R, R.o_vstart, ovl), oll = RVB_TW(R, R.o_vstart, ovl + 1) - osl;
             const double wl = dl.w * 0.5; // bond_mag = |J| (qmc_ising.rs:633-635)
             const uint32_t ncnt = i1 - nbase < 64u ? i1 - nbase : 64u;
             for (uint32_t k = 0; k < ncnt; ++k) {
@@ -1166,7 +1229,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
                 else if (flip != SSE_NO_VAR) {
                     const uint32_t rel = flip - vs;
                     const uint32_t finc = wrap(rel + 1, vl) + vs;
-                    rvb_overlaps_w(R, LDSW(R.o_cps, flip), LDSW(R.o_cps, finc), M, os, ol, lane, [&](uint32_t ip) { push_adj(ov, ip + os, weight); });
+                    rvb_overlaps_w<G>(R, RVB_TW(R, R.o_cps, flip), RVB_TW(R, R.o_cps, finc), M, os, ol, lane, [&](uint32_t ip) { push_adj(ov, ip + os, weight); });
                 } else {
                     for (uint32_t pi = os; pi < os + ol; ++pi) push_adj(ov, pi, weight);
                 }
@@ -1211,10 +1274,10 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
         const uint32_t v = cl.v_at(i), fi = cl.f_at(i);
         const uint32_t sv = (uint32_t)wv_find(A.o_sub, nsub, v, lane); // the list is this attempt's own: the shared var -> sub table is filled when its turn comes
         if (fi != SSE_NO_VAR) {
-            const uint32_t vs = LDSW(R.o_vstart, v), vl = LDSW(R.o_vstart, v + 1) - vs;
-            uint32_t t0 = LDSW(R.o_cps, fi), t1;
-            if (fi - vs + 1 >= vl) { LDSW(A.o_sfl, sv) |= 1u; t1 = LDSW(R.o_cps, vs); }
-            else t1 = LDSW(R.o_cps, fi + 1);
+            const uint32_t vs = RVB_TW(R, R.o_vstart, v), vl = RVB_TW(R, R.o_vstart, v + 1) - vs;
+            uint32_t t0 = RVB_TW(R, R.o_cps, fi), t1;
+            if (fi - vs + 1 >= vl) { LDSW(A.o_sfl, sv) |= 1u; t1 = RVB_TW(R, R.o_cps, vs); }
+            else t1 = RVB_TW(R, R.o_cps, fi + 1);
             for (int q = 0; q < 2; ++q) { // sorted insert: the entries above x move up by one (lane per entry)
                 const uint32_t x = q ? t1 : t0;
                 uint32_t pos = 0;
@@ -1282,7 +1345,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
 // Phases B-D of one attempt (calculate_flip_prob, accept, mutate_graph) whose growth products — sub-variables with their starting
 // flags, toggles, windows — are the lists R points at (R0: the replica's own scratch).  Returns true when the sweep has to stop.
 // BIG: scan steps of >= 4096 slots whatever the wave count (the main launch of the two-launch form, whose lists hold 64 * UG ops)
-template <int W, bool CL, bool BIG = false>
+template <int W, bool CL, bool BIG = false, bool G = false>
 __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, const RvbLds &R0, const RvbLds &R, uint32_t r, RvbDraw g,
                                             uint32_t nsub, uint32_t nwin, uint32_t ntog, uint32_t M, uint32_t &gr, uint32_t &nsucc) {
     constexpr int UG = BIG ? (W <= 4 ? SSE_RVB_UG4 : 8) : 8, UL = BIG ? (W <= 4 ? SSE_RVB_UL4 : (W <= 8 ? 8 : 4)) : 4; // (the lists of the main launch hold 64 * UG ops)
@@ -1290,17 +1353,18 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     uint32_t *ops = B.ops + (size_t)r * B.stride;
     SSE_STAMP_INIT;
-    for (uint32_t s = tid; s < nsub; s += blockDim.x) { LDSH(R0.o_v2s, LDSW(R.o_sub, s)) = (uint16_t)s; LDSW(R0.o_last, s) = 0u; }
+    for (uint32_t s = tid; s < nsub; s += blockDim.x) { RVB_TH(R0.tg, R0.o_v2s, LDSW(R.o_sub, s)) = (uint16_t)s; LDSW(R0.o_last, s) = 0u; }
     __syncthreads();
 
     // ================= phase B: calculate_flip_prob (rvb.rs:649-946) over the windows =================
     double mult = 1.0;             // wave 0
     uint32_t nb = 0, next_tog = 0; // wave 0
-    BSetW bw;
+    BSetW<G> bw;
     bw.o_key = R.o_bk; bw.o_wb = R.o_bwb; bw.o_wa = R.o_bwa; bw.o_ix = R.o_bix; bw.n = 0; bw.tb = 0.0; bw.ta = 0.0;
+    if constexpr (G) bw.tg = R.tg;
     for (uint32_t wi = 0; wi < nwin; ++wi) {
         const uint32_t from = LDSW(R.o_wfrom, wi), until = LDSW(R.o_wuntil, wi);
-        rvb_fetch<W, CL, UL, UG, BM>(B, L, R, r, from, until, M, nsub, gr);
+        rvb_fetch<W, CL, UL, UG, BM, G>(B, L, R, r, from, until, M, nsub, gr);
         SSE_STAMP(8);
         if (wave == 0 && wi == 0 && from == 0) { // set_initial_bonds (rvb.rs:617-645): the cluster's bonds to the outside, in order
             bool ok = true;
@@ -1310,7 +1374,7 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
                 while (m && ok) {
                     const uint32_t k = (uint32_t)__ffsll((long long)m) - 1u;
                     m &= m - 1;
-                    ok = rvb_update_bonds_w<CL, W>(B, L, R, LDSW(R.o_sub, base + k), bw, true, lane);
+                    ok = rvb_update_bonds_w<CL, W, G>(B, L, R, LDSW(R.o_sub, base + k), bw, true, lane);
                 }
             }
             if (!ok) LDSW(R.o_ctl, RC_ERR) = 7u;
@@ -1322,14 +1386,14 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
             uint32_t wrow[UG];
             if (BIG && more) rvb_gather_rows<W, UG>(B, r, gp, until, M, wrow); // on their way while wave 0 replays this batch
             if (wave == 0 && !LDSW(R.o_ctl, RC_ERR)) {
-                if (rvb_replay_prob<W, CL>(B, L, R, glen, ntog, next_tog, nb, mult, bw, lane)) LDSW(R.o_ctl, RC_BROKE) = 1u;
+                if (rvb_replay_prob<W, CL, G>(B, L, R, glen, ntog, next_tog, nb, mult, bw, lane)) LDSW(R.o_ctl, RC_BROKE) = 1u;
             }
             __syncthreads(); // the lists are free again; everybody learns whether the product is already zero
             SSE_STAMP(10);
             if (LDSW(R.o_ctl, RC_BROKE) || LDSW(R.o_ctl, RC_ERR)) { done = true; break; }
             if (!more) break;
             if (!BIG) rvb_gather_rows<W, UG>(B, r, gp, until, M, wrow);
-            rvb_gather<W, CL, UG, BM>(B, L, R, r, gp, until, M, gr, wrow);
+            rvb_gather<W, CL, UG, BM, G>(B, L, R, r, gp, until, M, gr, wrow);
             SSE_STAMP(9);
         }
         if (done) break;
@@ -1358,17 +1422,17 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
         uint32_t nt2 = 0;
         for (uint32_t wi = 0; wi < nwin; ++wi) {
             const uint32_t from = LDSW(R.o_wfrom, wi), until = LDSW(R.o_wuntil, wi);
-            rvb_state_at<W, CL, UL, BM>(B, L, R, r, from, nsub, true); // substate ^= cluster_state (:396-399, :315-318)
+            rvb_state_at<W, CL, UL, BM, G>(B, L, R, r, from, nsub, true); // substate ^= cluster_state (:396-399, :315-318)
             SSE_STAMP(8);
             if (tid == 0 && wi == 0 && from == 0) {
-                if (!rvb_initial_bonds<CL, W>(B, L, R, nsub, bs, false)) LDSW(R.o_ctl, RC_ERR) = 7u;
+                if (!rvb_initial_bonds<CL, W, G>(B, L, R, nsub, bs, false)) LDSW(R.o_ctl, RC_ERR) = 7u;
             }
             uint32_t gp = from;
             for (;;) {
                 SSE_STAMP(12);
                 uint32_t wrow[UG];
                 rvb_gather_rows<W, UG>(B, r, gp, until, M, wrow);
-                rvb_gather<W, CL, UG, BM>(B, L, R, r, gp, until, M, gr, wrow);
+                rvb_gather<W, CL, UG, BM, G>(B, L, R, r, gp, until, M, gr, wrow);
                 SSE_STAMP(9);
                 const uint32_t glen = LDSW(R.o_ctl, RC_GLEN);
                 gp = LDSW(R.o_ctl, RC_NEXTP);
@@ -1377,14 +1441,14 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
                         const uint32_t p = LDSW(R.o_glp, i), wd = LDSW(R.o_glw, i);
                         const uint32_t b = sse_op_bond(wd), in = sse_op_in(wd), out = sse_op_out(wd);
                         const Bd d = decode_bond<CL, W>(B, L, b);
-                        const uint32_t sa = v2s_get(R, d.a), sc = d.c != SSE_NO_VAR ? v2s_get(R, d.c) : 0xFFFFu;
+                        const uint32_t sa = v2s_get<G>(R, d.a), sc = d.c != SSE_NO_VAR ? v2s_get<G>(R, d.c) : 0xFFFFu;
                         const bool at_flip = nt2 < ntog && p == LDSW(R.o_tog, nt2);
                         if (b < B.E && bs.find(b) >= 0) {
                             // rotate the boundary op onto a boundary bond drawn by weight (:414-432)
                             const uint4 o = g.next();
                             const uint32_t nbnd = LDSW(bs.o_key, bs.pick_before(u01(o.x)));
                             const Bd nd = decode_bond<CL, W>(B, L, nbnd);
-                            const uint32_t s2 = ((LDSW(R.o_sfl, v2s_get(R, nd.a)) >> 2) & 1u) | (((LDSW(R.o_sfl, v2s_get(R, nd.c)) >> 2) & 1u) << 1);
+                            const uint32_t s2 = ((LDSW(R.o_sfl, v2s_get<G>(R, nd.a)) >> 2) & 1u) | (((LDSW(R.o_sfl, v2s_get<G>(R, nd.c)) >> 2) & 1u) << 1);
                             ops[p] = sse_op_make(nbnd, s2, s2);
                             continue;
                         }
@@ -1412,8 +1476,8 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
                                 continue; // diagonal and untouched by the cluster (:513-514)
                             }
                         }
-                        bool ok = rvb_update_bonds<CL, W>(B, L, R, d.a, bs, false);
-                        if (ok && d.c != SSE_NO_VAR) ok = rvb_update_bonds<CL, W>(B, L, R, d.c, bs, false);
+                        bool ok = rvb_update_bonds<CL, W, G>(B, L, R, d.a, bs, false);
+                        if (ok && d.c != SSE_NO_VAR) ok = rvb_update_bonds<CL, W, G>(B, L, R, d.c, bs, false);
                         if (!ok) { LDSW(R.o_ctl, RC_ERR) = 7u; break; }
                     }
                 }
@@ -1428,31 +1492,34 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
         nsucc++;
     }
     __syncthreads();
-    for (uint32_t s = tid; s < nsub; s += blockDim.x) LDSH(R.o_v2s, LDSW(R.o_sub, s)) = (uint16_t)0xFFFFu;
+    for (uint32_t s = tid; s < nsub; s += blockDim.x) RVB_TH(R.tg, R.o_v2s, LDSW(R.o_sub, s)) = (uint16_t)0xFFFFu;
     __syncthreads();
     if (LDSW(R.o_ctl, RC_ERR)) return true;
     return false;
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int W, bool CL>
+// G: the five per-variable tables in the replica's row of B.rvb_tbl (SSE_PASSES_RVB_G launches), every other region in LDS
+template <int W, bool CL, bool G = false>
 __device__ __forceinline__ uint32_t rvb_pass(const DevBatch &B, const Lds<W> &L, uint32_t r, uint64_t epoch, uint32_t M, uint32_t updates,
                                              uint32_t &gr, uint32_t &err) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     uint32_t *ops = B.ops + (size_t)r * B.stride;
     RvbLds R0;
-    rvb_carve<W>(R0, L, B);
+    rvb_carve<W, G>(R0, L, B, r);
+    if constexpr (G)
+        if (R0.o_free > B.lds_words) { err = 5u; return 0u; } // the launch's LDS does not hold the fixed scratch (host and carve disagree): loud, never cut off
     if (tid == 0) { LDSW(R0.o_ctl, RC_ERR) = 0u; LDSW(R0.o_ctl, RC_SKIP) = 0u; LDSW(R0.o_ctl, RC_BROKE) = 0u; }
-    for (uint32_t i = tid; i < B.E; i += blockDim.x) LDSH(R0.o_bix, i) = (uint16_t)0xFFFFu;
+    for (uint32_t i = tid; i < B.E; i += blockDim.x) RVB_TH(R0.tg, R0.o_bix, i) = (uint16_t)0xFFFFu;
     __syncthreads();
     SSE_STAMP_INIT; // diagnostic builds: 6 constants table, 7 growth, 8 states, 9 gathers, 10 replay (probability), 11 accept, 12 replay (mutation)
-    const uint32_t C = rvb_find_constants<W, CL>(B, L, R0, r, M);
+    const uint32_t C = rvb_find_constants<W, CL, G>(B, L, R0, r, M);
     SSE_STAMP(6);
     if (C == 0xFFFFFFFFu) { err = 6u; return 0u; } // constant-op table does not fit in LDS
     const uint32_t nzero = LDSW(R0.o_ctl, RC_NZERO);
     uint32_t nsucc = 0;
-    // small growth areas behind the used part of the constant-op table: as many as fit, at most one per wave
-    const uint32_t slots0 = (R0.o_cps + C + 1u) & ~1u;
+    // small growth areas behind the used part of the constant-op table (G: behind the scratch): as many as fit, at most one per wave
+    const uint32_t slots0 = G ? R0.o_free : (R0.o_cps + C + 1u) & ~1u;
     uint32_t P = B.lds_words > slots0 ? (B.lds_words - slots0) / SSE_RVB_SLOT_WORDS : 0u;
     if (P > (uint32_t)W) P = (uint32_t)W;
     if (P > B.rvb_growers) P = B.rvb_growers;
@@ -1467,7 +1534,7 @@ __device__ __forceinline__ uint32_t rvb_pass(const DevBatch &B, const Lds<W> &L,
     if (P && (uint32_t)wave < P && a0 + (uint32_t)wave < updates) {
         RvbDraw g;
         g.k0 = B.seed_lo; g.k1 = B.seed_hi; g.replica = B.rid ? B.rid[r] : B.replica_offset + r; g.epoch_lo = (uint32_t)epoch; g.attempt = a0 + (uint32_t)wave; g.k = 0;
-        rvb_grow<W, CL, true>(B, L, R0, grow_area_small(slots0 + (uint32_t)wave * SSE_RVB_SLOT_WORDS), g, C, nzero, M, lane);
+        rvb_grow<W, CL, true, G>(B, L, R0, grow_area_small(slots0 + (uint32_t)wave * SSE_RVB_SLOT_WORDS), g, C, nzero, M, lane);
     }
     __syncthreads();
     SSE_STAMP(7);
@@ -1478,7 +1545,7 @@ __device__ __forceinline__ uint32_t rvb_pass(const DevBatch &B, const Lds<W> &L,
         GrowArea A = P ? grow_area_small(slots0 + aj * SSE_RVB_SLOT_WORDS) : big;
         if (!P || LDSW(A.o_out, GO_ERR)) { // no room for small areas, or this cluster outgrew its own: the large area
             A = big;
-            if (wave == 0) rvb_grow<W, CL, false>(B, L, R0, big, g, C, nzero, M, lane);
+            if (wave == 0) rvb_grow<W, CL, false, G>(B, L, R0, big, g, C, nzero, M, lane);
             __syncthreads();
             SSE_STAMP(7);
         }
@@ -1487,7 +1554,7 @@ __device__ __forceinline__ uint32_t rvb_pass(const DevBatch &B, const Lds<W> &L,
         g.k = LDSW(A.o_out, GO_K);
         RvbLds R = R0; // this attempt's lists
         R.o_sub = A.o_sub; R.o_sfl = A.o_sfl; R.o_tog = A.o_tog; R.o_togs = A.o_togs; R.o_wfrom = A.o_wfrom; R.o_wuntil = A.o_wuntil;
-        if (rvb_attempt<W, CL>(B, L, R0, R, r, g, nsub, nwin, ntog, M, gr, nsucc)) { stop = true; break; }
+        if (rvb_attempt<W, CL, false, G>(B, L, R0, R, r, g, nsub, nwin, ntog, M, gr, nsucc)) { stop = true; break; }
     } // attempts of the batch, in order
     } // batches
     __syncthreads();

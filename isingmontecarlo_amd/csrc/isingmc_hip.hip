@@ -25,7 +25,7 @@ struct isingmc_batch {
     uint32_t rvb_updates = 0;
     bool w8_ok = false;                 // an 8-wave off-diagonal geometry without LDS union-find fits (and the row stride allows it)
     uint32_t *d_acc_row = nullptr;
-    size_t lds_bytes = 0, lds_bytes_rvb = 0, lds_fixed_words_ = 0, lds_total_words = 0;
+    size_t lds_words = 0, lds_words_rvb = 0, lds_words_diag = 0, lds_total_words = 0; // LDS words: general, RVB and diagonal launches; all of LDS
     uint32_t max_ntrans = 0, uf_ids_limit = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -33,9 +33,9 @@ struct isingmc_batch {
     float last_ms = 0.f;
     uint32_t last_launches = 0;
     bool fast_diag = false;             // the diagonal-pass launch uses sse_fast.hip.h (headline geometry: LDS edge tables, 4 waves, N <= 4096)
-    size_t lds_bytes_fast = 0;
+    size_t lds_words_fast = 0;
     bool fused_launch = false;          // ISINGMC_CFG_FUSED_LAUNCH: whole timesteps in one kernel (no diagonal-only launches)
-    size_t lds_bytes_pm_diag = 0;       // +-J decode: LDS of the diagonal launch with its per-wave spin bytes in LDS (0 = they do not fit: mode 4 there too)
+    size_t lds_words_pm_diag = 0;       // +-J decode: LDS of the diagonal launch with its per-wave spin bytes in LDS (0 = they do not fit: mode 4 there too)
     bool lean_cluster = false;          // cluster (+ free spins + sampling) launches use sse_cluster.hip.h when their ids fit its LDS union-find
     bool last_lean = false;             // ... and the last such launch did
     bool defer = false;                 // ... leaving its flips as one byte per slot for the next (trimmed) diagonal launch to apply
@@ -236,36 +236,59 @@ static int ensure_materialized(isingmc_batch *b) {
     return ISINGMC_OK;
 }
 
-static size_t lds_fixed_words(uint32_t W, uint32_t N, uint32_t nwords, uint32_t ledges, bool tg = false, uint32_t pm_words = 0) {
-    // mirrors Lds<W>::carve up to and including o_cl: state, touched bits, touched bytes, round buffers, misc, chunk counters,
-    // edge table, per-wave rank tables (u16) and marker tables (u8); with the tables in HBM (tg) only the bit arrays remain
-    // (+ the coupling signs of the +-J decode)
-    if (tg) return (size_t)nwords * 2 + 4 * W + 16 + 2 * SSE_MAX_CHUNKS + ledges + pm_words;
-    return (size_t)nwords * 2 + ((size_t)N + 3) / 4 + 4 * W + 16 + 2 * SSE_MAX_CHUNKS + ledges + ((size_t)W * N + 1) / 2 + ((size_t)W * N + 3) / 4;
-}
-// dynamic LDS of the fast diagonal-pass launch (mirrors Lds<4>::carve up to o_cur, then FastLds: sse_fast.hip.h fast_carve)
-static size_t fast_lds_bytes(uint32_t N, uint32_t nwords, uint32_t E, uint32_t Nb) {
-    const size_t o_edges = (size_t)nwords * 2 + ((size_t)N + 3) / 4 + 4 * 4 + 16 + 2 * SSE_MAX_CHUNKS;
-    size_t words = ((o_edges + 3) & ~(size_t)3) + 16 + Nb + N + 64;
-    if (words < o_edges + E) words = o_edges + E; // the directed loop behind the pass stages the compact edge table there
-    return (4 * words + 7) & ~(size_t)7;
-}
 static bool is_tg(const isingmc_batch *b) { return b->mode == SSE_MODE_GLOBAL_TABLES || b->mode == SSE_MODE_PM_GLOBAL_TABLES; }
 static bool is_pm(const isingmc_batch *b) { return b->mode == SSE_MODE_PM_GLOBAL_TABLES; }
-// dynamic LDS of the diagonal-pass launch: the fixed regions up to the per-wave tables, which it uses as [W][N] spin bytes
-static size_t diag_lds_bytes(const isingmc_batch *b) {
-    const size_t words = is_tg(b) ? b->lds_fixed_words_ : b->lds_fixed_words_ - ((size_t)b->W * b->dev.N + 1) / 2;
-    return (4 * words + 7) & ~(size_t)7;
+static uint32_t lds_edges(const isingmc_batch *b) { return b->mode == SSE_MODE_LDS_EDGES ? b->dev.E : 0u; } // compact edge table words in LDS
+
+// Dynamic LDS of every kind of launch, read off the carve its kernel lays its LDS out with (the carves are the only statement of
+// the layouts; what the host adds on top — constant-op tables, growth areas, headroom — is policy and stays at the call sites).
+// f(L) on a fresh Lds<W> for the runtime wave count W (1, 4, 6, 8 or 16)
+template <class F>
+static size_t with_lds(uint32_t W, F &&f) {
+    return W == 1 ? f(Lds<1>{}) : W == 4 ? f(Lds<4>{}) : W == 6 ? f(Lds<6>{}) : W == 8 ? f(Lds<8>{}) : f(Lds<16>{});
+}
+// general / off-diagonal launch at W waves whose LDS union-find holds ufcap ids (tg: per-variable tables in HBM; pm_words: +-J signs)
+static size_t general_lds_words(uint32_t W, const DevBatch &D, uint32_t ledges, bool tg, uint32_t pm_words, uint32_t ufcap) {
+    return with_lds(W, [&](auto L) { L.carve(D.N, D.nwords, ufcap, ledges, D.has_long, tg, pm_words); return (size_t)L.end; });
+}
+// diagonal-pass launch (diag_only: the +-J decode's diagonal kernel, mode SSE_MODE_PM_LDS_TABLES)
+static size_t diag_lds_words(uint32_t W, const DevBatch &D, uint32_t ledges, bool tg, uint32_t pm_words, bool diag_only = false) {
+    return with_lds(W, [&](auto L) { L.carve(D.N, D.nwords, 0u, ledges, 0u, tg, pm_words, diag_only); return (size_t)L.end_diag; });
+}
+// trimmed diagonal-pass launch (sse_fast.hip.h): its tables, or the compact edge table that the directed loop behind the pass stages
+// in the same place
+static size_t fast_lds_words(const DevBatch &D) {
+    Lds<4> L;
+    L.carve(D.N, D.nwords, 0u, D.E, 0u);
+    return std::max<size_t>(fast_carve<4>(L, D).end, L.o_signs);
+}
+// RVB sweep inside the general kernel at W waves: its scratch (rvb_carve) and a constant-op table of cap entries (cutoff <= cap)
+static size_t rvb_lds_words(uint32_t W, const DevBatch &D, uint32_t ledges, bool tg, uint32_t pm_words) {
+    return with_lds(W, [&](auto L) { RvbLds R; L.carve(D.N, D.nwords, 0u, ledges, 0u, tg, pm_words); rvb_carve(R, L, D); return (size_t)R.o_cps + D.cap; });
+}
+// RVB sweep with its tables in HBM (SSE_PASSES_RVB_G, 16 waves): the LDS scratch of rvb_carve<16, true> and `areas` small growth areas
+static size_t rvb_global_lds_words(const isingmc_batch *b, uint32_t areas) {
+    Lds<16> L; RvbLds R;
+    L.carve(b->dev.N, b->dev.nwords, 0u, lds_edges(b), 0u, true);
+    rvb_carve<16, true>(R, L, b->dev);
+    return (size_t)R.o_free + (size_t)areas * SSE_RVB_SLOT_WORDS;
+}
+// bytes of a launch of `words` dynamic LDS words (whole 8-byte units)
+static size_t lds_bytes_of(size_t words) { return (4 * words + 7) & ~(size_t)7; }
+// a launch and the DevBatch it is given: the LDS it asks for and the LDS its kernel sees (DevBatch::lds_words), from one word count
+static void give_lds(LaunchCfg &c, DevBatch &d, size_t words) {
+    c.lds_bytes = lds_bytes_of(words);
+    d.lds_words = (uint32_t)(c.lds_bytes / 4);
 }
 
 // LDS footprint of the next launch.  The union-find of the cluster pass lives in LDS as 16-bit parents when all
 // ids fit; its capacity follows the largest transverse-op count seen so far (+ headroom), so that the footprint
 // stays small enough for two workgroups per CU whenever the model allows it.  Replicas that outgrow it use the HBM
 // union-find for that sweep and the host enlarges the table before the next launch.
-struct LdsPlan { uint32_t W, ufcap; size_t lds_bytes; bool all_ids_fit; };
+struct LdsPlan { uint32_t W, ufcap; size_t words; bool all_ids_fit; };
 static LdsPlan plan_lds(const isingmc_batch *b, uint32_t W) {
     const DevBatch &D = b->dev;
-    const size_t fixed = lds_fixed_words(W, D.N, D.nwords, b->mode == SSE_MODE_LDS_EDGES ? D.E : 0u, is_tg(b), is_pm(b) ? D.pm_words : 0u);
+    auto words = [&](size_t ids) { return general_lds_words(W, D, lds_edges(b), is_tg(b), is_pm(b) ? D.pm_words : 0u, (uint32_t)ids); };
     const size_t ids_max = (size_t)W * D.N + D.cap;
     const size_t want = (size_t)W * D.N + b->max_ntrans + b->max_ntrans / 16 + 384;
     size_t ids = want;
@@ -273,25 +296,24 @@ static LdsPlan plan_lds(const isingmc_batch *b, uint32_t W) {
     if (is_tg(b)) ids = 0; // tables in HBM: the union-find lives there too
     if (ids > 65535) ids = 65535;
     if (ids > ids_max) ids = ids_max;
-    auto words = [&](size_t n) { return (n + 1) / 2 + (D.has_long ? 2 * ((n + 31) / 32) : 0); };
-    while (ids > 0 && fixed + words(ids) > b->lds_total_words) ids -= (ids > 64 ? 64 : ids);
+    while (ids > 0 && words(ids) > b->lds_total_words) ids -= (ids > 64 ? 64 : ids);
     LdsPlan p;
     p.W = W; p.ufcap = (uint32_t)ids;
-    p.lds_bytes = (4 * (fixed + words(ids)) + 7) & ~(size_t)7;
-    p.all_ids_fit = !is_tg(b) && fixed + 64 <= b->lds_total_words && ids >= (want < ids_max ? want : ids_max) && !b->uf_ids_limit;
+    p.words = words(ids);
+    p.all_ids_fit = !is_tg(b) && words(0) + 64 <= b->lds_total_words && ids >= (want < ids_max ? want : ids_max) && !b->uf_ids_limit;
     return p;
 }
 static void size_lds(isingmc_batch *b) {
     const LdsPlan p = plan_lds(b, b->W);
     b->dev.lds_ufcap = p.ufcap;
-    b->lds_bytes = p.lds_bytes;
+    b->lds_words = p.words;
 }
 
 // LDS plan of the dedicated cluster kernel (sse_cluster.hip.h): 16 waves, packed per-wave tables, 16-bit parents for
 // 16 N + (transverse ops seen so far + headroom) ids.  ok = false: the ids do not fit (the general kernel takes the launch);
 // also when the largest id count the kernel would accept under that cap (want - 1) is not its case (cl_ids_fit: few
 // variables and many cuts, whose flip bits would overrun the per-wave tables).
-struct LeanPlan { bool ok; uint32_t ufcap; size_t lds_bytes; };
+struct LeanPlan { bool ok; uint32_t ufcap; size_t words; };
 static LeanPlan plan_lean(const isingmc_batch *b) {
     const DevBatch &D = b->dev;
     LeanPlan p{false, 0u, 0};
@@ -302,7 +324,7 @@ static LeanPlan plan_lean(const isingmc_batch *b) {
     if (want > 65535 || !cluster_ids_fit(D.N, (uint32_t)want - 1u, (uint32_t)want)) return p;
     const size_t words = cluster_lds_words(D.N, D.nwords, D.Nb, (uint32_t)want, D.has_long != 0u);
     if (words > b->lds_total_words) return p;
-    p.ok = true; p.ufcap = (uint32_t)want; p.lds_bytes = (4 * words + 7) & ~(size_t)7;
+    p.ok = true; p.ufcap = (uint32_t)want; p.words = words;
     return p;
 }
 
@@ -377,7 +399,7 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         }
         b->dev.rvb_tbl = (uint32_t *)q;
     }
-    if (rvb_g && rvb_global_lds_words(b->dev.N, b->dev.nwords, b->mode == SSE_MODE_LDS_EDGES ? b->dev.E : 0u, 0) > b->lds_total_words) {
+    if (rvb_g && rvb_global_lds_words(b, 0) > b->lds_total_words) {
         b->err = "RVB scratch (ISINGMC_CFG_RVB_GLOBAL_TABLES): the spin-state bit arrays and the fixed RVB regions exceed LDS";
         return ISINGMC_ENOTIMPL;
     }
@@ -400,8 +422,7 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         const int rc2 = dalloc(b, &b->dev.segs2, (size_t)b->dev.R * b->dev.stride, false);
         if (rc2) return rc2;
     }
-    lc.lds_bytes = ((domask & SSE_DO_RVB) && b->lds_bytes_rvb > b->lds_bytes) ? b->lds_bytes_rvb : b->lds_bytes;
-    b->dev.lds_words = (uint32_t)(lc.lds_bytes / 4);
+    give_lds(lc, b->dev, ((domask & SSE_DO_RVB) && b->lds_words_rvb > b->lds_words) ? b->lds_words_rvb : b->lds_words);
     auto launch_dev = [&](const LaunchCfg &c, const DevBatch &dev, const SweepArgs &a) -> hipError_t {
         switch (c.W) {
         case 1: return launch_sweep_w1(c, dev, a);
@@ -412,7 +433,6 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         default: return hipErrorInvalidValue;
         }
     };
-    auto launch = [&](const LaunchCfg &c, const SweepArgs &a) -> hipError_t { return launch_dev(c, b->dev, a); };
     auto fail_launch = [&](hipError_t e) { b->err = std::string("sweep launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; };
     uint32_t launches = 0;
     b->pass_ms[0] = b->pass_ms[1] = b->pass_ms[2] = 0.f;
@@ -443,25 +463,22 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
             }
         }
         LdsPlan po = plan_lds(b, Wo);
-        if (hbm_uf) {
-            const DevBatch &D = b->dev;
-            po.ufcap = 0;
-            po.lds_bytes = (4 * (lds_fixed_words(8, D.N, D.nwords, b->mode == SSE_MODE_LDS_EDGES ? D.E : 0u) + 64) + 7) & ~(size_t)7;
-        }
-        lc.W = Wo; lc.lds_bytes = po.lds_bytes;
+        if (hbm_uf) { po.ufcap = 0; po.words = general_lds_words(Wo, b->dev, lds_edges(b), false, 0u, 0u) + 64; }
+        lc.W = Wo;
         dev_off.lds_ufcap = po.ufcap;
         dev_off.lds_flipcap = 0u;
+        size_t words = po.words;
         if ((is_tg(b) || hbm_uf) && !(domask & SSE_DO_RVB)) {
             // HBM union-find launch: the LDS behind the fixed regions takes the flip bits of the ids (Wo * N + transverse ops seen so
             // far + headroom; a replica with more ids looks its flips up in HBM as before)
-            const size_t used = po.lds_bytes / 4;
+            const size_t used = lds_bytes_of(words) / 4;
             const size_t want = ((size_t)Wo * b->dev.N + b->max_ntrans + b->max_ntrans / 16 + 384 + 31) / 32;
             const size_t avail = b->lds_total_words > used + 16 ? b->lds_total_words - used - 16 : 0;
             const size_t fw = want < avail ? want : avail;
-            lc.lds_bytes = (4 * (used + fw) + 7) & ~(size_t)7;
+            words = used + fw;
             dev_off.lds_flipcap = (uint32_t)(32 * fw);
         }
-        dev_off.lds_words = (uint32_t)(lc.lds_bytes / 4);
+        give_lds(lc, dev_off, words);
         b->last_W_off = Wo;
     };
     bool use_dev_off = false;
@@ -471,16 +488,10 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         // sequential lane does not care); taken when the cluster tables of that geometry fit as well
         const LdsPlan p16 = plan_lds(b, 16);
         if (p16.all_ids_fit) {
-            const DevBatch &D = b->dev;
-            const size_t fixed16 = lds_fixed_words(16, D.N, D.nwords, b->mode == SSE_MODE_LDS_EDGES ? D.E : 0u);
-            const size_t o_cur16 = fixed16 - ((size_t)16 * D.N + 1) / 2 - ((size_t)16 * D.N + 3) / 4;
-            size_t want = 4 * (o_cur16 + 2 + rvb_fixed_words(D.N, D.E) + (size_t)D.cap);
-            const size_t max_lds = b->lds_total_words * 4;
-            if (want > max_lds) want = max_lds;
-            want &= ~(size_t)7;
-            lc.W = 16;
-            lc.lds_bytes = want > p16.lds_bytes ? want : p16.lds_bytes;
-            dev_off.lds_ufcap = p16.ufcap; dev_off.lds_words = (uint32_t)(lc.lds_bytes / 4);
+            size_t words = rvb_lds_words(16, b->dev, lds_edges(b), false, 0u);
+            if (words > b->lds_total_words) words = b->lds_total_words;
+            lc.W = 16; dev_off.lds_ufcap = p16.ufcap;
+            give_lds(lc, dev_off, words > p16.words ? words : p16.words);
             use_dev_off = true;
             b->last_W_off = 16;
         }
@@ -500,9 +511,9 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
     plan_lean_now();
     auto launch_lean = [&](const SweepArgs &a) -> hipError_t {
         LaunchCfg ll = lc;
-        ll.W = 16; ll.K = b->K; ll.lds_bytes = lean.lds_bytes;
+        ll.W = 16; ll.K = b->K;
         DevBatch dv = b->dev;
-        dv.lds_ufcap = lean.ufcap; dv.lds_words = (uint32_t)(lean.lds_bytes / 4);
+        dv.lds_ufcap = lean.ufcap; give_lds(ll, dv, lean.words);
         SweepArgs al = a;
         al.defer_flips = b->defer ? 1u : 0u;
         hipError_t e = launch_cluster(ll, dv, al);
@@ -512,7 +523,7 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         lf.W = b->W; lf.passes = SSE_PASSES_OFFDIAG;
         const LdsPlan pf = plan_lds(b, b->W);
         DevBatch df = b->dev;
-        lf.lds_bytes = pf.lds_bytes; df.lds_ufcap = pf.ufcap; df.lds_words = (uint32_t)(pf.lds_bytes / 4);
+        df.lds_ufcap = pf.ufcap; give_lds(lf, df, pf.words);
         SweepArgs af = a;
         af.only_flagged = 1u;
         return launch_dev(lf, df, af);
@@ -525,12 +536,9 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
             LaunchCfg lg = lfused;
             lg.W = 16; lg.K = 4; lg.passes = SSE_PASSES_RVB_G;
             lg.mode = b->mode == SSE_MODE_LDS_EDGES ? SSE_MODE_LDS_EDGES : SSE_MODE_GENERAL;
-            const uint32_t ledges = b->mode == SSE_MODE_LDS_EDGES ? b->dev.E : 0u;
-            size_t words = rvb_global_lds_words(b->dev.N, b->dev.nwords, ledges, 16);
+            size_t words = rvb_global_lds_words(b, 16);
             if (words > b->lds_total_words) words = b->lds_total_words; // (fewer small growth areas; the large one always fits)
-            lg.lds_bytes = (4 * words) & ~(size_t)7;
-            DevBatch dg = b->dev;
-            dg.lds_words = (uint32_t)(lg.lds_bytes / 4);
+            DevBatch dg = b->dev; give_lds(lg, dg, words);
             b->last_rvb_global = true;
             return launch_rvb_global(lg, dg, a);
         }
@@ -543,22 +551,16 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
                 else { (void)hipGetLastError(); b->rvb_split = false; } // no room for the records: the fused kernel from now on
             }
             const DevBatch &D = b->dev;
-            const uint32_t ledges = b->mode == SSE_MODE_LDS_EDGES ? D.E : 0u;
-            const size_t max_lds = b->lds_total_words * 4;
-            const size_t main_bytes = (4 * rvb_split_main_words(b->rvb_main_W, D.N, D.nwords, ledges, D.E, D.Nb) + 7) & ~(size_t)7;
-            if (D.rvb_prod && main_bytes <= max_lds) {
+            const size_t main_words = rvb_main_lds_words(b->rvb_main_W, D, lds_edges(b));
+            if (D.rvb_prod && lds_bytes_of(main_words) <= b->lds_total_words * 4) {
                 LaunchCfg lg = lfused;
-                size_t want = 4 * (rvb_split_grow_fixed_words(D.N, D.nwords, ledges) + (size_t)D.cap + 16 * 640 + 2);
-                if (want > max_lds) want = max_lds;
-                lg.W = 16; lg.lds_bytes = want & ~(size_t)7;
-                DevBatch dg = D;
-                dg.lds_words = (uint32_t)(lg.lds_bytes / 4);
+                size_t words = (size_t)rvb_grow_table_start(D, lds_edges(b)) + D.cap + 16 * 640; // the constant-op table, 16 small growth areas
+                if (words > b->lds_total_words) words = b->lds_total_words;
+                lg.W = 16; DevBatch dg = D; give_lds(lg, dg, words);
                 hipError_t e = launch_rvb_grow(lg, dg, a);
                 if (e != hipSuccess) return e;
                 LaunchCfg lm = lfused;
-                lm.W = b->rvb_main_W; lm.lds_bytes = main_bytes;
-                DevBatch dm = D;
-                dm.lds_words = (uint32_t)(main_bytes / 4);
+                lm.W = b->rvb_main_W; DevBatch dm = D; give_lds(lm, dm, main_words);
                 b->last_rvb_split = true;
                 return launch_rvb_main(lm, dm, a);
             }
@@ -610,8 +612,8 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         ld.passes = SSE_PASSES_DIAG;
         const bool use_fast = b->fast_diag && !(A.domask & SSE_DO_HEATBATH);
         // the diagonal launch needs the fixed regions up to the per-wave tables, which it uses as [W][N] bytes
-        ld.lds_bytes = use_fast ? b->lds_bytes_fast : diag_lds_bytes(b);
-        if (is_pm(b) && b->lds_bytes_pm_diag) { ld.mode = SSE_MODE_PM_LDS_TABLES; ld.lds_bytes = b->lds_bytes_pm_diag; } // (the cluster tables stay in HBM)
+        size_t diag_words = use_fast ? b->lds_words_fast : b->lds_words_diag;
+        if (is_pm(b) && b->lds_words_pm_diag) { ld.mode = SSE_MODE_PM_LDS_TABLES; diag_words = b->lds_words_pm_diag; } // (the cluster tables stay in HBM)
         const uint32_t rest = A.domask & ~diag_bits;
         constexpr size_t MAX_TIMED = 256;
         const size_t want_ev = 4 * (size_t)(nsteps < MAX_TIMED ? nsteps : MAX_TIMED);
@@ -632,7 +634,8 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
                 else { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
             }
             if (timed) HIP_TRY(b, hipEventRecord(b->evpool[4 * done], b->stream));
-            hipError_t e = use_fast ? launch_sweep_fast(ld, b->dev, a1) : launch(ld, a1);
+            DevBatch dd = b->dev; give_lds(ld, dd, diag_words);
+            hipError_t e = use_fast ? launch_sweep_fast(ld, dd, a1) : launch_dev(ld, dd, a1);
             if (e != hipSuccess) return fail_launch(e);
             launches++; b->pass_launches[0]++;
             if (timed) HIP_TRY(b, hipEventRecord(b->evpool[4 * done + 1], b->stream));
@@ -660,7 +663,7 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
                     lo.passes = SSE_PASSES_OFFDIAG;
                     const LdsPlan po = plan_lds(b, lc.W);
                     DevBatch dv = use_dev_off ? dev_off : b->dev;
-                    lo.lds_bytes = po.lds_bytes; dv.lds_ufcap = po.ufcap; dv.lds_flipcap = 0u; dv.lds_words = (uint32_t)(po.lds_bytes / 4);
+                    dv.lds_ufcap = po.ufcap; dv.lds_flipcap = 0u; give_lds(lo, dv, po.words);
                     if (lean_now && (rest2 & SSE_DO_CLUSTER) && !(rest2 & ~(SSE_DO_CLUSTER | SSE_DO_FREE))) e = launch_lean(a2);
                     else e = launch_dev(lo, dv, a2);
                 } else if (lean_now && (rest2 & SSE_DO_CLUSTER) && !(rest2 & ~(SSE_DO_CLUSTER | SSE_DO_FREE))) {
@@ -890,25 +893,27 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
     // Per-variable scan tables: in LDS while W copies of them fit (with room for a union-find), otherwise in a per-replica
     // HBM scratch served by L2 / Infinity Cache (MODE 2; ISINGMC_CFG_GLOBAL_TABLES forces it on any model).
     bool TG = (cfg->flags & ISINGMC_CFG_GLOBAL_TABLES) != 0;
-    if (!TG && lds_fixed_words(W, D.N, D.nwords, ledges) + 4096 > total_words) {
+    // (words of the general launch at w waves, tables in LDS, no union-find)
+    auto fixed_lds = [&](uint32_t w) { return general_lds_words(w, D, ledges, false, 0u, 0u); };
+    if (!TG && fixed_lds(W) + 4096 > total_words) {
         if (cfg->waves_per_replica) { // explicit geometry: keep the LDS tables if a smaller W makes them fit (previous behaviour)
-            while (W > 1 && lds_fixed_words(W, D.N, D.nwords, ledges) + 4096 > total_words) W = (W == 4) ? 1 : (W == 6 ? 4 : W >> 1);
-            if (lds_fixed_words(W, D.N, D.nwords, ledges) + 64 > total_words) TG = true, W = cfg->waves_per_replica;
+            while (W > 1 && fixed_lds(W) + 4096 > total_words) W = (W == 4) ? 1 : (W == 6 ? 4 : W >> 1);
+            if (fixed_lds(W) + 64 > total_words) TG = true, W = cfg->waves_per_replica;
         } else TG = true;
     }
     if (TG && CL) { b->err = "ISINGMC_CFG_GLOBAL_TABLES needs the general bond table: combine it with ISINGMC_CFG_NO_LDS_TABLES"; return fail(ISINGMC_EINVAL); }
     if (TG && K == 2) K = 4;
-    const size_t fixed = lds_fixed_words(W, D.N, D.nwords, ledges, TG, TG ? (D.E + 31u) / 32u : 0u); // (room for the +-J decode's signs, decided below)
-    if (fixed + 64 > total_words) { b->err = "model too large: the spin-state bit arrays alone exceed LDS"; return fail(ISINGMC_ENOTIMPL); }
+    const uint32_t pm_room = TG ? (D.E + 31u) / 32u : 0u; // (room for the +-J decode's signs, decided below)
+    if (general_lds_words(W, D, ledges, TG, pm_room, 0u) + 64 > total_words) { b->err = "model too large: the spin-state bit arrays alone exceed LDS"; return fail(ISINGMC_ENOTIMPL); }
     // off-diagonal launches may use their own wave count (see run()): explicit, or decided per launch (then up to 16)
     uint32_t W_off = cfg->waves_offdiag;
     if (W_off != 0 && W_off != 1 && W_off != 4 && W_off != 6 && W_off != 8 && W_off != 16) { b->err = "waves_offdiag must be 0, 1, 4, 6, 8 or 16"; return fail(ISINGMC_EINVAL); }
     if (!W_off && cfg->waves_per_replica) W_off = W; // an explicit waves_per_replica pins both kinds of launch
     if (TG) W_off = W;                               // tables in HBM: one geometry for every launch
-    if (W_off && lds_fixed_words(W_off, D.N, D.nwords, ledges, TG) + 64 > total_words) W_off = W;
-    const bool w16_possible = !TG && lds_fixed_words(16, D.N, D.nwords, ledges) + 64 <= total_words;
+    if (W_off && general_lds_words(W_off, D, ledges, TG, 0u, 0u) + 64 > total_words) W_off = W;
+    const bool w16_possible = !TG && fixed_lds(16) + 64 <= total_words;
     // (8 waves without an LDS union-find: the geometry of launches whose cluster ids need the 32-bit union-find in HBM anyway)
-    const bool w8_possible = !TG && W < 8 && (K == 4 || K == 1) && lds_fixed_words(8, D.N, D.nwords, ledges) + 64 <= total_words;
+    const bool w8_possible = !TG && W < 8 && (K == 4 || K == 1) && fixed_lds(8) + 64 <= total_words;
     b->w8_ok = w8_possible && !W_off;
     const uint32_t Wmax = W_off ? (W_off > W ? W_off : W) : ((W < 16 && w16_possible) ? 16u : (w8_possible ? 8u : W));
     const size_t ids_max = (size_t)Wmax * D.N + D.cap;
@@ -923,31 +928,30 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
         b->mode = SSE_MODE_PM_GLOBAL_TABLES;
         D.pm_words = (D.E + 31u) / 32u;
         // the diagonal launch keeps its per-wave spin bytes in LDS when W * N bytes fit next to the small arrays
-        const size_t words = (size_t)D.nwords * 2 + 4 * W + 16 + 2 * SSE_MAX_CHUNKS + D.pm_words + ((size_t)W * D.N + 3) / 4;
-        b->lds_bytes_pm_diag = (words + 64 <= total_words && !(cfg->flags & ISINGMC_CFG_GLOBAL_TABLES)) ? ((4 * words + 7) & ~(size_t)7) : 0;
+        const size_t words = diag_lds_words(W, D, 0u, false, D.pm_words, true);
+        b->lds_words_pm_diag = (words + 64 <= total_words && !(cfg->flags & ISINGMC_CFG_GLOBAL_TABLES)) ? words : 0;
     }
     { // chunk grid and row stride: one function (also exported for the CPU-side bound checks of tests/test_abi_cpu.py)
         uint32_t geo[4];
         if (isingmc_plan_geometry(D.cap, W, K, Wmax, geo) != ISINGMC_OK) { b->err = "capacity too large for the row stride"; return fail(ISINGMC_EINVAL); }
         D.CH = geo[0]; D.nchunks = geo[1]; D.stride = geo[2];
     }
-    b->lds_fixed_words_ = fixed; b->lds_total_words = total_words; b->uf_ids_limit = cfg->lds_uf_ids_limit;
-    b->lds_bytes_fast = fast_lds_bytes(D.N, D.nwords, D.E, D.Nb);
+    b->lds_words_diag = diag_lds_words(W, D, ledges, TG, pm_room); b->lds_total_words = total_words; b->uf_ids_limit = cfg->lds_uf_ids_limit;
+    b->lds_words_fast = fast_lds_words(D);
     b->fast_diag = CL && !TG && W == 4 && (K == 4 || K == 2) && D.N <= SSE_FAST_MAX_VARS && !b->fused_launch &&
-                   !(cfg->flags & ISINGMC_CFG_NO_FAST_DIAG) && b->lds_bytes_fast <= 40 * 1024; // 4 workgroups per CU
+                   !(cfg->flags & ISINGMC_CFG_NO_FAST_DIAG) && lds_bytes_of(b->lds_words_fast) <= 40 * 1024; // 4 workgroups per CU
     // the cluster update of that geometry has its own kernel too (16 waves, packed tables; sse_cluster.hip.h)
     b->lean_cluster = CL && !TG && !generic && D.N <= 4095u && !b->fused_launch && !cfg->waves_offdiag && !cfg->waves_per_replica &&
                       !(cfg->flags & ISINGMC_CFG_NO_LEAN_CLUSTER);
     { // the RVB pass reuses everything from the scan tables on: launches that run it get enough LDS for its scratch
       // and constant-op table (other launches keep the smaller footprint, which decides workgroups per CU)
-        const size_t o_cur = TG ? fixed : fixed - ((size_t)W * D.N + 1) / 2 - ((size_t)W * D.N + 3) / 4;
-        const size_t want = 4 * (o_cur + 2 + rvb_fixed_words(D.N, D.E) + (size_t)D.cap);
-        b->lds_bytes_rvb = (want < (size_t)max_lds ? want : (size_t)max_lds) & ~(size_t)7;
+        const size_t want = rvb_lds_words(W, D, ledges, TG, pm_room);
+        b->lds_words_rvb = want < total_words ? want : total_words;
     }
     b->rvb_global = (cfg->flags & ISINGMC_CFG_RVB_GLOBAL_TABLES) != 0; // (the two-launch form keeps its tables in LDS: never with this flag)
     b->rvb_split = !generic && !TG && !is_pm(b) && !b->fused_launch && !(cfg->flags & ISINGMC_CFG_RVB_FUSED) && !b->rvb_global;
     { // waves of the RVB main launch: as many as keep about 16 waves on a CU (its LDS footprint decides how many replicas share one)
-        const size_t w4 = 4 * rvb_split_main_words(4, D.N, D.nwords, CL ? D.E : 0u, D.E, D.Nb);
+        const size_t w4 = 4 * (size_t)rvb_main_lds_words(4, D, ledges);
         const size_t per_cu = w4 ? (size_t)max_lds / w4 : 0;
         b->rvb_main_W = per_cu >= 4 ? 4u : (per_cu >= 2 ? 8u : 16u);
     }
@@ -1429,8 +1433,8 @@ int isingmc_last_rvb_ms(isingmc_batch *b, float *ms, uint32_t *launches) {
 }
 int isingmc_get_launch_info(const isingmc_batch *b, uint32_t out[8]) {
     if (!b || !out) return ISINGMC_EINVAL;
-    out[0] = b->W; out[1] = (uint32_t)b->lds_bytes; out[2] = b->dev.lds_ufcap; out[3] = b->dev.nwords;
-    out[4] = b->K; out[5] = b->mode == SSE_MODE_LDS_EDGES ? 1u : 0u; out[6] = (b->fused_launch ? 0u : 1u) | (b->last_W_off << 8) | (is_tg(b) ? 2u : 0u) | (b->fast_diag ? 4u : 0u) | (b->last_lean ? 32u : 0u) | (b->last_rvb_split ? 64u : 0u) | (b->last_rvb_global ? 128u : 0u) | ((b->last_rvb_split ? b->rvb_main_W : 0u) << 16); out[7] = (uint32_t)diag_lds_bytes(b);
+    out[0] = b->W; out[1] = (uint32_t)lds_bytes_of(b->lds_words); out[2] = b->dev.lds_ufcap; out[3] = b->dev.nwords;
+    out[4] = b->K; out[5] = b->mode == SSE_MODE_LDS_EDGES ? 1u : 0u; out[6] = (b->fused_launch ? 0u : 1u) | (b->last_W_off << 8) | (is_tg(b) ? 2u : 0u) | (b->fast_diag ? 4u : 0u) | (b->last_lean ? 32u : 0u) | (b->last_rvb_split ? 64u : 0u) | (b->last_rvb_global ? 128u : 0u) | ((b->last_rvb_split ? b->rvb_main_W : 0u) << 16); out[7] = (uint32_t)lds_bytes_of(b->lds_words_diag);
     return ISINGMC_OK;
 }
 

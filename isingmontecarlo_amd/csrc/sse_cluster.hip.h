@@ -59,6 +59,7 @@ struct ClLds { // word offsets into lds_raw
     uint32_t o_ent;    // [16][N + 1] per (wave, variable): id | marker << 16 | touched << 24; after the joins: root list + flip bits
     uint32_t o_frozen, o_froot; // [ufwords] (h != 0)
     uint32_t o_parent; // [ufcap] u16
+    uint32_t end;      // first word behind the parent table: the launch's dynamic LDS
     __host__ __device__ __forceinline__ void carve(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) {
         uint32_t base = 0;
         o_tab = base; base += Nb + 1u;
@@ -71,16 +72,9 @@ struct ClLds { // word offsets into lds_raw
         o_frozen = base; base += has_long ? (ufcap + 31u) / 32u : 0u;
         o_froot = base; base += has_long ? (ufcap + 31u) / 32u : 0u;
         o_parent = base;
+        end = base + (ufcap + 1u) / 2u;
     }
 };
-// words in front of the parent table (host: LDS planning)
-static inline __host__ __device__ size_t cl_fixed_words(uint32_t N, uint32_t nwords, uint32_t Nb) {
-    return (size_t)Nb + 1 + 2 * (size_t)nwords + 16 + 2 * SSE_MAX_CHUNKS + (size_t)SSE_CLW * (N + 1);
-}
-// whole dynamic LDS of a launch whose parent table holds ufcap ids (host: LDS planning)
-static inline __host__ __device__ size_t cl_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) {
-    return cl_fixed_words(N, nwords, Nb) + ((size_t)ufcap + 1) / 2 + (has_long ? 2 * (((size_t)ufcap + 31) / 32) : 0);
-}
 // Is a replica with N variables and S ids (16 N + C: initial segments and placeholders, cuts) this kernel's case?  The 16-bit
 // parent table must hold S + 1 entries (id S is the null id of empty slots) below the 16-bit limit, and after the joins the S flip
 // bits reuse the per-wave tables o_ent (16 (N + 1) words): with few variables and many cuts they would run into the tables behind.

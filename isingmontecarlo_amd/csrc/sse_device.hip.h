@@ -243,10 +243,12 @@ struct Lds {           // word offsets into lds_raw
     uint32_t o_frozen; // [ufwords]     bit per id: segment holds a longitudinal op
     uint32_t o_froot;  // [ufwords]     bit per id: root is frozen
     uint32_t o_parent; // [ufcap] u16 (the LDS union-find is only used when every id fits 16 bits)
+    uint32_t end;      // first word behind the parent table: the dynamic LDS of a launch of this layout
+    uint32_t end_diag; // first word behind what a diagonal-pass launch uses (the regions up to o_cur, o_cur as [W][N] u8 spin bytes)
     // diag_only: the launch runs the diagonal pass (+ directed loop) alone and its per-wave spin BYTES are the only per-variable
     // table (large models whose cluster tables live in HBM can still keep these in LDS)
-    __device__ __forceinline__ void carve(uint32_t N, uint32_t nwords, uint32_t ufcap, uint32_t ledges, uint32_t has_long, bool tg = false,
-                                          uint32_t pm_words = 0, bool diag_only = false) {
+    __host__ __device__ __forceinline__ void carve(uint32_t N, uint32_t nwords, uint32_t ufcap, uint32_t ledges, uint32_t has_long, bool tg = false,
+                                                   uint32_t pm_words = 0, bool diag_only = false) {
         uint32_t base = 0;
         o_state = base; base += nwords;
         o_touch = base; base += nwords;
@@ -260,10 +262,12 @@ struct Lds {           // word offsets into lds_raw
         o_edges = base; base += ledges;
         o_signs = base; base += pm_words;
         o_cur = base; base += diag_only ? (W * N + 3) / 4 : (W * N + 1) / 2;
+        end_diag = o_cur + (W * N + 3) / 4;
         o_cl = base; base += diag_only ? 0u : (W * N + 3) / 4;
         o_frozen = base; base += has_long ? (ufcap + 31) / 32 : 0u;
         o_froot = base; base += has_long ? (ufcap + 31) / 32 : 0u;
         o_parent = base;
+        end = base + (ufcap + 1) / 2;
     }
 };
 // Per-variable tables of the ordered scans (spin bytes of the diagonal pass, cut ranks / cut markers / touched bytes of the
@@ -1699,17 +1703,16 @@ hipError_t launch_sweep_w8(const LaunchCfg &c, const DevBatch &B, const SweepArg
 hipError_t launch_sweep_w16(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
 hipError_t launch_sweep_fast(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A); // sweep_fast.hip: sse_fast.hip.h, W = 4
 hipError_t launch_cluster(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);    // sweep_cluster.hip: sse_cluster.hip.h, W = 16
-size_t cluster_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long); // dynamic LDS words of that kernel
+size_t cluster_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long); // dynamic LDS words of that kernel (ClLds::carve)
 bool cluster_ids_fit(uint32_t N, uint32_t S, uint32_t ufcap);                          // ... and its gate on the ids of a replica
 // sweep_rvb.hip (sse_rvb_split.hip.h): the RVB sweep as a growth launch (16 waves) and a main launch (c.W = 4, 8 or 16 waves)
 hipError_t launch_rvb_grow(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
 hipError_t launch_rvb_main(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
-size_t rvb_split_grow_fixed_words(uint32_t N, uint32_t nwords, uint32_t ledges);           // LDS words of the growth launch in front of the constant-op table
-size_t rvb_split_main_words(uint32_t W, uint32_t N, uint32_t nwords, uint32_t ledges, uint32_t E, uint32_t Nb); // LDS words of the main launch
+uint32_t rvb_grow_table_start(const DevBatch &B, uint32_t ledges);         // growth launch: where its constant-op table starts (rvb_carve_grow)
+uint32_t rvb_main_lds_words(uint32_t W, const DevBatch &B, uint32_t ledges); // main launch: its dynamic LDS (rvb_carve_main)
 size_t rvb_split_prod_stride(uint32_t Nb);                                                // words per attempt in DevBatch::rvb_prod; 0 = the model is too large for the two-launch form
 // sweep_rvb_global.hip: the RVB sweep alone with its per-variable tables in HBM (SSE_PASSES_RVB_G; c.W = 16, c.K = 4; B.rvb_tbl allocated)
 hipError_t launch_rvb_global(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
-size_t rvb_global_lds_words(uint32_t N, uint32_t nwords, uint32_t ledges, uint32_t areas); // LDS words of that launch with `areas` small growth areas
 
 template <int W, int K, int CL, int PHASE, int PASSES>
 hipError_t launch_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {

@@ -52,7 +52,7 @@ struct FastLds {
 // The tables start where the general layout keeps the compact edge table: the directed loop behind the diagonal pass is the
 // only user of that table in this kernel and stages it when the tables below are dead.
 template <int W>
-__device__ __forceinline__ FastLds fast_carve(const Lds<W> &L, const DevBatch &B) {
+__host__ __device__ __forceinline__ FastLds fast_carve(const Lds<W> &L, const DevBatch &B) {
     FastLds F;
     uint32_t base = (L.o_edges + 3u) & ~3u; // 16-byte aligned: the class constants are read as one b128
     F.o_nb = base; base += 16;

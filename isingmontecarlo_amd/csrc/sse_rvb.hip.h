@@ -83,26 +83,17 @@ enum { RC_NSUB = 0, RC_NWIN = 1, RC_ACCEPT = 2, RC_GLEN = 3, RC_NEXTP = 4, RC_ER
 
 __device__ __forceinline__ double &ldsd(uint32_t off, uint32_t i) { return reinterpret_cast<double *>(lds_raw)[(off >> 1) + i]; }
 
-// words of RVB scratch in front of the constant-op table (mirrors rvb_carve; used by the host to size LDS)
-__host__ __device__ inline uint32_t rvb_fixed_words(uint32_t N, uint32_t E) {
-    const uint32_t adj = SSE_RVB_ADJ_LDS && (N < 65535u && E < 65535u) ? (N + 2) / 2 + E : 0u;
-    static_assert(3 * SSE_RVB_GCAP >= 7 * SSE_RVB_SETCAP, "the candidate sets of the large growth area live in the gathered-op lists");
-    return 2u + 4 * SSE_RVB_BONDCAP + (N + 1) + N + (N + 1) / 2 + adj + 3 * SSE_RVB_MAXSUB +
-           6 * SSE_RVB_MAXCL + 2 * SSE_RVB_MAXWIN + SSE_RVB_BONDCAP + 3 * SSE_RVB_GCAP + (E + 1) / 2 + 16 + 8;
-}
-
-// words of RVB scratch in LDS with the five per-variable tables in HBM (rvb_carve<.., G = true>), in front of the small growth areas
-__host__ __device__ constexpr uint32_t rvb_global_fixed_words() {
-    return 2u + 4 * SSE_RVB_BONDCAP + 3 * SSE_RVB_MAXSUB + 6 * SSE_RVB_MAXCL + 2 * SSE_RVB_MAXWIN + SSE_RVB_BONDCAP + 3 * SSE_RVB_GCAP + 16 + 8;
-}
 // words per replica of DevBatch::rvb_tbl: vstart [N+1], zero [N], v2s [N] u16, bix [E] u16, cps [cap] (a sweep holds at most cutoff <= cap
 // constant ops, so the table cannot overflow), rounded up to 64 bytes
 __host__ __device__ inline size_t rvb_tbl_words(uint32_t N, uint32_t E, uint32_t cap) {
     return ((size_t)(N + 1) + N + (N + 1) / 2 + (E + 1) / 2 + cap + 15) & ~(size_t)15;
 }
 
+static_assert(3 * SSE_RVB_GCAP >= 7 * SSE_RVB_SETCAP, "the candidate sets of the large growth area live in the gathered-op lists");
+// RVB scratch behind Lds::o_cur.  G = false: the constant-op table at o_cps takes the rest of the launch's LDS (B.lds_words).
+// G = true: the small growth areas start at o_free
 template <int W, bool G = false>
-__device__ __forceinline__ void rvb_carve(RvbLds &R, const Lds<W> &L, const DevBatch &B, uint32_t r = 0) {
+__host__ __device__ __forceinline__ void rvb_carve(RvbLds &R, const Lds<W> &L, const DevBatch &B, uint32_t r = 0) {
     if constexpr (G) { // the five per-variable tables in this replica's row of B.rvb_tbl, everything else in LDS as below
         const size_t words = rvb_tbl_words(B.N, B.E, B.cap);
         R.tg = B.rvb_tbl + (size_t)r * words;

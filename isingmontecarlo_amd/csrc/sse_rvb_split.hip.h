@@ -42,12 +42,9 @@ __host__ __device__ inline uint32_t rvb_region_words(uint32_t bmw) {
 
 __device__ __forceinline__ uint32_t rvb_prod_words(uint32_t bmw, uint32_t nsub, uint32_t nwin, uint32_t ntog) { return 8u + bmw + 2u * ntog + 2u * nsub + 2u * nwin; }
 
-// LDS of the growth launch behind Lds::o_cur: what rvb_find_constants and rvb_grow touch, then the table
-__host__ __device__ inline uint32_t rvb_grow_fixed_words(uint32_t N) {
-    return 2u + (N + 1) + N + (N + 1) / 2 + 7 * SSE_RVB_SETCAP + 2 * SSE_RVB_MAXCL + 4 * SSE_RVB_MAXCL + 3 * SSE_RVB_MAXSUB + 2 * SSE_RVB_MAXWIN + 16 + 8;
-}
+// LDS of the growth launch behind Lds::o_cur: what rvb_find_constants and rvb_grow touch, then the table at o_cps
 template <int W>
-__device__ __forceinline__ void rvb_carve_grow(RvbLds &R, const Lds<W> &L, const DevBatch &B) {
+__host__ __device__ __forceinline__ void rvb_carve_grow(RvbLds &R, const Lds<W> &L, const DevBatch &B) {
     uint32_t base = (L.o_cur + 1u) & ~1u;
     R.o_bfw = base; R.o_bnw = base + 2 * SSE_RVB_SETCAP; R.o_bfk = base + 4 * SSE_RVB_SETCAP; R.o_bfv = base + 5 * SSE_RVB_SETCAP; R.o_bnk = base + 6 * SSE_RVB_SETCAP;
     base += 7 * SSE_RVB_SETCAP;
@@ -73,13 +70,9 @@ __device__ __forceinline__ void rvb_carve_grow(RvbLds &R, const Lds<W> &L, const
 
 // LDS of the main launch: [nwords] state, [2W] totals, [E] compact edges (CL), then the scratch of rvb_attempt and the record
 // region: two prefetched small records side by side, or one large record over both (the next record waits in registers meanwhile)
-__host__ __device__ inline uint32_t rvb_main_words(uint32_t W, uint32_t N, uint32_t nwords, uint32_t ledges, uint32_t E, uint32_t Nb) {
-    return nwords + 2 * W + 16 + ledges + 2u + 4 * SSE_RVB_BONDCAP + (N + 1) / 2 + SSE_RVB_MAXSUB + SSE_RVB_BONDCAP + 3 * rvb_gcap_main(W) + (E + 1) / 2 + 16 +
-           rvb_region_words(rvb_bm_words(Nb)) + 8;
-}
 struct RvbMainLds { uint32_t o_pbuf, o_big; };
 template <int W>
-__device__ __forceinline__ void rvb_carve_main(Lds<W> &L, RvbLds &R, RvbMainLds &P, const DevBatch &B, uint32_t ledges) {
+__host__ __device__ __forceinline__ void rvb_carve_main(Lds<W> &L, RvbLds &R, RvbMainLds &P, const DevBatch &B, uint32_t ledges) {
     uint32_t base = 0;
     L.o_state = base; base += B.nwords;
     L.o_tot = base; base += 2 * W;

@@ -10,7 +10,7 @@ static hipError_t launch_cluster_one(const LaunchCfg &c, const DevBatch &B, cons
     hipLaunchKernelGGL((cluster_kernel<K, HL, PHASE>), dim3(B.R), dim3(SSE_CLW * 64), c.lds_bytes, c.stream, B, A);
     return hipGetLastError();
 }
-size_t cluster_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) { return cl_lds_words(N, nwords, Nb, ufcap, has_long); }
+size_t cluster_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) { ClLds L; L.carve(N, nwords, Nb, ufcap, has_long); return L.end; }
 bool cluster_ids_fit(uint32_t N, uint32_t S, uint32_t ufcap) { return cl_ids_fit(N, S, ufcap); }
 hipError_t launch_cluster(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     if (c.mode != SSE_MODE_LDS_EDGES || B.N > SSE_CL_MAX_VARS || !(A.domask & SSE_DO_CLUSTER)) return hipErrorInvalidValue;
@@ -31,8 +31,7 @@ extern "C" int isingmc_plan_cluster_lds(uint32_t N, uint32_t nwords, uint32_t Nb
     L.carve(N, nwords, Nb, ufcap, has_long != 0u);
     out[0] = L.o_tab; out[1] = L.o_state; out[2] = L.o_touch; out[3] = L.o_misc; out[4] = L.o_chn; out[5] = L.o_chtr;
     out[6] = L.o_ent; out[7] = L.o_frozen; out[8] = L.o_froot; out[9] = L.o_parent;
-    const size_t words = sse::cl_lds_words(N, nwords, Nb, ufcap, has_long != 0u);
-    out[10] = words > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)words;
+    out[10] = L.end;
     out[11] = sse::cl_ids_fit(N, S, ufcap) ? 1u : 0u;
     out[12] = sse::cl_list_cap(N, S);
     return ISINGMC_OK;

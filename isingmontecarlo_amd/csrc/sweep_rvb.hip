@@ -16,10 +16,16 @@ static hipError_t launch_main_one(const LaunchCfg &c, const DevBatch &B, const S
     hipLaunchKernelGGL((rvb_main_kernel<W, CL>), dim3(B.R), dim3(W * 64), c.lds_bytes, c.stream, B, A);
     return hipGetLastError();
 }
-size_t rvb_split_grow_fixed_words(uint32_t N, uint32_t nwords, uint32_t ledges) {
-    return (size_t)2 * nwords + (N + 3) / 4 + 4 * 16 + 16 + 2 * SSE_MAX_CHUNKS + ledges + rvb_grow_fixed_words(N); // Lds<16>::carve up to o_cur, then rvb_carve_grow
+uint32_t rvb_grow_table_start(const DevBatch &B, uint32_t ledges) { Lds<16> L; RvbLds R; L.carve(B.N, B.nwords, 0u, ledges, 0u); rvb_carve_grow<16>(R, L, B); return R.o_cps; }
+template <int W>
+static uint32_t rvb_main_end(const DevBatch &B, uint32_t ledges) {
+    Lds<W> L; RvbLds R; RvbMainLds P;
+    rvb_carve_main<W>(L, R, P, B, ledges); // (its end: the record region is its last; a field for it changes rvb_main_kernel's registers)
+    return P.o_big + rvb_region_words(rvb_bm_words(B.Nb));
 }
-size_t rvb_split_main_words(uint32_t W, uint32_t N, uint32_t nwords, uint32_t ledges, uint32_t E, uint32_t Nb) { return rvb_main_words(W, N, nwords, ledges, E, Nb); }
+uint32_t rvb_main_lds_words(uint32_t W, const DevBatch &B, uint32_t ledges) {
+    return W == 4 ? rvb_main_end<4>(B, ledges) : (W == 8 ? rvb_main_end<8>(B, ledges) : rvb_main_end<16>(B, ledges));
+}
 size_t rvb_split_prod_stride(uint32_t Nb) { return rvb_bm_words(Nb) <= SSE_RVB_BM_MAX ? SSE_RVB_PROD_STRIDE + rvb_bm_words(Nb) : 0u; }
 hipError_t launch_rvb_grow(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     if (!B.rvb_prod) return hipErrorInvalidValue;

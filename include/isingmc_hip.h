@@ -280,6 +280,41 @@ int isingmc_pt_get_slots(isingmc_batch *b, uint32_t *slot_of_replica, double *be
 int isingmc_pt_get_state(isingmc_batch *b, uint64_t *step, uint64_t *total_swaps);
 int isingmc_pt_set_state(isingmc_batch *b, const uint32_t *slot_of_replica, const uint32_t *config_id_of_replica, uint64_t step, uint64_t total_swaps);
 
+/* ---- sample record: the sampled p = 0 states kept on the device, and exact autocorrelations of two-valued observables ------------
+ * QmcStepper::timesteps_sample / timesteps_measure (qmc_traits/qmc_stepper.rs:23-95) hand the caller the state at every sampled
+ * step, and autocorrelations.rs builds on that list.  While a record is attached, every sampled step of isingmc_timesteps
+ * ((step + 1) % sampling_freq == 0) appends the p = 0 states of all replicas, exactly what isingmc_get_state would return if the
+ * call ended on that step: a device-to-device copy on the batch's stream, no host synchronisation.  The record is
+ * [capacity][R][state words] in device memory; rows are indexed by replica, not by tempering slot (isingmc_pt_timesteps goes
+ * through isingmc_timesteps and records too).  A call whose t / sampling_freq samples do not fit returns ISINGMC_ECAPACITY before
+ * anything is launched and leaves the batch and the record as they were.  Launches that run several steps
+ * (ISINGMC_CFG_FUSED_LAUNCH) end on each sampled step while a record is attached: same epochs, same results.  Nothing is
+ * recorded, and no launch changes, without a record.  Checkpoints do not carry the record. */
+/* capacity samples (<= 1 << 20); 0 detaches and frees; attaching again replaces the record by an empty one */
+int isingmc_record_attach(isingmc_batch *b, uint32_t capacity);
+/* rows written so far and the capacity (both 0 without a record); either pointer may be NULL */
+int isingmc_record_count(const isingmc_batch *b, uint32_t *count, uint32_t *capacity);
+/* the next sample goes to row 0 again */
+int isingmc_record_clear(isingmc_batch *b);
+/* rows first .. first + count - 1 as bytes 0/1 like isingmc_get_state: out[count][N] of replica r; r == UINT32_MAX: out[count][R][N] */
+int isingmc_record_read(isingmc_batch *b, uint32_t first, uint32_t count, uint32_t r, uint8_t *out);
+/* Two-valued observables of the recorded states.  Observable g is the group of variables group_vars[group_start[g] ..
+ * group_start[g + 1]) (non-empty, variables < N, group_start[0] = 0; a variable may repeat across groups) and a flip bit: its bit at
+ * sample t is parity(state bits of the group) ^ group_flip[g] (NULL: no flips), 1 standing for the value +1.  This covers a variable
+ * (autocorrelations.rs:37-50: {v}, 0), a product of spins (:52-75: its variables, 1 if their number is even) and a bond
+ * (qmc_ising.rs:988-997: {a, b}, 1 if J < 0).  out_bits[R][ngroups][(count + 31) / 32]: bit t & 31 of word t >> 5 is sample
+ * first + t; unused high bits of the last word are 0.  ISINGMC_ENOTIMPL for models whose 64 state rows exceed LDS (N > ~20000). */
+int isingmc_record_series(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars, const uint8_t *group_flip,
+                          uint32_t first, uint32_t count, uint32_t *out_bits);
+/* fft_autocorrelation (autocorrelations.rs:99-133) of those observables over samples first .. first + count - 1, without transforms
+ * and exact: with T = count, x the +-1 series of one observable, s = sum_t x[t] and C(tau) = sum_t x[t] x[(t + tau) mod T] =
+ * T - 2 popcount(bits ^ rotate(bits, tau)), the observable contributes (T C(tau) - s^2) / (T^2 - s^2) (integers up to this one
+ * double division; 0 for a series that never changed); out[R][count] is the mean over the observables, added in group order.  The
+ * result does not depend on the flips and is reproducible bit for bit.  ISINGMC_ENOTIMPL when the series, twice, exceeds LDS
+ * (count > ~650000). */
+int isingmc_record_autocorrelation(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars,
+                                   uint32_t first, uint32_t count, double *out);
+
 /* stream plumbing: use the caller's hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) */
 int isingmc_set_stream(isingmc_batch *b, void *hip_stream);
 int isingmc_synchronize(isingmc_batch *b);

@@ -134,6 +134,12 @@ SYMBOLS = {
     "isingmc_last_rvb_ms": (C.c_int, [_vp, _P(C.c_float), _P(_u32)]),
     "isingmc_plan_geometry": (C.c_int, [_u32, _u32, _u32, _u32, _P(_u32)]),
     "isingmc_plan_cluster_lds": (C.c_int, [_u32, _u32, _u32, _u32, _u32, _u32, _P(_u32)]),
+    "isingmc_record_attach": (C.c_int, [_vp, _u32]),
+    "isingmc_record_count": (C.c_int, [_vp, _P(_u32), _P(_u32)]),
+    "isingmc_record_clear": (C.c_int, [_vp]),
+    "isingmc_record_read": (C.c_int, [_vp, _u32, _u32, _u32, _P(C.c_uint8)]),
+    "isingmc_record_series": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _P(C.c_uint8), _u32, _u32, _P(_u32)]),
+    "isingmc_record_autocorrelation": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _u32, _u32, _P(_f64)]),
 }
 
 _LIB = None
@@ -468,6 +474,97 @@ class QmcIsingGraph:
     def import_ops(self, words, r=0):
         w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
         self._check(self._lib.isingmc_import_ops(self._h, int(r), _ptr(w, C.c_uint32), len(w)))
+
+    # ---- sample record: the sampled p = 0 states stay on the device (qmc_stepper.rs:23-95; include/isingmc_hip.h) ----
+    def attach_sample_record(self, capacity):
+        """Keep the p = 0 states of every sampled step of timesteps / run in device memory, up to `capacity` samples (attaching
+        again starts an empty record).  A call whose samples do not fit raises ECAPACITY before it runs anything."""
+        self._check(self._lib.isingmc_record_attach(self._h, int(capacity)))
+
+    def detach_sample_record(self):
+        self._check(self._lib.isingmc_record_attach(self._h, 0))
+
+    def record_count(self):
+        """Samples recorded so far."""
+        return self._record_info()[0]
+
+    def record_capacity(self):
+        """Capacity of the attached record, 0 without one."""
+        return self._record_info()[1]
+
+    def _record_info(self):
+        n, cap = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.isingmc_record_count(self._h, C.byref(n), C.byref(cap)))
+        return n.value, cap.value
+
+    def record_clear(self):
+        self._check(self._lib.isingmc_record_clear(self._h))
+
+    def _record_range(self, first, count):
+        first = int(first)
+        return first, (self.record_count() - first) if count is None else int(count)
+
+    def record_states(self, first=0, count=None, r=None):
+        """Recorded states first .. first + count - 1 (default: to the end): uint8 [T][R][N], or [T][N] of replica r."""
+        first, count = self._record_range(first, count)
+        out = np.zeros((max(count, 0), self.nreplicas, self.nvars) if r is None else (max(count, 0), self.nvars), dtype=np.uint8)
+        if count == 0 and self.record_capacity():
+            return out  # an attached record without rows in the range: nothing to read
+        self._check(self._lib.isingmc_record_read(self._h, first, count, ALL if r is None else int(r), _ptr(out, C.c_uint8)))
+        return out
+
+    @staticmethod
+    def _groups(groups):
+        """Observable groups -> (ngroups, starts [ngroups + 1], variables) as the C ABI takes them."""
+        groups = [np.atleast_1d(np.asarray(g, dtype=np.uint32)) for g in groups]
+        start = np.zeros(len(groups) + 1, dtype=np.uint32)
+        start[1:] = np.cumsum([len(g) for g in groups])
+        vs = np.ascontiguousarray(np.concatenate(groups) if groups else np.zeros(0, dtype=np.uint32), dtype=np.uint32)
+        return len(groups), start, vs
+
+    def record_series(self, groups, flips=None, first=0, count=None):
+        """Bit series of two-valued observables over the recorded samples: observable g is parity(state bits of the variables
+        groups[g]) ^ flips[g], bit 1 standing for +1 (autocorrelations.variable_groups / product_groups / bond_groups build the
+        reference's three).  Returns uint32 [R][G][(T + 31) // 32], bit t & 31 of word t >> 5 = sample first + t."""
+        first, count = self._record_range(first, count)
+        ng, start, vs = self._groups(groups)
+        fl = None if flips is None else np.ascontiguousarray(np.asarray(flips, dtype=np.uint8))
+        if fl is not None and fl.shape != (ng,):
+            raise IsingMcError(-1, "flips must hold one entry per group")
+        out = np.zeros((self.nreplicas, ng, (max(count, 0) + 31) // 32), dtype=np.uint32)
+        self._check(self._lib.isingmc_record_series(self._h, ng, _ptr(start, C.c_uint32), _ptr(vs, C.c_uint32),
+                                                    _ptr(fl, C.c_uint8) if fl is not None else None, first, count, _ptr(out, C.c_uint32)))
+        return out
+
+    def record_autocorrelation(self, groups, first=0, count=None):
+        """fft_autocorrelation (autocorrelations.rs:99-133) of the observables `groups` over the recorded samples, computed on the
+        device from their bit series with population counts (exact up to one division per observable and lag; equal bit for bit
+        to autocorrelations.bit_autocorrelation).  Returns float64 [R][T]."""
+        first, count = self._record_range(first, count)
+        ng, start, vs = self._groups(groups)
+        out = np.zeros((self.nreplicas, max(count, 0)), dtype=np.float64)
+        self._check(self._lib.isingmc_record_autocorrelation(self._h, ng, _ptr(start, C.c_uint32), _ptr(vs, C.c_uint32), first, count, _ptr(out, C.c_double)))
+        return out
+
+    def timesteps_sample(self, t, beta, sampling_freq=1, flags=None):
+        """QmcStepper::timesteps_sample (qmc_stepper.rs:23-41) for the batch: (states uint8 [t // sampling_freq][R][N], energy [R]).
+        Uses the attached record when it has room for the samples (they stay in it); without a record, one is attached for the call
+        and detached again.  An attached record without room is left alone: ECAPACITY."""
+        nsamp = int(t) // int(sampling_freq)
+        have, cap = self._record_info()
+        own = cap - have < nsamp
+        if own:
+            if cap:
+                raise IsingMcError(-3, f"the attached sample record has room for {cap - have} of the {nsamp} samples")
+            self.attach_sample_record(max(nsamp, 1))
+            have = 0
+        try:
+            energy = self.timesteps(t, beta, sampling_freq, flags)
+            states = self.record_states(have, nsamp) if nsamp else np.zeros((0, self.nreplicas, self.nvars), dtype=np.uint8)
+        finally:
+            if own:
+                self.detach_sample_record()
+        return states, energy
 
     # ---- checkpoint / resume (the reference's serde feature, qmc_ising.rs:1001-1087) ----
     def save_checkpoint(self, path):

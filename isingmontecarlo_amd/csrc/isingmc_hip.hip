@@ -3,6 +3,7 @@
 #include "../../include/isingmc_hip.h"
 #include "sse_device.hip.h"
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -64,6 +65,12 @@ struct isingmc_batch {
     mutable std::string err;
     struct PtState *pt = nullptr;       // native parallel tempering (isingmc_pt_*), see the end of this file
     std::vector<uint32_t> ham_row_host; // [R] bond-table row of each local replica (tempering between different Hamiltonians), empty = identity
+    // sample record (isingmc_record_*): [rec_cap][R][nwords] words, rows 0 .. rec_count - 1 written; nullptr = none attached
+    uint32_t *rec = nullptr;
+    uint32_t rec_cap = 0, rec_count = 0;
+    // scratch of the record's observables, grown on demand: observable groups, bit series [R][ngroups][Tw], autocorrelations [R][T]
+    void *obs_groups = nullptr, *obs_series = nullptr, *obs_out = nullptr;
+    size_t obs_groups_bytes = 0, obs_series_bytes = 0, obs_out_bytes = 0;
 };
 
 #define HIP_TRY(b, expr)                                                                              \
@@ -365,6 +372,16 @@ static int check_errors(isingmc_batch *b) {
     return ISINGMC_OK;
 }
 
+// Append the p = 0 states to the sample record: a device-to-device copy of dev.state (current in HBM after every launch) on the
+// batch's stream, behind the last launch of a sampled step.  The caller has checked the room (isingmc_timesteps).
+static hipError_t record_append(isingmc_batch *b) {
+    const size_t row = (size_t)b->dev.R * b->dev.nwords;
+    if (b->rec_count >= b->rec_cap) return hipErrorInvalidValue;
+    const hipError_t e = hipMemcpyAsync(b->rec + (size_t)b->rec_count * row, b->dev.state, row * sizeof(uint32_t), hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess) b->rec_count++;
+    return e;
+}
+
 static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t freq, uint32_t domask, double prob,
                uint32_t *out_host) {
     if (!b) return ISINGMC_EINVAL;
@@ -435,6 +452,8 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
     };
     auto fail_launch = [&](hipError_t e) { b->err = std::string("sweep launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; };
     uint32_t launches = 0;
+    const bool recording = b->rec && freq; // (freq != 0: timesteps; single updates sample nothing)
+    auto fail_record = [&](hipError_t e) { b->err = std::string("sample record: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; };
     b->pass_ms[0] = b->pass_ms[1] = b->pass_ms[2] = 0.f;
     b->pass_launches[0] = b->pass_launches[1] = b->pass_launches[2] = 0;
     // passes of the first ("diagonal") launch of a split timestep: the diagonal pass and, unless an RVB sweep has to
@@ -590,17 +609,21 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
                 if ((e = launch_dev(lc, b->dev, a2)) != hipSuccess) return fail_launch(e);
                 launches++;
             }
+            if (recording && (done + 1) % freq == 0 && (e = record_append(b)) != hipSuccess) return fail_record(e);
         }
         b->pass_launches[1] = launches;
     } else if (!split) {
         const uint64_t per = b->steps_per_launch ? b->steps_per_launch : nsteps;
-        for (uint64_t done = 0; done < nsteps; done += per) {
+        for (uint64_t done = 0; done < nsteps; done += A.nsteps) {
             A.step0 = done;
             A.nsteps = (nsteps - done < per) ? nsteps - done : per;
+            // with a sample record attached a launch ends on the next sampled step, whose state the record takes (same epochs, same results)
+            if (recording && A.nsteps > freq - done % freq) A.nsteps = freq - done % freq;
             const bool lean_here = lean_now && A.nsteps == 1 && (A.domask & SSE_DO_CLUSTER) && !(A.domask & ~(SSE_DO_CLUSTER | SSE_DO_FREE));
             const hipError_t e = lean_here ? launch_lean(A) : (rvb_only ? launch_rvb(lc, use_dev_off ? dev_off : b->dev, A) : launch_dev(lc, (use_dev_off || lc.passes == SSE_PASSES_OFFDIAG) ? dev_off : b->dev, A));
             if (e != hipSuccess) return fail_launch(e);
             launches++;
+            if (recording && (done + A.nsteps) % freq == 0) { const hipError_t er = record_append(b); if (er != hipSuccess) return fail_record(er); }
         }
         b->pass_launches[1] = launches;
     } else {
@@ -674,6 +697,7 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
                 launches++; b->pass_launches[1]++;
             }
             if (timed) { HIP_TRY(b, hipEventRecord(b->evpool[4 * done + 3], b->stream)); timed_steps++; }
+            if (recording && sample && (e = record_append(b)) != hipSuccess) return fail_record(e);
         }
     }
     HIP_TRY(b, hipEventRecord(b->ev1, b->stream));
@@ -1078,6 +1102,7 @@ void isingmc_destroy(isingmc_batch *b) {
     for (void *p : b->allocs) (void)hipFree(p);
     if (b->dev.rvb_prod) (void)hipFree(b->dev.rvb_prod);
     if (b->dev.rvb_tbl) (void)hipFree(b->dev.rvb_tbl);
+    for (void *p : {(void *)b->rec, b->obs_groups, b->obs_series, b->obs_out}) if (p) (void)hipFree(p);
     for (hipEvent_t ev : b->evpool) (void)hipEventDestroy(ev);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
@@ -1124,6 +1149,12 @@ int isingmc_timesteps(isingmc_batch *b, uint64_t t, const double *beta, uint32_t
     if (flags & ISINGMC_FLAG_PREP) m |= 0x10000u;
     if (sampling_freq == 0) sampling_freq = 1; // qmc_stepper.rs:147 unwrap_or(1)
     if (t == 0) return ISINGMC_OK;
+    if (b->rec && t / sampling_freq > (uint64_t)(b->rec_cap - b->rec_count)) { // before anything is launched: the batch stays as it is
+        char buf[160];
+        snprintf(buf, sizeof buf, "sample record: %llu samples do not fit behind the %u recorded (capacity %u)", (unsigned long long)(t / sampling_freq), b->rec_count, b->rec_cap);
+        b->err = buf;
+        return ISINGMC_ECAPACITY;
+    }
     return run(b, beta, t, sampling_freq, m, 0.5, nullptr);
 }
 
@@ -1435,6 +1466,137 @@ int isingmc_get_launch_info(const isingmc_batch *b, uint32_t out[8]) {
     if (!b || !out) return ISINGMC_EINVAL;
     out[0] = b->W; out[1] = (uint32_t)lds_bytes_of(b->lds_words); out[2] = b->dev.lds_ufcap; out[3] = b->dev.nwords;
     out[4] = b->K; out[5] = b->mode == SSE_MODE_LDS_EDGES ? 1u : 0u; out[6] = (b->fused_launch ? 0u : 1u) | (b->last_W_off << 8) | (is_tg(b) ? 2u : 0u) | (b->fast_diag ? 4u : 0u) | (b->last_lean ? 32u : 0u) | (b->last_rvb_split ? 64u : 0u) | (b->last_rvb_global ? 128u : 0u) | ((b->last_rvb_split ? b->rvb_main_W : 0u) << 16); out[7] = (uint32_t)lds_bytes_of(b->lds_words_diag);
+    return ISINGMC_OK;
+}
+
+// ---- sample record (include/isingmc_hip.h) ----------------------------------------------------------------------------------
+static int rec_fail_alloc(isingmc_batch *b, const char *what, size_t bytes) {
+    (void)hipGetLastError();
+    char buf[160];
+    snprintf(buf, sizeof buf, "sample record: hipMalloc of %zu bytes (%s) failed", bytes, what);
+    b->err = buf;
+    return ISINGMC_ENODEVICE;
+}
+// a scratch buffer of at least `bytes`, kept for the next call (the stream is drained before an old one is freed)
+static int rec_grow(isingmc_batch *b, void **p, size_t *have, size_t bytes, const char *what) {
+    if (*have >= bytes && *p) return ISINGMC_OK;
+    if (*p) { (void)hipStreamSynchronize(b->stream); (void)hipFree(*p); *p = nullptr; *have = 0; }
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) return rec_fail_alloc(b, what, bytes);
+    *p = q; *have = bytes;
+    return ISINGMC_OK;
+}
+static int rec_range(isingmc_batch *b, uint32_t first, uint32_t count) {
+    if (!b->rec) { b->err = "no sample record attached (isingmc_record_attach)"; return ISINGMC_EINVAL; }
+    if (count == 0 || first > b->rec_count || count > b->rec_count - first) { b->err = "sample record: bad row range"; return ISINGMC_EINVAL; }
+    return ISINGMC_OK;
+}
+
+int isingmc_record_attach(isingmc_batch *b, uint32_t capacity) {
+    if (!b) return ISINGMC_EINVAL;
+    if (capacity > (1u << 20)) { b->err = "sample record: capacity above 2^20 samples"; return ISINGMC_EINVAL; }
+    HIP_TRY(b, hipSetDevice(b->device));
+    if (b->rec) { HIP_TRY(b, hipStreamSynchronize(b->stream)); (void)hipFree(b->rec); b->rec = nullptr; }
+    b->rec_cap = b->rec_count = 0;
+    if (capacity == 0) return ISINGMC_OK;
+    const size_t bytes = (size_t)capacity * b->dev.R * b->dev.nwords * sizeof(uint32_t);
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) return rec_fail_alloc(b, "record", bytes);
+    b->rec = (uint32_t *)q; b->rec_cap = capacity;
+    return ISINGMC_OK;
+}
+int isingmc_record_count(const isingmc_batch *b, uint32_t *count, uint32_t *capacity) {
+    if (!b) return ISINGMC_EINVAL;
+    if (count) *count = b->rec_count;
+    if (capacity) *capacity = b->rec_cap;
+    return ISINGMC_OK;
+}
+int isingmc_record_clear(isingmc_batch *b) {
+    if (!b) return ISINGMC_EINVAL;
+    b->rec_count = 0;
+    return ISINGMC_OK;
+}
+int isingmc_record_read(isingmc_batch *b, uint32_t first, uint32_t count, uint32_t r, uint8_t *out) {
+    if (!b) return ISINGMC_EINVAL;
+    if (!out || (r != UINT32_MAX && r >= b->dev.R)) { b->err = "bad replica index"; return ISINGMC_EINVAL; }
+    if (const int rc = rec_range(b, first, count)) return rc;
+    HIP_TRY(b, hipSetDevice(b->device));
+    const uint32_t R = b->dev.R, N = b->dev.N, nw = b->dev.nwords;
+    const uint32_t cnt = r == UINT32_MAX ? R : 1u, r0 = r == UINT32_MAX ? 0u : r;
+    // in pieces of at most 16 Mi words: rows of the selected replicas (one replica's rows are R * nwords words apart)
+    const size_t per_row = (size_t)cnt * nw;
+    const uint32_t piece = (uint32_t)std::max<size_t>(1, ((size_t)1 << 24) / per_row);
+    std::vector<uint32_t> w(std::min<size_t>(piece, count) * per_row);
+    for (uint32_t t0 = 0; t0 < count; t0 += piece) {
+        const uint32_t nt = count - t0 < piece ? count - t0 : piece;
+        const uint32_t *src = b->rec + ((size_t)(first + t0) * R + r0) * nw;
+        HIP_TRY(b, hipMemcpy2DAsync(w.data(), per_row * 4, src, (size_t)R * nw * 4, per_row * 4, nt, hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        for (size_t i = 0; i < (size_t)nt * cnt; ++i) {
+            uint8_t *o = out + ((size_t)t0 * cnt + i) * N;
+            for (uint32_t v = 0; v < N; ++v) o[v] = (w[i * nw + (v >> 5)] >> (v & 31)) & 1u;
+        }
+    }
+    return ISINGMC_OK;
+}
+
+// checks the groups, uploads them and runs record_series_kernel into the batch's series buffer: [R][ngroups][(count + 31) / 32]
+static int rec_make_series(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars, const uint8_t *group_flip,
+                           uint32_t first, uint32_t count) {
+    if (!ngroups || !group_start || !group_vars) { b->err = "sample record: no observable groups"; return ISINGMC_EINVAL; }
+    if (const int rc = rec_range(b, first, count)) return rc;
+    if (group_start[0] != 0u) { b->err = "sample record: group_start[0] must be 0"; return ISINGMC_EINVAL; }
+    for (uint32_t g = 0; g < ngroups; ++g)
+        if (group_start[g + 1] <= group_start[g]) { b->err = "sample record: every observable group needs at least one variable"; return ISINGMC_EINVAL; }
+    const uint32_t nv = group_start[ngroups];
+    for (uint32_t k = 0; k < nv; ++k)
+        if (group_vars[k] >= b->dev.N) { b->err = "sample record: group variable out of range"; return ISINGMC_EINVAL; }
+    if (4 * obs_series_lds_words(b->dev.nwords) > 4 * b->lds_total_words) {
+        b->err = "sample record: 64 state rows of this model exceed LDS (record_series_kernel stages them there)";
+        return ISINGMC_ENOTIMPL;
+    }
+    HIP_TRY(b, hipSetDevice(b->device));
+    // groups: [ngroups + 1] starts, [nv] variables, [ngroups] flip bytes
+    const size_t o_vars = (size_t)(ngroups + 1) * 4, o_flip = o_vars + (size_t)nv * 4;
+    if (const int rc = rec_grow(b, &b->obs_groups, &b->obs_groups_bytes, o_flip + ngroups, "observable groups")) return rc;
+    const size_t Tw = (count + 31u) / 32u;
+    if (const int rc = rec_grow(b, &b->obs_series, &b->obs_series_bytes, (size_t)b->dev.R * ngroups * Tw * 4, "bit series")) return rc;
+    char *gbuf = (char *)b->obs_groups;
+    HIP_TRY(b, hipMemcpyAsync(gbuf, group_start, o_vars, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(b, hipMemcpyAsync(gbuf + o_vars, group_vars, (size_t)nv * 4, hipMemcpyHostToDevice, b->stream));
+    if (group_flip) HIP_TRY(b, hipMemcpyAsync(gbuf + o_flip, group_flip, ngroups, hipMemcpyHostToDevice, b->stream));
+    ObsGroups G{ngroups, (const uint32_t *)gbuf, (const uint32_t *)(gbuf + o_vars), group_flip ? (const uint8_t *)(gbuf + o_flip) : nullptr};
+    const uint32_t *rows = b->rec + (size_t)first * b->dev.R * b->dev.nwords;
+    const hipError_t e = launch_record_series(b->stream, rows, b->dev.R, b->dev.nwords, count, G, (uint32_t *)b->obs_series);
+    if (e != hipSuccess) { b->err = std::string("record_series launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    return ISINGMC_OK;
+}
+
+int isingmc_record_series(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars, const uint8_t *group_flip,
+                          uint32_t first, uint32_t count, uint32_t *out_bits) {
+    if (!b) return ISINGMC_EINVAL;
+    if (!out_bits) { b->err = "sample record: no output buffer"; return ISINGMC_EINVAL; }
+    if (const int rc = rec_make_series(b, ngroups, group_start, group_vars, group_flip, first, count)) return rc;
+    const size_t bytes = (size_t)b->dev.R * ngroups * ((count + 31u) / 32u) * 4;
+    HIP_TRY(b, hipMemcpyAsync(out_bits, b->obs_series, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    return ISINGMC_OK;
+}
+int isingmc_record_autocorrelation(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars,
+                                   uint32_t first, uint32_t count, double *out) {
+    if (!b) return ISINGMC_EINVAL;
+    if (!out) { b->err = "sample record: no output buffer"; return ISINGMC_EINVAL; }
+    if (b->rec && 4 * (obs_autocorr_lds_words(count) + 2) > 4 * b->lds_total_words) {
+        b->err = "sample record: a series of this many samples, twice, exceeds LDS (bit_autocorr_kernel keeps it there)";
+        return ISINGMC_ENOTIMPL;
+    }
+    if (const int rc = rec_make_series(b, ngroups, group_start, group_vars, nullptr, first, count)) return rc;
+    const size_t bytes = (size_t)b->dev.R * count * sizeof(double);
+    if (const int rc = rec_grow(b, &b->obs_out, &b->obs_out_bytes, bytes, "autocorrelations")) return rc;
+    const hipError_t e = launch_bit_autocorr(b->stream, (const uint32_t *)b->obs_series, b->dev.R, ngroups, count, (double *)b->obs_out);
+    if (e != hipSuccess) { b->err = std::string("bit_autocorr launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    HIP_TRY(b, hipMemcpyAsync(out, b->obs_out, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
     return ISINGMC_OK;
 }
 

@@ -1714,6 +1714,30 @@ size_t rvb_split_prod_stride(uint32_t Nb);                                      
 // sweep_rvb_global.hip: the RVB sweep alone with its per-variable tables in HBM (SSE_PASSES_RVB_G; c.W = 16, c.K = 4; B.rvb_tbl allocated)
 hipError_t launch_rvb_global(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A);
 
+// observe.hip (sse_observe.hip.h): the sample record's observables, record -> bit series -> autocorrelations
+constexpr uint32_t OBS_TILE = 64;         // samples per workgroup of record_series_kernel: one wave's ballot
+constexpr uint32_t OBS_SERIES_WAVES = 4;  // waves of that workgroup (they share the staged rows and split the groups)
+constexpr uint32_t OBS_LAGS = 4;          // lags per lane and pass of bit_autocorr_kernel
+constexpr uint32_t OBS_MAX_THREADS = 1024;
+
+// LDS row stride of the staged state rows: odd, so that the 32 lanes of a half-wave, which read the same word of 32
+// consecutive rows, fall on 32 different banks (nwords = 32 at N = 1024 would put them all on one)
+__host__ __device__ inline uint32_t obs_row_stride(uint32_t nwords) { return nwords | 1u; }
+__host__ __device__ inline size_t obs_series_lds_words(uint32_t nwords) { return (size_t)OBS_TILE * obs_row_stride(nwords); }
+// LDS words of bit_autocorr_kernel's series image: the series twice back to back (2 T bits in 2 Tw words).  Lag tau reads the
+// words (tau >> 5) + w and + w + 1 for w < Tw, at most word 2 Tw - 1, and of them the bits below tau + T <= 2 T - 1.
+__host__ __device__ inline size_t obs_autocorr_lds_words(uint32_t T) { return 2 * (size_t)((T + 31u) / 32u); }
+
+struct ObsGroups {
+    uint32_t ngroups;
+    const uint32_t *start;  // [ngroups + 1] offsets into vars
+    const uint32_t *vars;   // variables of every group, < N
+    const uint8_t *flip;    // [ngroups] or nullptr
+};
+
+hipError_t launch_record_series(hipStream_t stream, const uint32_t *rec, uint32_t R, uint32_t nwords, uint32_t T, const ObsGroups &G, uint32_t *out);
+hipError_t launch_bit_autocorr(hipStream_t stream, const uint32_t *series, uint32_t R, uint32_t ngroups, uint32_t T, double *out);
+
 template <int W, int K, int CL, int PHASE, int PASSES>
 hipError_t launch_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_kernel<W, K, CL, PHASE, PASSES>),

@@ -49,7 +49,9 @@ extern "C" {
                                         realisations on one graph. */
 #define ISINGMC_CFG_GLOBAL_TABLES 8u /* keep the per-variable scan tables (spins, cut ranks) in a per-replica HBM scratch instead of
                                         LDS.  Chosen automatically for models whose tables exceed LDS (N >~ 10^4 variables, e.g. a
-                                        32^3 lattice); this flag forces the path on any model (testing).  Needs
+                                        32^3 lattice; the compact edge table of a uniform-|J| model leaves LDS first, and
+                                        with it the tables of a chain stay in LDS up to N ~ 11000); this flag forces the path
+                                        on any model (testing) and then needs
                                         ISINGMC_CFG_NO_LDS_TABLES or non-uniform couplings; slots_per_lane 1 or 4; RVB updates only with
                                         ISINGMC_CFG_RVB_GLOBAL_TABLES (without it they return ISINGMC_ENOTIMPL). */
 #define ISINGMC_CFG_NO_FAST_DIAG 16u /* run the diagonal pass through the general kernel even where the instruction-trimmed one

@@ -788,7 +788,7 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
     if (!generic && !(cfg->transverse >= 0.0)) { g_create_error = "transverse field must be >= 0"; return ISINGMC_EINVAL; }
     for (uint32_t e = 0; !generic && e < cfg->nedges; ++e)
         if (cfg->edges[2 * e] >= cfg->nvars || cfg->edges[2 * e + 1] >= cfg->nvars || cfg->edges[2 * e] == cfg->edges[2 * e + 1]) {
-            g_create_error = "edge endpoint out of range";
+            g_create_error = cfg->edges[2 * e] == cfg->edges[2 * e + 1] ? "edge joins a variable to itself (self-loop)" : "edge endpoint out of range";
             return ISINGMC_EINVAL;
         }
     int ndev = 0;
@@ -912,19 +912,31 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
         for (uint32_t e = 0; e < D.E; ++e) if (tab[(size_t)hI * D.Nb + e].w != tab[0].w) { D.uniformJ = 0u; break; }
     b->fused_launch = (cfg->flags & ISINGMC_CFG_FUSED_LAUNCH) != 0;
     D.rvb_growers = (cfg->flags & ISINGMC_CFG_RVB_SERIAL_GROWTH) ? 0u : 64u;
-    const bool CL = !generic && !perJ && D.uniformJ && D.N <= SSE_CE_MAX_VARS && (size_t)D.E * 4 <= 48 * 1024 && !(cfg->flags & ISINGMC_CFG_NO_LDS_TABLES);
-    const uint32_t ledges = CL ? D.E : 0u;
+    bool CL = !generic && !perJ && D.uniformJ && D.N <= SSE_CE_MAX_VARS && (size_t)D.E * 4 <= 48 * 1024 && !(cfg->flags & ISINGMC_CFG_NO_LDS_TABLES);
+    uint32_t ledges = CL ? D.E : 0u;
     // Per-variable scan tables: in LDS while W copies of them fit (with room for a union-find), otherwise in a per-replica
     // HBM scratch served by L2 / Infinity Cache (MODE 2; ISINGMC_CFG_GLOBAL_TABLES forces it on any model).
     bool TG = (cfg->flags & ISINGMC_CFG_GLOBAL_TABLES) != 0;
     // (words of the general launch at w waves, tables in LDS, no union-find)
     auto fixed_lds = [&](uint32_t w) { return general_lds_words(w, D, ledges, false, 0u, 0u); };
-    if (!TG && fixed_lds(W) + 4096 > total_words) {
-        if (cfg->waves_per_replica) { // explicit geometry: keep the LDS tables if a smaller W makes them fit (previous behaviour)
-            while (W > 1 && fixed_lds(W) + 4096 > total_words) W = (W == 4) ? 1 : (W == 6 ? 4 : W >> 1);
-            if (fixed_lds(W) + 64 > total_words) TG = true, W = cfg->waves_per_replica;
-        } else TG = true;
+    // the engine's own move of the tables to HBM (the caller did not ask for it): true when they do not fit at the geometry asked for
+    auto tables_to_hbm = [&]() {
+        W = cfg->waves_per_replica ? cfg->waves_per_replica : 4;
+        if (fixed_lds(W) + 4096 <= total_words) return false;
+        if (!cfg->waves_per_replica) return true;
+        // explicit geometry: keep the LDS tables if a smaller W makes them fit (previous behaviour)
+        while (W > 1 && fixed_lds(W) + 4096 > total_words) W = (W == 4) ? 1 : (W == 6 ? 4 : W >> 1);
+        if (fixed_lds(W) + 64 <= total_words) return false;
+        W = cfg->waves_per_replica;
+        return true;
+    };
+    if (!TG && tables_to_hbm()) {
+        // The tables do not fit next to the compact edge table (a long chain: up to 48 KB of edges): the edge table leaves LDS first
+        // (the general bond table serves the model), and the HBM tables, which need the general bond table, come without it too.
+        if (CL) { CL = false; ledges = 0u; TG = tables_to_hbm(); }
+        else TG = true;
     }
+    // (only with the caller's own ISINGMC_CFG_GLOBAL_TABLES)
     if (TG && CL) { b->err = "ISINGMC_CFG_GLOBAL_TABLES needs the general bond table: combine it with ISINGMC_CFG_NO_LDS_TABLES"; return fail(ISINGMC_EINVAL); }
     if (TG && K == 2) K = 4;
     const uint32_t pm_room = TG ? (D.E + 31u) / 32u : 0u; // (room for the +-J decode's signs, decided below)

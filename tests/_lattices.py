@@ -20,6 +20,29 @@ def two_d_ferro(l):
     return two_d_periodic(l, lambda i, j, d: -1.0)
 
 
+def rect_periodic(lx, ly, jfun=None):
+    """lx x ly periodic lattice with the ordering rule of two_d_periodic: site (i,j) -> j*lx+i, i < lx, j < ly, visited with i
+    outermost; all right bonds first, then all down bonds (a side of length 1 or 2 gives self-loops or duplicate edges:
+    callers keep both sides >= 3)."""
+    idx = [(i, j) for i in range(lx) for j in range(ly)]
+    f = lambda i, j: j * lx + i
+    if jfun is None:
+        jfun = lambda i, j, d: -1.0 if d == 0 else (1.0 if i % 2 == 0 else -1.0)
+    right = [((f(i, j), f((i + 1) % lx, j)), jfun(i, j, 0)) for i, j in idx]
+    down = [((f(i, j), f(i, (j + 1) % ly)), jfun(i, j, 1)) for i, j in idx]
+    return right + down
+
+
+def star(n, j=1.0):
+    """Variable 0 joined to each of 1 .. n-1 (degree n - 1 at the centre, 1 everywhere else)."""
+    return [((0, v), j) for v in range(1, n)]
+
+
+def complete(n, j=1.0):
+    """Every pair (a, b), a < b, in lexicographic order."""
+    return [((a, b), j) for a in range(n) for b in range(a + 1, n)]
+
+
 def split(edges):
     return [list(e) for e, _ in edges], [j for _, j in edges]
 

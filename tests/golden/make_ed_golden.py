@@ -55,6 +55,18 @@ CASES = [
     dict(name="single_bond", n=2, edges=[(0, 1, 1.0)], gamma=1.0, h=0.0, betas=[1.0]),
     dict(name="ring5_randmag", n=5, edges=[(0, 1, 0.7), (1, 2, -1.3), (2, 3, 1.9), (3, 4, -0.6), (4, 0, 1.1)],
          gamma=1.2, h=0.0, betas=[1.0, 3.0]),
+    # degenerate topologies (the GPU parity tests of tests/test_gpu_shape_edges.py lean on the oracle being right on them); the tag
+    # keeps them out of the high-statistics GPU rows of tests/test_gpu_ed_statistics.py, which stay on the systems above
+    dict(degenerate=True, name="noedges4", n=4, edges=[], gamma=1.0, h=0.0, betas=[1.0]),
+    dict(degenerate=True, name="noedges3_long", n=3, edges=[], gamma=0.7, h=0.4, betas=[1.5]),
+    dict(degenerate=True, name="isolated6", n=6, edges=[(0, 1, 1.0), (1, 3, -1.0)], gamma=1.0, h=0.0, betas=[1.0, 2.0]),  # 2, 4 and 5 (the highest index) isolated
+    dict(degenerate=True, name="isolated5_long", n=5, edges=[(0, 2, -1.0)], gamma=0.8, h=-0.3, betas=[1.5]),
+    dict(degenerate=True, name="dup_same_sign", n=3, edges=[(0, 1, 1.0), (0, 1, 1.0), (1, 2, -1.0)], gamma=1.0, h=0.0, betas=[1.5]),
+    dict(degenerate=True, name="dup_opposite_sign", n=3, edges=[(0, 1, 1.0), (0, 1, -1.0), (1, 2, 1.0)], gamma=1.0, h=0.0, betas=[1.5]),
+    dict(degenerate=True, name="dup_reversed", n=3, edges=[(0, 1, 0.8), (1, 0, 0.8), (1, 2, -1.0), (2, 0, 1.0)], gamma=1.0, h=0.2, betas=[1.5]),
+    dict(degenerate=True, name="star6_fm", n=6, edges=[(0, v, -1.0) for v in range(1, 6)], gamma=1.0, h=0.0, betas=[1.0, 2.0]),
+    dict(degenerate=True, name="k5_afm", n=5, edges=[(a, b, 1.0) for a in range(5) for b in range(a + 1, 5)], gamma=1.0, h=0.0, betas=[1.0]),
+    dict(degenerate=True, name="k4_fm_long", n=4, edges=[(a, b, -0.5) for a in range(4) for b in range(a + 1, 4)], gamma=1.0, h=0.3, betas=[1.0]),
 ]
 
 
@@ -97,6 +109,8 @@ def main():
     for c in CASES:
         rec = dict(name=c["name"], nvars=c["n"], edges=[[a, b] for a, b, _ in c["edges"]],
                    J=[j for _, _, j in c["edges"]], gamma=c["gamma"], h=c["h"], results=[])
+        if c.get("degenerate"):
+            rec["degenerate"] = True
         for beta in c["betas"]:
             rec["results"].append(thermal(c["n"], c["edges"], c["gamma"], c["h"], beta))
         out.append(rec)

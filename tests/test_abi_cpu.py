@@ -150,6 +150,39 @@ def test_lattice_builders_match_reference_ordering():
     assert lat.one_d_periodic(16)[-1] == ((15, 0), 1.0)
 
 
+def test_rectangular_star_and_complete_builders():
+    import _lattices as lat
+    fs = [None, lambda i, j, d: -1.0, lambda i, j, d: 0.5 + 0.25 * ((3 * i + 5 * j + d) % 7)]
+    for l in (3, 4, 5, 8):
+        for f in fs:
+            assert lat.rect_periodic(l, l, f) == lat.two_d_periodic(l, f)
+    e = lat.rect_periodic(3, 5)
+    assert len(e) == 30 and max(max(ab) for ab, _ in e) == 14 and len({ab for ab, _ in e}) == 30
+    assert e[0][0] == (0, 1) and e[2 * 5][0] == (2, 0) and e[15][0] == (0, 3) and e[15 + 4][0] == (12, 0)  # wraps: i = 2 -> 0, j = 4 -> 0
+    deg = np.bincount(np.array([ab for ab, _ in e]).ravel(), minlength=15)
+    assert (deg == 4).all()
+    assert lat.star(5, -2.0) == [((0, 1), -2.0), ((0, 2), -2.0), ((0, 3), -2.0), ((0, 4), -2.0)]
+    k = lat.complete(12, 1.0)
+    assert len(k) == 66 and k[0][0] == (0, 1) and k[-1][0] == (10, 11) and len({ab for ab, _ in k}) == 66
+
+
+def test_create_rejects_self_loops_before_any_device():
+    """An edge (a, a) is sz_a sz_a = 1: a constant the reference never checks for and whose two-variable op would name one variable
+    twice (the op word carries two in / out bits for it).  isingmc_create refuses it, before it looks for a device."""
+    import isingmontecarlo_amd as im
+    lib = im.load_library()
+    h = C.c_void_p()
+    ed = np.array([0, 1, 2, 2, 1, 2], dtype=np.uint32); js = np.array([1.0, 1.0, -1.0])
+    cfg = im._Config(struct_size=C.sizeof(im._Config), nreplicas=1, nvars=3, nedges=3,
+                     edges=ed.ctypes.data_as(C.POINTER(C.c_uint32)), J=js.ctypes.data_as(C.POINTER(C.c_double)),
+                     transverse=1.0, capacity=8, cutoff0=4, device=-1)
+    assert lib.isingmc_create(C.byref(cfg), C.byref(h)) == -1 and not h.value
+    assert b"self-loop" in lib.isingmc_last_error(None)
+    with pytest.raises(im.IsingMcError) as ei:
+        im.QmcIsingGraph([((0, 1), 1.0), ((1, 1), 1.0)], 1.0, 0.0, 4, 1)
+    assert ei.value.code == -1 and "self-loop" in str(ei.value)
+
+
 def test_fft_autocorrelation_matches_direct_sum():
     """fft_autocorrelation (autocorrelations.rs:99-133) against the defining circular sum."""
     from isingmontecarlo_amd.autocorrelations import fft_autocorrelation
@@ -250,7 +283,8 @@ def test_row_stride_covers_every_whole_tile_access():
     lib = im.load_library()
     out = (C.c_uint32 * 4)()
     rng = np.random.default_rng(5)
-    caps = [1, 2, 63, 64, 255, 256, 257, 1023, 1024, 4095, 4096, 4097, 8192, 32768 + 1, 1 << 18, (1 << 18) + 777, 1 << 20, 3_000_001] + [int(x) for x in rng.integers(1, 1 << 22, 60)]
+    caps = [1, 2, 63, 64, 97, 255, 256, 257, 1023, 1024, 4095, 4096, 4097, 8191, 8192, 32768 + 1, 1 << 18, (1 << 18) + 777, 1 << 20, 3_000_001] + [int(x) for x in rng.integers(1, 1 << 22, 60)]
+    caps += [24 * n + 256 for n in (1, 33, 4071, 4072, 4095, 4096, 4097, 6144, 6175, 8480, 8481, 11041, 11042, 12288, 12289)]  # tests/test_gpu_shape_edges.py
     for cap in caps:
         for W, Wmax in [(1, 1), (4, 4), (4, 8), (4, 16), (6, 6), (6, 16), (8, 8), (8, 16), (16, 16), (1, 16)]:
             for K in (1, 2, 4):
@@ -297,7 +331,7 @@ def test_dedicated_cluster_kernel_lds_layout_and_gate():
         return [int(x) for x in out]
 
     rng = np.random.default_rng(11)
-    Ns = sorted(set(range(1, 257)) | set(range(257, 4096, 37)) | {511, 512, 1023, 1024, 1025, 2047, 2048, 4094, 4095})
+    Ns = sorted(set(range(1, 257)) | set(range(257, 4096, 37)) | {511, 512, 1023, 1024, 1025, 2047, 2048, 4071, 4072, 4094, 4095})
     accepted = rejected_by_bits = 0
     for N in Ns:
         tab = 16 * (N + 1)

@@ -45,7 +45,9 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 with open(os.path.join(HERE, "golden", "ed_tfim.json")) as f:
-    ED = json.load(f)
+    # (the systems tagged "degenerate" -- no edges, isolated variables, duplicate edges, star, complete graph -- pin the CPU oracle in
+    # tests/test_oracle_cpu.py for the parity tests of tests/test_gpu_shape_edges.py; the rows here keep the regular systems)
+    ED = [c for c in json.load(f) if not c.get("degenerate")]
 SYSTEMS = {c["name"]: c for c in ED}
 OBS = ("energy", "abs_m", "m2", "sx")
 

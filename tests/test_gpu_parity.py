@@ -8,10 +8,10 @@ import _lattices as lat
 pytestmark = pytest.mark.gpu
 
 
-def make_pair(oracle, edges, gamma, h, cutoff, cap, seed, R, waves=0, state=None, k=0, cfg_flags=0, uf_limit=0):
+def make_pair(oracle, edges, gamma, h, cutoff, cap, seed, R, waves=0, state=None, k=0, cfg_flags=0, uf_limit=0, nvars=None):
     import isingmontecarlo_amd as im
     g = im.QmcIsingGraph(edges, gamma, h, cutoff, seed, state=state, nreplicas=R, capacity=cap,
-                         waves_per_replica=waves, slots_per_lane=k, cfg_flags=cfg_flags, lds_uf_ids_limit=uf_limit)
+                         waves_per_replica=waves, slots_per_lane=k, cfg_flags=cfg_flags, lds_uf_ids_limit=uf_limit, nvars=nvars)
     e, j = lat.split(edges)
     m = oracle.Model(g.nvars, e, j, gamma, h)
     reps = [oracle.Replica(m, cap, cutoff, seed, r, None if state is None else state) for r in range(R)]

@@ -658,7 +658,9 @@ class QmcIsingGraph:
         return (ms[0], ms[1]), (n[0], n[1])
 
     def last_rvb_ms(self):
-        """(ms, launches) of the RVB-sweep launches of the last run (part of last_pass_ms()[0][1])."""
+        """(ms, launches) of the RVB sweeps that ran as launches of their own in the last run; both are part of index 1 of
+        last_pass_ms().  Only calls with split launches keep them: with CFG_FUSED_LAUNCH, and after single_rvb_sweep, both are 0
+        even where such launches ran (they are all counted under last_pass_ms()[1][1])."""
         ms, n = C.c_float(), C.c_uint32()
         self._check(self._lib.isingmc_last_rvb_ms(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value

@@ -293,11 +293,13 @@ static void give_lds(LaunchCfg &c, DevBatch &d, size_t words) {
 // stays small enough for two workgroups per CU whenever the model allows it.  Replicas that outgrow it use the HBM
 // union-find for that sweep and the host enlarges the table before the next launch.
 struct LdsPlan { uint32_t W, ufcap; size_t words; bool all_ids_fit; };
+// ids that the union-find of a launch at W waves is sized for: W per variable, the transverse ops seen so far, headroom
+static size_t uf_ids_wanted(const isingmc_batch *b, uint32_t W) { return (size_t)W * b->dev.N + b->max_ntrans + b->max_ntrans / 16 + 384; }
 static LdsPlan plan_lds(const isingmc_batch *b, uint32_t W) {
     const DevBatch &D = b->dev;
     auto words = [&](size_t ids) { return general_lds_words(W, D, lds_edges(b), is_tg(b), is_pm(b) ? D.pm_words : 0u, (uint32_t)ids); };
     const size_t ids_max = (size_t)W * D.N + D.cap;
-    const size_t want = (size_t)W * D.N + b->max_ntrans + b->max_ntrans / 16 + 384;
+    const size_t want = uf_ids_wanted(b, W);
     size_t ids = want;
     if (b->uf_ids_limit) ids = b->uf_ids_limit;
     if (is_tg(b)) ids = 0; // tables in HBM: the union-find lives there too
@@ -326,7 +328,7 @@ static LeanPlan plan_lean(const isingmc_batch *b) {
     LeanPlan p{false, 0u, 0};
     if (!b->lean_cluster) return p;
     const size_t ids_max = (size_t)16 * D.N + D.cap;
-    size_t want = (size_t)16 * D.N + b->max_ntrans + b->max_ntrans / 16 + 384;
+    size_t want = uf_ids_wanted(b, 16);
     if (want > ids_max) want = ids_max;
     if (want > 65535 || !cluster_ids_fit(D.N, (uint32_t)want - 1u, (uint32_t)want)) return p;
     const size_t words = cluster_lds_words(D.N, D.nwords, D.Nb, (uint32_t)want, D.has_long != 0u);
@@ -382,26 +384,73 @@ static hipError_t record_append(isingmc_batch *b) {
     return e;
 }
 
-static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t freq, uint32_t domask, double prob,
-               uint32_t *out_host) {
-    if (!b) return ISINGMC_EINVAL;
+// ---- The sweep driver: prepare() once per call, plan_step() for the launches of a timestep, run() walks them in one loop ----
+// One kernel launch of a timestep as a value: plan_step() lists them in order, issue() makes its DevBatch and SweepArgs and dispatches it.
+enum LaunchKind : uint8_t {
+    L_SWEEP, L_FAST_DIAG, // the general kernel of cfg.W waves and cfg.passes; the trimmed diagonal kernel (sse_fast.hip.h)
+    L_CLUSTER,            // the dedicated cluster kernel (sse_cluster.hip.h); an only_flagged L_SWEEP follows for the replicas it flagged
+    L_RVB_FUSED, L_RVB_GROW, L_RVB_MAIN, L_RVB_GLOBAL, // the RVB sweep: in the general kernel; growth, then main launch (sse_rvb_split.hip.h); tables in HBM
+};
+enum Bucket : uint8_t { B_DIAG = 0, B_OTHER = 1, B_RVB = 2 }; // index into pass_ms / pass_launches; an RVB launch counts under B_OTHER too
+struct Launch {
+    LaunchKind kind;
+    Bucket bucket;
+    bool sampled;      // carries the call's sampling_freq / out_u32 (and runs on a sampled step even with an empty domask)
+    bool only_flagged; // SweepArgs::only_flagged
+    bool follows;      // second kernel of the launch before it: counted and timed with that one
+    uint32_t domask, ufcap, flipcap; // its passes; DevBatch::lds_ufcap and lds_flipcap
+    size_t words;      // its dynamic LDS
+    LaunchCfg cfg;     // (lds_bytes: filled in by issue())
+};
+struct Plan {
+    Launch l[5];    // (at most: diagonal, RVB growth + main, cluster + its follow-up)
+    uint32_t n;
+    bool replan;    // a split call without RVB sweeps: planned again every REPLAN_EVERY steps, from the transverse-op counts seen by then
+    bool lean;      // the dedicated cluster kernel would take a cluster launch (reported as last_lean whether or not one follows)
+    uint32_t W_off; // waves chosen for the off-diagonal launches (reported as last_W_off), 0 = no choice made
+};
+struct Call { // what a call asks for, fixed by prepare()
+    SweepArgs A;          // passes, sampling and outputs of the whole call; issue() narrows them per launch
+    uint64_t nsteps, chunk; // chunk: steps per walk through the plan (1, or the steps of a fused launch)
+    uint32_t phase;
+    bool split;           // a diagonal launch and the rest per timestep, instead of whole timesteps per launch
+    bool recording;       // a sample record is attached and the call samples
+};
+constexpr size_t MAX_TIMED = 256; // steps of a split call whose launches carry events
+constexpr uint64_t REPLAN_EVERY = 16;
+static bool rvb_alone(uint32_t m) { return (m & ~SSE_DO_GROW) == SSE_DO_RVB; }
+// whole timesteps per launch around an RVB sweep with its tables in HBM, which needs a launch of its own
+static bool fused_around_rvb_g(const isingmc_batch *b, const Call &c) { return !c.split && (c.A.domask & SSE_DO_RVB) && b->rvb_global && !rvb_alone(c.A.domask); }
+// the RVB sweep of a split timestep is a launch of its own unless a directed loop runs too (then both stay in the all-passes
+// second launch; with the tables in HBM there is no such kernel and the sweep is split out all the same)
+static bool split_rvb_own_launch(const isingmc_batch *b, uint32_t m) { return (m & SSE_DO_RVB) && (!(m & SSE_DO_LOOP) || b->rvb_global); }
+static uint32_t rvb_attempts(const isingmc_batch *b) { return b->rvb_updates ? b->rvb_updates : (b->dev.N + 1u) / 2u; }
+// Does the dedicated cluster kernel take a launch of these passes?  Its plan fits, K is one of its two, no test limit on the
+// ids, cluster with or without free spins and nothing else, one step per launch.
+static bool lean_takes(const isingmc_batch *b, const LeanPlan &lean, uint32_t mask, bool one_step) {
+    return lean.ok && (b->K == 4 || b->K == 2) && !b->uf_ids_limit && (mask & SSE_DO_CLUSTER) && !(mask & ~(SSE_DO_CLUSTER | SSE_DO_FREE)) && one_step;
+}
+
+// Once per call: argument checks, the beta upload, pending flips, every allocation.  The step loop allocates and frees nothing.
+static int prepare(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t freq, uint32_t domask, double prob, uint32_t *out_host, Call &c) {
     HIP_TRY(b, hipSetDevice(b->device));
-    SweepArgs A{};
-    A.beta = nullptr;
+    SweepArgs &A = c.A;
     if (beta) {
         for (uint32_t r = 0; r < b->dev.R; ++r)
             if (!(beta[r] >= 0.0) || !std::isfinite(beta[r])) { b->err = "beta must be finite and >= 0"; return ISINGMC_EINVAL; }
         HIP_TRY(b, hipMemcpyAsync(b->d_beta, beta, sizeof(double) * b->dev.R, hipMemcpyHostToDevice, b->stream));
         A.beta = b->d_beta;
-    } else if (b->beta_dev) {
-        A.beta = b->beta_dev;
-    } else if (domask & SSE_DO_DIAG) {
-        b->err = "beta is required for a diagonal update";
-        return ISINGMC_EINVAL;
-    }
+    } else if (b->beta_dev) A.beta = b->beta_dev;
+    else if (domask & SSE_DO_DIAG) { b->err = "beta is required for a diagonal update"; return ISINGMC_EINVAL; }
     if ((domask & SSE_DO_RVB) && b->generic) { b->err = "RVB updates are Ising-specific: not available with generic interactions"; return ISINGMC_ENOTIMPL; }
     if ((domask & SSE_DO_CLUSTER) && b->generic && !b->generic_sym) { b->err = "Cannot perform cluster updates on graphs that break ising symmetry."; return ISINGMC_ENOTIMPL; } // qmc_runner.rs:224-226
     if ((domask & SSE_DO_RVB) && is_tg(b) && !b->rvb_global) { b->err = "RVB updates keep their working set in LDS: not available for models whose per-variable tables live in HBM (set ISINGMC_CFG_RVB_GLOBAL_TABLES)"; return ISINGMC_ENOTIMPL; }
+    A.sampling_freq = freq; A.domask = domask & 0xFFFFu; A.prob = prob; A.rvb_updates = b->rvb_updates;
+    A.out_u32 = out_host ? b->d_out : nullptr;
+    c.nsteps = nsteps; c.phase = (domask >> 16) & 1u;
+    c.split = !b->fused_launch && (domask & SSE_DO_DIAG);
+    c.recording = b->rec && freq; // (freq != 0: timesteps; single updates sample nothing)
+    c.chunk = (c.split || fused_around_rvb_g(b, c)) ? 1 : (b->steps_per_launch && b->steps_per_launch < nsteps ? b->steps_per_launch : nsteps);
     const bool rvb_g = (domask & SSE_DO_RVB) && b->rvb_global;
     if (rvb_g && !b->dev.rvb_tbl) { // the per-replica table scratch of RVB_G launches, on the first one (no fall-back when it cannot be had)
         const size_t words = rvb_tbl_words(b->dev.N, b->dev.E, b->dev.cap);
@@ -416,305 +465,252 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
         }
         b->dev.rvb_tbl = (uint32_t *)q;
     }
-    if (rvb_g && rvb_global_lds_words(b, 0) > b->lds_total_words) {
-        b->err = "RVB scratch (ISINGMC_CFG_RVB_GLOBAL_TABLES): the spin-state bit arrays and the fixed RVB regions exceed LDS";
-        return ISINGMC_ENOTIMPL;
-    }
+    if (rvb_g && rvb_global_lds_words(b, 0) > b->lds_total_words) { b->err = "RVB scratch (ISINGMC_CFG_RVB_GLOBAL_TABLES): the spin-state bit arrays and the fixed RVB regions exceed LDS"; return ISINGMC_ENOTIMPL; }
     if (domask & SSE_DO_RVB) b->last_rvb_global = false;
     // Pending cluster flips: only a call whose first launch is the trimmed diagonal kernel may start on the un-flipped strings
-    {
-        const bool first_is_fast_diag = !b->fused_launch && (domask & SSE_DO_DIAG) && b->fast_diag && !(domask & SSE_DO_HEATBATH) && b->defer;
-        if (b->pending && !first_is_fast_diag) { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
-    }
-    A.sampling_freq = freq;
-    A.domask = domask & 0xFFFFu;
-    A.prob = prob;
-    A.out_u32 = out_host ? b->d_out : nullptr;
-    A.rvb_updates = b->rvb_updates;
-    LaunchCfg lc{};
-    lc.W = b->W; lc.K = b->K; lc.mode = b->mode; lc.phase = (domask >> 16) & 1u; lc.stream = b->stream;
+    const bool first_is_fast_diag = c.split && b->fast_diag && !(domask & SSE_DO_HEATBATH) && b->defer;
+    if (b->pending && !first_is_fast_diag) { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
     size_lds(b);
     if (!b->dev.segs2 && (domask & SSE_DO_CLUSTER) && !plan_lds(b, b->W_off ? b->W_off : b->W).all_ids_fit) {
         // the cluster ids of (some) replicas need the 32-bit union-find in HBM: room for the second id of every slot
-        const int rc2 = dalloc(b, &b->dev.segs2, (size_t)b->dev.R * b->dev.stride, false);
-        if (rc2) return rc2;
+        if (const int rc2 = dalloc(b, &b->dev.segs2, (size_t)b->dev.R * b->dev.stride, false)) return rc2;
     }
-    give_lds(lc, b->dev, ((domask & SSE_DO_RVB) && b->lds_words_rvb > b->lds_words) ? b->lds_words_rvb : b->lds_words);
-    auto launch_dev = [&](const LaunchCfg &c, const DevBatch &dev, const SweepArgs &a) -> hipError_t {
-        switch (c.W) {
-        case 1: return launch_sweep_w1(c, dev, a);
-        case 4: return launch_sweep_w4(c, dev, a);
-        case 6: return launch_sweep_w6(c, dev, a);
-        case 8: return launch_sweep_w8(c, dev, a);
-        case 16: return launch_sweep_w16(c, dev, a);
-        default: return hipErrorInvalidValue;
-        }
-    };
-    auto fail_launch = [&](hipError_t e) { b->err = std::string("sweep launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; };
-    uint32_t launches = 0;
-    const bool recording = b->rec && freq; // (freq != 0: timesteps; single updates sample nothing)
-    auto fail_record = [&](hipError_t e) { b->err = std::string("sample record: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; };
     b->pass_ms[0] = b->pass_ms[1] = b->pass_ms[2] = 0.f;
     b->pass_launches[0] = b->pass_launches[1] = b->pass_launches[2] = 0;
-    // passes of the first ("diagonal") launch of a split timestep: the diagonal pass and, unless an RVB sweep has to
-    // come in between, the directed loop (one sequential walk: it gains nothing from the wider off-diagonal geometry)
-    const uint32_t diag_bits = SSE_DO_DIAG | SSE_DO_HEATBATH | SSE_DO_GROW | ((A.domask & SSE_DO_RVB) ? 0u : SSE_DO_LOOP);
-    const bool split = !b->fused_launch && (A.domask & SSE_DO_DIAG);
-    size_t timed_steps = 0; // split path: steps whose launches carry events
-    // launches without a diagonal or RVB pass use the kernel that leaves that code out
-    DevBatch dev_off = b->dev;
-    const bool loop_only = (A.domask & (SSE_DO_DIAG | SSE_DO_RVB | SSE_DO_CLUSTER | SSE_DO_FREE)) == 0 && (A.domask & SSE_DO_LOOP);
-    // The off-diagonal kernel is latency-bound and small in registers: more waves per replica help as long as the
-    // per-wave scan tables and the union-find of W*N + (transverse ops) ids still fit in LDS.  Decided from the largest
-    // transverse-op count seen so far, and again every few timesteps of a long call (the count grows while a batch
-    // equilibrates; replicas that outgrow the table only fall back to the slower HBM union-find, never fail).
-    auto plan_offdiag = [&]() {
-        uint32_t Wo = b->W_off ? b->W_off : b->W;
-        bool hbm_uf = false;
-        if (!b->W_off && b->W < 16) {
-            const LdsPlan p16 = plan_lds(b, 16);
-            if (p16.all_ids_fit) Wo = 16;
-            else if (b->w8_ok && !b->uf_ids_limit && !plan_lds(b, b->W).all_ids_fit) {
-                // the largest replicas need the 32-bit union-find in HBM whatever the geometry: spend the LDS on the scan
-                // tables of 8 waves instead of on a 16-bit parent table that they cannot use (the HBM path is bound by
-                // memory latency: twice the waves, twice the accesses in flight)
-                Wo = 8; hbm_uf = true;
-            }
-        }
-        LdsPlan po = plan_lds(b, Wo);
-        if (hbm_uf) { po.ufcap = 0; po.words = general_lds_words(Wo, b->dev, lds_edges(b), false, 0u, 0u) + 64; }
-        lc.W = Wo;
-        dev_off.lds_ufcap = po.ufcap;
-        dev_off.lds_flipcap = 0u;
-        size_t words = po.words;
-        if ((is_tg(b) || hbm_uf) && !(domask & SSE_DO_RVB)) {
-            // HBM union-find launch: the LDS behind the fixed regions takes the flip bits of the ids (Wo * N + transverse ops seen so
-            // far + headroom; a replica with more ids looks its flips up in HBM as before)
-            const size_t used = lds_bytes_of(words) / 4;
-            const size_t want = ((size_t)Wo * b->dev.N + b->max_ntrans + b->max_ntrans / 16 + 384 + 31) / 32;
-            const size_t avail = b->lds_total_words > used + 16 ? b->lds_total_words - used - 16 : 0;
-            const size_t fw = want < avail ? want : avail;
-            words = used + fw;
-            dev_off.lds_flipcap = (uint32_t)(32 * fw);
-        }
-        give_lds(lc, dev_off, words);
-        b->last_W_off = Wo;
-    };
-    bool use_dev_off = false;
-    const bool rvb_only = (A.domask & ~SSE_DO_GROW) == SSE_DO_RVB;
-    if ((split || rvb_only) && (A.domask & SSE_DO_RVB) && !b->W_off && b->W < 16) {
+    // records of a sweep's attempts, for an RVB sweep as a growth and a main launch (the attempt count is fixed for the call)
+    const uint32_t updates = rvb_attempts(b);
+    const size_t pstride = rvb_split_prod_stride(b->dev.Nb);
+    const bool rvb_own_launch = c.split ? split_rvb_own_launch(b, A.domask) : rvb_alone(A.domask);
+    if (rvb_own_launch && !b->rvb_global && b->rvb_split && c.chunk == 1 && pstride && b->dev.rvb_prod_cap < updates) {
+        if (b->dev.rvb_prod) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->dev.rvb_prod); b->dev.rvb_prod = nullptr; b->dev.rvb_prod_cap = 0; }
+        void *q = nullptr;
+        if (hipMalloc(&q, (size_t)b->dev.R * updates * pstride * sizeof(uint32_t)) == hipSuccess) { b->dev.rvb_prod = (uint32_t *)q; b->dev.rvb_prod_cap = updates; b->dev.rvb_prod_stride = (uint32_t)pstride; }
+        else { (void)hipGetLastError(); b->rvb_split = false; } // no room for the records: the fused kernel from now on
+    }
+    const size_t want_ev = c.split ? 4 * (size_t)(c.nsteps < MAX_TIMED ? c.nsteps : MAX_TIMED) : 0;
+    while (b->evpool.size() < want_ev) { hipEvent_t ev; HIP_TRY(b, hipEventCreate(&ev)); b->evpool.push_back(ev); }
+    return ISINGMC_OK;
+}
+
+// Kernel and geometry of the launch that carries a call's off-diagonal work: all of a fused call, what follows the diagonal launch
+// of a split one.  `base` is the all-passes launch in the batch's own geometry.
+static Launch plan_off(const isingmc_batch *b, const Call &c, const Launch &base, uint32_t *W_chosen) {
+    const uint32_t m = c.A.domask;
+    Launch o = base;
+    if ((c.split || rvb_alone(m)) && (m & SSE_DO_RVB) && !b->W_off && b->W < 16) {
         // RVB sweeps: the cooperative window scans of an attempt cover 4x more slots per step with 16 waves (the
         // sequential lane does not care); taken when the cluster tables of that geometry fit as well
         const LdsPlan p16 = plan_lds(b, 16);
         if (p16.all_ids_fit) {
-            size_t words = rvb_lds_words(16, b->dev, lds_edges(b), false, 0u);
-            if (words > b->lds_total_words) words = b->lds_total_words;
-            lc.W = 16; dev_off.lds_ufcap = p16.ufcap;
-            give_lds(lc, dev_off, words > p16.words ? words : p16.words);
-            use_dev_off = true;
-            b->last_W_off = 16;
+            const size_t words = std::min(rvb_lds_words(16, b->dev, lds_edges(b), false, 0u), b->lds_total_words);
+            *W_chosen = o.cfg.W = 16; o.ufcap = p16.ufcap; o.words = std::max(words, p16.words);
         }
     }
-    if (rvb_only) lc.passes = SSE_PASSES_RVB;   // the RVB sweep alone: its own kernel (no scratch spills, unlike the all-passes kernel)
-    else if (loop_only) lc.passes = SSE_PASSES_DIAG; // a lone directed loop uses the small launch geometry too
-    else if (!(A.domask & (SSE_DO_DIAG | SSE_DO_RVB | SSE_DO_LOOP)) || (split && !(A.domask & SSE_DO_RVB))) {
-        lc.passes = SSE_PASSES_OFFDIAG;
-        plan_offdiag();
+    // launches without a diagonal or RVB pass use the kernel that leaves that code out
+    const bool loop_only = (m & (SSE_DO_DIAG | SSE_DO_RVB | SSE_DO_CLUSTER | SSE_DO_FREE)) == 0 && (m & SSE_DO_LOOP);
+    if (rvb_alone(m)) o.cfg.passes = SSE_PASSES_RVB;   // the RVB sweep alone: its own kernel (no scratch spills, unlike the all-passes kernel)
+    else if (loop_only) o.cfg.passes = SSE_PASSES_DIAG; // a lone directed loop uses the small launch geometry too
+    else if (!(m & (SSE_DO_DIAG | SSE_DO_RVB | SSE_DO_LOOP)) || (c.split && !(m & SSE_DO_RVB))) o.cfg.passes = SSE_PASSES_OFFDIAG;
+    if (o.cfg.passes != SSE_PASSES_OFFDIAG) return o;
+    // The off-diagonal kernel is latency-bound and small in registers: more waves per replica help as long as the
+    // per-wave scan tables and the union-find of W*N + (transverse ops) ids still fit in LDS.  Decided from the largest
+    // transverse-op count seen so far, and again every few timesteps of a long call (the count grows while a batch
+    // equilibrates; replicas that outgrow the table only fall back to the slower HBM union-find, never fail).
+    uint32_t Wo = b->W_off ? b->W_off : b->W;
+    bool hbm_uf = false;
+    if (!b->W_off && b->W < 16) {
+        if (plan_lds(b, 16).all_ids_fit) Wo = 16;
+        else if (b->w8_ok && !b->uf_ids_limit && !plan_lds(b, b->W).all_ids_fit) {
+            // the largest replicas need the 32-bit union-find in HBM whatever the geometry: spend the LDS on the scan
+            // tables of 8 waves instead of on a 16-bit parent table that they cannot use (the HBM path is bound by
+            // memory latency: twice the waves, twice the accesses in flight)
+            Wo = 8; hbm_uf = true;
+        }
     }
-    // The cluster (+ free spins + sampling) launch of the headline geometry: the dedicated kernel, then the general one for the
-    // replicas it flagged (ids beyond its LDS union-find, no op, no cut: a handful while a batch equilibrates, none afterwards;
-    // that launch runs in the small diagonal geometry and its workgroups leave at once when their flag is clear).
-    bool lean_now = false;
-    LeanPlan lean{};
-    auto plan_lean_now = [&]() { lean = plan_lean(b); lean_now = lean.ok && (b->K == 4 || b->K == 2) && !b->uf_ids_limit; b->last_lean = lean_now; };
-    plan_lean_now();
-    auto launch_lean = [&](const SweepArgs &a) -> hipError_t {
-        LaunchCfg ll = lc;
-        ll.W = 16; ll.K = b->K;
-        DevBatch dv = b->dev;
-        dv.lds_ufcap = lean.ufcap; give_lds(ll, dv, lean.words);
-        SweepArgs al = a;
-        al.defer_flips = b->defer ? 1u : 0u;
-        hipError_t e = launch_cluster(ll, dv, al);
-        if (e != hipSuccess) return e;
-        if (b->defer) b->pending = true;
-        LaunchCfg lf = lc;
-        lf.W = b->W; lf.passes = SSE_PASSES_OFFDIAG;
+    LdsPlan po = plan_lds(b, Wo);
+    if (hbm_uf) { po.ufcap = 0; po.words = general_lds_words(Wo, b->dev, lds_edges(b), false, 0u, 0u) + 64; }
+    *W_chosen = o.cfg.W = Wo; o.ufcap = po.ufcap; o.flipcap = 0u; o.words = po.words;
+    if (is_tg(b) || hbm_uf) {
+        // HBM union-find launch: the LDS behind the fixed regions takes the flip bits of the ids (those the union-find is sized
+        // for; a replica with more ids looks its flips up in HBM as before)
+        const size_t used = lds_bytes_of(po.words) / 4;
+        const size_t want = (uf_ids_wanted(b, Wo) + 31) / 32;
+        const size_t avail = b->lds_total_words > used + 16 ? b->lds_total_words - used - 16 : 0;
+        const size_t fw = want < avail ? want : avail;
+        o.words = used + fw; o.flipcap = (uint32_t)(32 * fw);
+    }
+    return o;
+}
+
+// The RVB sweep as a launch of its own, in one of its three forms.  r: the launch of the fused kernel (SSE_PASSES_RVB).
+static void add_rvb(Plan &P, const isingmc_batch *b, Launch r, bool one_step) {
+    const DevBatch &D = b->dev;
+    r.domask = SSE_DO_RVB;
+    const bool records = !b->rvb_global && b->rvb_split && one_step && D.rvb_prod && D.rvb_prod_cap >= rvb_attempts(b);
+    const size_t main_words = records ? rvb_main_lds_words(b->rvb_main_W, D, lds_edges(b)) : 0;
+    if (b->rvb_global) { // the tables in HBM (sweep_rvb_global.hip): 16 waves, the LDS scratch without the per-variable tables + one small growth area per wave
+        r.kind = L_RVB_GLOBAL; r.ufcap = D.lds_ufcap; r.flipcap = 0u;
+        r.cfg.W = 16; r.cfg.K = 4; r.cfg.passes = SSE_PASSES_RVB_G; r.cfg.mode = b->mode == SSE_MODE_LDS_EDGES ? SSE_MODE_LDS_EDGES : SSE_MODE_GENERAL;
+        r.words = std::min(rvb_global_lds_words(b, 16), b->lds_total_words); // (fewer small growth areas; the large one always fits)
+    } else if (records && lds_bytes_of(main_words) <= b->lds_total_words * 4) { // growth launch + main launch (sse_rvb_split.hip.h)
+        r.kind = L_RVB_GROW; r.cfg.W = 16; r.ufcap = D.lds_ufcap; r.flipcap = 0u;
+        r.words = std::min((size_t)rvb_grow_table_start(D, lds_edges(b)) + D.cap + 16 * 640, b->lds_total_words); // the constant-op table, 16 small growth areas
+        P.l[P.n++] = r;
+        r.kind = L_RVB_MAIN; r.follows = true; r.cfg.W = b->rvb_main_W; r.words = main_words;
+    } else r.kind = L_RVB_FUSED;
+    P.l[P.n++] = r;
+}
+// Cluster / free-spin / sampling passes in launch `L`, or in the dedicated cluster kernel when it takes them: then the general
+// kernel follows for the replicas it flagged (ids beyond its LDS union-find, no op, no cut: a handful while a batch equilibrates,
+// none afterwards; that launch runs in the small diagonal geometry and its workgroups leave at once when their flag is clear).
+static void add_offdiag(Plan &P, const isingmc_batch *b, const LeanPlan &lean, Launch L, uint32_t mask, bool one_step) {
+    L.domask = mask; L.sampled = true;
+    if (lean_takes(b, lean, mask, one_step)) {
+        Launch cl = L;
+        cl.kind = L_CLUSTER; cl.cfg.W = 16; cl.ufcap = lean.ufcap; cl.flipcap = 0u; cl.words = lean.words;
+        P.l[P.n++] = cl;
         const LdsPlan pf = plan_lds(b, b->W);
-        DevBatch df = b->dev;
-        df.lds_ufcap = pf.ufcap; give_lds(lf, df, pf.words);
-        SweepArgs af = a;
-        af.only_flagged = 1u;
-        return launch_dev(lf, df, af);
-    };
-    // RVB sweep: growth launch + main launch where that applies (sse_rvb_split.hip.h), else the fused kernel in geometry `lfused`
-    auto launch_rvb = [&](const LaunchCfg &lfused, const DevBatch &dfused, const SweepArgs &a) -> hipError_t {
-        const uint32_t updates = a.rvb_updates ? a.rvb_updates : (b->dev.N + 1u) / 2u;
-        b->last_rvb_split = false;
-        if (b->rvb_global) { // the tables in HBM (sweep_rvb_global.hip): 16 waves, the LDS scratch without the per-variable tables + one small growth area per wave
-            LaunchCfg lg = lfused;
-            lg.W = 16; lg.K = 4; lg.passes = SSE_PASSES_RVB_G;
-            lg.mode = b->mode == SSE_MODE_LDS_EDGES ? SSE_MODE_LDS_EDGES : SSE_MODE_GENERAL;
-            size_t words = rvb_global_lds_words(b, 16);
-            if (words > b->lds_total_words) words = b->lds_total_words; // (fewer small growth areas; the large one always fits)
-            DevBatch dg = b->dev; give_lds(lg, dg, words);
-            b->last_rvb_global = true;
-            return launch_rvb_global(lg, dg, a);
-        }
-        const size_t pstride = rvb_split_prod_stride(b->dev.Nb);
-        if (b->rvb_split && a.nsteps == 1 && updates && pstride) {
-            if (b->dev.rvb_prod_cap < updates) { // records of a sweep's attempts (grown on demand; no room -> the fused kernel)
-                if (b->dev.rvb_prod) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->dev.rvb_prod); b->dev.rvb_prod = nullptr; b->dev.rvb_prod_cap = 0; }
-                void *q = nullptr;
-                if (hipMalloc(&q, (size_t)b->dev.R * updates * pstride * sizeof(uint32_t)) == hipSuccess) { b->dev.rvb_prod = (uint32_t *)q; b->dev.rvb_prod_cap = updates; b->dev.rvb_prod_stride = (uint32_t)pstride; }
-                else { (void)hipGetLastError(); b->rvb_split = false; } // no room for the records: the fused kernel from now on
-            }
-            const DevBatch &D = b->dev;
-            const size_t main_words = rvb_main_lds_words(b->rvb_main_W, D, lds_edges(b));
-            if (D.rvb_prod && lds_bytes_of(main_words) <= b->lds_total_words * 4) {
-                LaunchCfg lg = lfused;
-                size_t words = (size_t)rvb_grow_table_start(D, lds_edges(b)) + D.cap + 16 * 640; // the constant-op table, 16 small growth areas
-                if (words > b->lds_total_words) words = b->lds_total_words;
-                lg.W = 16; DevBatch dg = D; give_lds(lg, dg, words);
-                hipError_t e = launch_rvb_grow(lg, dg, a);
-                if (e != hipSuccess) return e;
-                LaunchCfg lm = lfused;
-                lm.W = b->rvb_main_W; DevBatch dm = D; give_lds(lm, dm, main_words);
-                b->last_rvb_split = true;
-                return launch_rvb_main(lm, dm, a);
-            }
-        }
-        return launch_dev(lfused, dfused, a);
-    };
-    HIP_TRY(b, hipEventRecord(b->ev0, b->stream));
-    if (!split && rvb_g && !rvb_only) {
-        // whole timesteps in one launch (ISINGMC_CFG_FUSED_LAUNCH) around an RVB sweep with its tables in HBM, which needs a launch of its
-        // own: per step, the passes in front of the sweep, the sweep, the passes behind it (the kernel's order: same epochs, same results)
-        const uint32_t pre = A.domask & (SSE_DO_DIAG | SSE_DO_HEATBATH | SSE_DO_GROW), post = A.domask & ~(pre | SSE_DO_RVB);
-        for (uint64_t done = 0; done < nsteps; ++done) {
-            SweepArgs a1 = A;
-            a1.nsteps = 1; a1.step0 = done; a1.sampling_freq = 0; a1.out_u32 = nullptr;
-            hipError_t e = hipSuccess;
-            if (pre & SSE_DO_DIAG) {
-                a1.domask = pre;
-                if ((e = launch_dev(lc, b->dev, a1)) != hipSuccess) return fail_launch(e);
-                launches++;
-            }
-            a1.domask = SSE_DO_RVB;
-            if ((e = launch_rvb(lc, b->dev, a1)) != hipSuccess) return fail_launch(e);
-            launches++;
-            if (post || (freq && (done + 1) % freq == 0)) {
-                SweepArgs a2 = A;
-                a2.domask = post; a2.nsteps = 1; a2.step0 = done;
-                if ((e = launch_dev(lc, b->dev, a2)) != hipSuccess) return fail_launch(e);
-                launches++;
-            }
-            if (recording && (done + 1) % freq == 0 && (e = record_append(b)) != hipSuccess) return fail_record(e);
-        }
-        b->pass_launches[1] = launches;
-    } else if (!split) {
-        const uint64_t per = b->steps_per_launch ? b->steps_per_launch : nsteps;
-        for (uint64_t done = 0; done < nsteps; done += A.nsteps) {
-            A.step0 = done;
-            A.nsteps = (nsteps - done < per) ? nsteps - done : per;
-            // with a sample record attached a launch ends on the next sampled step, whose state the record takes (same epochs, same results)
-            if (recording && A.nsteps > freq - done % freq) A.nsteps = freq - done % freq;
-            const bool lean_here = lean_now && A.nsteps == 1 && (A.domask & SSE_DO_CLUSTER) && !(A.domask & ~(SSE_DO_CLUSTER | SSE_DO_FREE));
-            const hipError_t e = lean_here ? launch_lean(A) : (rvb_only ? launch_rvb(lc, use_dev_off ? dev_off : b->dev, A) : launch_dev(lc, (use_dev_off || lc.passes == SSE_PASSES_OFFDIAG) ? dev_off : b->dev, A));
-            if (e != hipSuccess) return fail_launch(e);
-            launches++;
-            if (recording && (done + A.nsteps) % freq == 0) { const hipError_t er = record_append(b); if (er != hipSuccess) return fail_record(er); }
-        }
-        b->pass_launches[1] = launches;
+        L.follows = L.only_flagged = true; L.cfg.W = b->W; L.cfg.passes = SSE_PASSES_OFFDIAG;
+        L.ufcap = pf.ufcap; L.flipcap = 0u; L.words = pf.words;
+    }
+    P.l[P.n++] = L;
+}
+
+// The launches of one timestep (of one chunk of timesteps on the fused path), in order.  Reads the batch and the call; changes nothing.
+static Plan plan_step(const isingmc_batch *b, const Call &c) {
+    Plan P{};
+    const uint32_t m = c.A.domask;
+    Launch base{};
+    base.kind = L_SWEEP; base.bucket = B_OTHER; base.ufcap = b->dev.lds_ufcap;
+    base.cfg.W = b->W; base.cfg.K = b->K; base.cfg.mode = b->mode; base.cfg.phase = c.phase; base.cfg.passes = SSE_PASSES_ALL; base.cfg.stream = b->stream;
+    base.words = ((m & SSE_DO_RVB) && b->lds_words_rvb > b->lds_words) ? b->lds_words_rvb : b->lds_words;
+    const Launch off = plan_off(b, c, base, &P.W_off);
+    const LeanPlan lean = plan_lean(b);
+    P.lean = lean_takes(b, lean, SSE_DO_CLUSTER, true);
+    P.replan = c.split && off.cfg.passes == SSE_PASSES_OFFDIAG;
+    if (fused_around_rvb_g(b, c)) {
+        // per step, the passes in front of the sweep, the sweep, the passes behind it (the kernel's order: same epochs, same results),
+        // in the batch's own geometry and the all-passes kernel
+        const uint32_t pre = m & (SSE_DO_DIAG | SSE_DO_HEATBATH | SSE_DO_GROW), post = m & ~(pre | SSE_DO_RVB);
+        if (pre & SSE_DO_DIAG) { P.l[P.n] = off; P.l[P.n++].domask = pre; }
+        add_rvb(P, b, off, true);
+        P.l[P.n] = off; P.l[P.n].domask = post; P.l[P.n++].sampled = true;
+    } else if (!c.split) {
+        if (rvb_alone(m)) { Launch r = off; r.sampled = true; add_rvb(P, b, r, c.chunk == 1); } // (sampled: isingmc_rvb_update's successes)
+        else add_offdiag(P, b, lean, off, m, c.chunk == 1);
     } else {
         // Two launches per timestep: the diagonal pass as its own kernel (twice the occupancy: it needs neither the
         // union-find LDS nor the registers of the cluster scan), then everything else.  Same Philox epochs, same
         // results as the fused launch; n / cutoff / chunk counters go through HBM in between (a few KB per replica).
-        LaunchCfg ld = lc;
-        ld.W = b->W;
-        ld.passes = SSE_PASSES_DIAG;
-        const bool use_fast = b->fast_diag && !(A.domask & SSE_DO_HEATBATH);
+        // The first launch takes the diagonal pass and, unless an RVB sweep has to come in between, the directed loop (one
+        // sequential walk: it gains nothing from the wider off-diagonal geometry)
+        const uint32_t diag_bits = SSE_DO_DIAG | SSE_DO_HEATBATH | SSE_DO_GROW | ((m & SSE_DO_RVB) ? 0u : SSE_DO_LOOP);
+        const bool use_fast = b->fast_diag && !(m & SSE_DO_HEATBATH);
+        Launch d = base;
+        d.kind = use_fast ? L_FAST_DIAG : L_SWEEP; d.bucket = B_DIAG; d.domask = m & diag_bits; d.cfg.passes = SSE_PASSES_DIAG;
         // the diagonal launch needs the fixed regions up to the per-wave tables, which it uses as [W][N] bytes
-        size_t diag_words = use_fast ? b->lds_words_fast : b->lds_words_diag;
-        if (is_pm(b) && b->lds_words_pm_diag) { ld.mode = SSE_MODE_PM_LDS_TABLES; diag_words = b->lds_words_pm_diag; } // (the cluster tables stay in HBM)
-        const uint32_t rest = A.domask & ~diag_bits;
-        constexpr size_t MAX_TIMED = 256;
-        const size_t want_ev = 4 * (size_t)(nsteps < MAX_TIMED ? nsteps : MAX_TIMED);
-        while (b->evpool.size() < want_ev) { hipEvent_t ev; HIP_TRY(b, hipEventCreate(&ev)); b->evpool.push_back(ev); }
-        constexpr uint64_t REPLAN_EVERY = 16;
-        for (uint64_t done = 0; done < nsteps; ++done) {
-            if (done && done % REPLAN_EVERY == 0 && lc.passes == SSE_PASSES_OFFDIAG) {
-                int rcq = check_errors(b); // drains the stream, refreshes max_ntrans; an error ends the call here
-                if (rcq) return rcq;
-                plan_offdiag();
-                plan_lean_now();
+        d.words = use_fast ? b->lds_words_fast : b->lds_words_diag;
+        if (is_pm(b) && b->lds_words_pm_diag) { d.cfg.mode = SSE_MODE_PM_LDS_TABLES; d.words = b->lds_words_pm_diag; } // (the cluster tables stay in HBM)
+        P.l[P.n++] = d;
+        uint32_t rest = m & ~diag_bits;
+        Launch second = off;
+        if (split_rvb_own_launch(b, rest)) {
+            // the RVB sweep as its own launch (register budget of its own: the all-passes kernel spills to scratch), then the
+            // cluster / free-spin launch: the plain off-diagonal kernel in the same geometry (with a directed loop — only behind an
+            // RVB_G launch — the kernel of every pass, as without the RVB launch)
+            Launch r = off; r.bucket = B_RVB; r.cfg.passes = SSE_PASSES_RVB; add_rvb(P, b, r, true);
+            rest &= ~SSE_DO_RVB;
+            if (!(rest & SSE_DO_LOOP)) {
+                const LdsPlan po = plan_lds(b, off.cfg.W);
+                second.cfg.passes = SSE_PASSES_OFFDIAG; second.ufcap = po.ufcap; second.flipcap = 0u; second.words = po.words;
             }
-            const bool timed = done < MAX_TIMED;
-            SweepArgs a1 = A;
-            a1.domask = A.domask & diag_bits; a1.nsteps = 1; a1.step0 = done; a1.sampling_freq = 0; a1.out_u32 = nullptr;
-            if (b->pending) { // (every step of a run after the first: the cluster update of the step before left flip bytes)
-                if (use_fast && b->defer) { a1.defer_flips = 1u; b->pending = false; }
-                else { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
-            }
-            if (timed) HIP_TRY(b, hipEventRecord(b->evpool[4 * done], b->stream));
-            DevBatch dd = b->dev; give_lds(ld, dd, diag_words);
-            hipError_t e = use_fast ? launch_sweep_fast(ld, dd, a1) : launch_dev(ld, dd, a1);
-            if (e != hipSuccess) return fail_launch(e);
-            launches++; b->pass_launches[0]++;
-            if (timed) HIP_TRY(b, hipEventRecord(b->evpool[4 * done + 1], b->stream));
-            const bool sample = freq && (done + 1) % freq == 0;
-            uint32_t rest2 = rest;
-            if ((rest & SSE_DO_RVB) && (!(rest & SSE_DO_LOOP) || b->rvb_global)) {
-                // the RVB sweep as its own launch (register budget of its own: the all-passes kernel spills to scratch), then the
-                // cluster / free-spin launch in its usual geometry
-                SweepArgs ar = A;
-                ar.domask = SSE_DO_RVB; ar.nsteps = 1; ar.step0 = done; ar.sampling_freq = 0; ar.out_u32 = nullptr;
-                LaunchCfg lr = lc;
-                lr.passes = SSE_PASSES_RVB;
-                e = launch_rvb(lr, use_dev_off ? dev_off : b->dev, ar);
-                if (e != hipSuccess) return fail_launch(e);
-                launches++; b->pass_launches[1]++; b->pass_launches[2]++;
-                rest2 = rest & ~SSE_DO_RVB;
-            }
-            if (timed) HIP_TRY(b, hipEventRecord(b->evpool[4 * done + 2], b->stream)); // (= the event above when no RVB sweep ran)
-            if (rest2 || sample) {
-                SweepArgs a2 = A;
-                a2.domask = rest2; a2.nsteps = 1; a2.step0 = done;
-                if (rest2 != rest && !(rest2 & SSE_DO_LOOP)) { // behind an RVB launch: the plain off-diagonal kernel and geometry
-                    // (with a directed loop — only behind an RVB_G launch — the kernel of every pass below, as without the RVB launch)
-                    LaunchCfg lo = lc;
-                    lo.passes = SSE_PASSES_OFFDIAG;
-                    const LdsPlan po = plan_lds(b, lc.W);
-                    DevBatch dv = use_dev_off ? dev_off : b->dev;
-                    dv.lds_ufcap = po.ufcap; dv.lds_flipcap = 0u; give_lds(lo, dv, po.words);
-                    if (lean_now && (rest2 & SSE_DO_CLUSTER) && !(rest2 & ~(SSE_DO_CLUSTER | SSE_DO_FREE))) e = launch_lean(a2);
-                    else e = launch_dev(lo, dv, a2);
-                } else if (lean_now && (rest2 & SSE_DO_CLUSTER) && !(rest2 & ~(SSE_DO_CLUSTER | SSE_DO_FREE))) {
-                    e = launch_lean(a2);
-                } else
-                e = launch_dev(lc, (use_dev_off || lc.passes == SSE_PASSES_OFFDIAG) ? dev_off : b->dev, a2);
-                if (e != hipSuccess) return fail_launch(e);
-                launches++; b->pass_launches[1]++;
-            }
-            if (timed) { HIP_TRY(b, hipEventRecord(b->evpool[4 * done + 3], b->stream)); timed_steps++; }
-            if (recording && sample && (e = record_append(b)) != hipSuccess) return fail_record(e);
         }
+        add_offdiag(P, b, lean, second, rest, true);
+    }
+    return P;
+}
+
+static void report_plan(isingmc_batch *b, const Plan &P) { b->last_lean = P.lean; if (P.W_off) b->last_W_off = P.W_off; }
+static hipError_t launch_sweep(const LaunchCfg &c, const DevBatch &dev, const SweepArgs &a) {
+    return c.W == 1 ? launch_sweep_w1(c, dev, a) : c.W == 4 ? launch_sweep_w4(c, dev, a) : c.W == 6 ? launch_sweep_w6(c, dev, a) :
+           c.W == 8 ? launch_sweep_w8(c, dev, a) : c.W == 16 ? launch_sweep_w16(c, dev, a) : hipErrorInvalidValue;
+}
+// Launch L for `steps` timesteps from step0: the one place where a launch's DevBatch and SweepArgs are made
+static hipError_t issue(isingmc_batch *b, const Call &c, const Launch &L, uint64_t step0, uint64_t steps) {
+    LaunchCfg cfg = L.cfg; DevBatch d = b->dev;
+    d.lds_ufcap = L.ufcap; d.lds_flipcap = L.flipcap; give_lds(cfg, d, L.words);
+    SweepArgs a = c.A;
+    a.domask = L.domask; a.nsteps = steps; a.step0 = step0; a.only_flagged = L.only_flagged ? 1u : 0u;
+    if (!L.sampled) { a.sampling_freq = 0; a.out_u32 = nullptr; }
+    switch (L.kind) {
+    case L_SWEEP: return launch_sweep(cfg, d, a);
+    case L_FAST_DIAG: // (every step of a run after the first: the cluster update of the step before left flip bytes)
+        if (b->pending && b->defer) { a.defer_flips = 1u; b->pending = false; }
+        return launch_sweep_fast(cfg, d, a);
+    case L_CLUSTER: {
+        a.defer_flips = b->defer ? 1u : 0u;
+        const hipError_t e = launch_cluster(cfg, d, a);
+        if (e == hipSuccess && b->defer) b->pending = true;
+        return e;
+    }
+    case L_RVB_FUSED: b->last_rvb_split = false; return launch_sweep(cfg, d, a);
+    case L_RVB_GROW: b->last_rvb_split = false; return launch_rvb_grow(cfg, d, a);
+    case L_RVB_MAIN: b->last_rvb_split = true; return launch_rvb_main(cfg, d, a);
+    case L_RVB_GLOBAL: b->last_rvb_split = false; b->last_rvb_global = true; return launch_rvb_global(cfg, d, a);
+    }
+    return hipErrorInvalidValue;
+}
+
+static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t freq, uint32_t domask, double prob, uint32_t *out_host) {
+    if (!b) return ISINGMC_EINVAL;
+    Call c{};
+    int rc = prepare(b, beta, nsteps, freq, domask, prob, out_host, c);
+    if (rc) return rc;
+    Plan P = plan_step(b, c); report_plan(b, P);
+    HIP_TRY(b, hipEventRecord(b->ev0, b->stream));
+    size_t timed_steps = 0;
+    for (uint64_t done = 0, len = 0; done < nsteps; done += len) {
+        if (P.replan && done && done % REPLAN_EVERY == 0) {
+            if ((rc = check_errors(b))) return rc; // drains the stream, refreshes max_ntrans; an error ends the call here
+            P = plan_step(b, c); report_plan(b, P);
+        }
+        len = std::min(c.chunk, nsteps - done);
+        // with a sample record attached a launch ends on the next sampled step, whose state the record takes (same epochs, same results)
+        if (c.recording && len > freq - done % freq) len = freq - done % freq;
+        const bool sample = freq && (done + len) % freq == 0;
+        // flip bytes left by the cluster update of the step before: the trimmed diagonal kernel applies them, any other needs them applied
+        if (b->pending && c.split && !(P.l[0].kind == L_FAST_DIAG && b->defer)) { rc = ensure_materialized(b); if (rc) return rc; }
+        // events of a timed step: [0] in front of the diagonal launch, [1] behind it, [2] behind the RVB sweep (= [1] without one), [3] at the end
+        hipEvent_t *ev = (c.split && done < MAX_TIMED) ? &b->evpool[4 * done] : nullptr;
+        uint32_t stage = 0;
+        for (uint32_t i = 0; i < P.n; ++i) {
+            const Launch &L = P.l[i];
+            if (!L.domask && !sample) continue; // nothing to run behind the other launches and nothing to sample
+            constexpr uint32_t events_before[3] = {1u, 3u, 2u}; // by bucket
+            if (ev) while (stage < events_before[L.bucket]) HIP_TRY(b, hipEventRecord(ev[stage++], b->stream));
+            const hipError_t e = issue(b, c, L, done, len);
+            if (e != hipSuccess) { b->err = std::string("sweep launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+            if (L.follows) continue;
+            b->pass_launches[L.bucket]++; if (L.bucket == B_RVB) b->pass_launches[B_OTHER]++;
+        }
+        if (ev) { while (stage < 4) HIP_TRY(b, hipEventRecord(ev[stage++], b->stream)); timed_steps++; }
+        const hipError_t er = c.recording && sample ? record_append(b) : hipSuccess;
+        if (er != hipSuccess) { b->err = std::string("sample record: ") + hipGetErrorString(er); return ISINGMC_ENODEVICE; }
     }
     HIP_TRY(b, hipEventRecord(b->ev1, b->stream));
-    int rc = check_errors(b);
+    rc = check_errors(b);
+    // kernel time of the call and of its buckets: the events of the timed steps, scaled up to the whole run; all of it under B_OTHER when not split
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) { b->last_ms = ms; b->last_launches = launches; }
-    if (!split) b->pass_ms[1] = b->last_ms;
+    if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) { b->last_ms = ms; b->last_launches = b->pass_launches[B_DIAG] + b->pass_launches[B_OTHER]; }
+    if (!c.split) b->pass_ms[B_OTHER] = b->last_ms;
     for (size_t i = 0; i < timed_steps; ++i) {
         float t = 0.f;
-        if (hipEventElapsedTime(&t, b->evpool[4 * i], b->evpool[4 * i + 1]) == hipSuccess) b->pass_ms[0] += t;
-        if (hipEventElapsedTime(&t, b->evpool[4 * i + 1], b->evpool[4 * i + 3]) == hipSuccess) b->pass_ms[1] += t;
-        if (hipEventElapsedTime(&t, b->evpool[4 * i + 1], b->evpool[4 * i + 2]) == hipSuccess) b->pass_ms[2] += t;
+        if (hipEventElapsedTime(&t, b->evpool[4 * i], b->evpool[4 * i + 1]) == hipSuccess) b->pass_ms[B_DIAG] += t;
+        if (hipEventElapsedTime(&t, b->evpool[4 * i + 1], b->evpool[4 * i + 3]) == hipSuccess) b->pass_ms[B_OTHER] += t;
+        if (hipEventElapsedTime(&t, b->evpool[4 * i + 1], b->evpool[4 * i + 2]) == hipSuccess) b->pass_ms[B_RVB] += t;
     }
-    if (split && timed_steps && timed_steps < nsteps) { // scale the sampled steps up to the whole run
-        const float f = (float)nsteps / (float)timed_steps;
-        b->pass_ms[0] *= f; b->pass_ms[1] *= f; b->pass_ms[2] *= f;
-    }
+    const float scale = timed_steps && timed_steps < nsteps ? (float)nsteps / (float)timed_steps : 1.f;
+    for (float &t : b->pass_ms) t *= scale;
     if (rc) return rc;
     if (out_host) HIP_TRY(b, hipMemcpy(out_host, b->d_out, sizeof(uint32_t) * b->dev.R, hipMemcpyDeviceToHost));
     return ISINGMC_OK;

@@ -350,6 +350,24 @@ int isingmc_plan_geometry(uint32_t capacity, uint32_t W, uint32_t K, uint32_t Wm
  * the u16 root list), o_frozen, o_froot, o_parent; dynamic LDS words of the launch; 1 if the replica is the kernel's case (else
  * it is left to the general kernel); entries of the root list}.  Exposed so that the layout can be asserted on a CPU box. */
 int isingmc_plan_cluster_lds(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t has_long, uint32_t ufcap, uint32_t S, uint32_t out[13]);
+/* Host-only: every launch geometry and mode isingmc_create chooses for cfg on a device whose workgroups have lds_bytes of LDS, by the
+ * function create itself calls; or the code and message (isingmc_last_error(NULL)) create would refuse cfg with once it has found a
+ * device.  No device is looked for and nothing is allocated.  LDS sizes are in 32-bit words.
+ *   out[0]  W waves per replica            out[1]  K slots per lane             out[2]  mode (0 general bond table, 1 compact edge
+ *   table in LDS, 2 per-variable tables in HBM, 4 the same with the +-J decode)
+ *   out[3]  waves of off-diagonal launches (0 = decided per launch)             out[4]  Wmax, most waves of any launch
+ *   out[5]  1 if the 8-wave geometry without an LDS union-find is allowed       out[6..8]  chunk size, chunks, row stride
+ *   (isingmc_plan_geometry)                out[9]  +-J decode: sign words per bond-table row
+ *   out[10] +-J decode: LDS of the diagonal launch with its spin bytes in LDS (0 = they stay in HBM)
+ *   out[11] LDS of the general diagonal launch                                  out[12] LDS of the trimmed diagonal kernel
+ *   out[13] 1 = the trimmed diagonal kernel runs        out[14] 1 = the dedicated cluster kernel may run
+ *   out[15] 1 = its flips are deferred to the next diagonal launch              out[16] LDS of a general launch with an RVB sweep
+ *   out[17] 1 = RVB sweeps keep their tables in HBM      out[18] 1 = RVB sweeps run as growth + main launch
+ *   out[19] waves of that main launch      out[20] bytes per replica of the per-variable tables in HBM (0 = in LDS)
+ *   out[21], out[22] words per replica of the union-find scratch in HBM (low, high half)
+ *   out[23] LDS of the general launch and out[24] ids of its LDS union-find, both before any sweep has run
+ *   out[25] state words per replica        out[26] bonds                        out[27..31] 0 */
+int isingmc_plan_batch(const isingmc_config *cfg, uint32_t lds_bytes, uint32_t out[32]);
 
 #ifdef __cplusplus
 }

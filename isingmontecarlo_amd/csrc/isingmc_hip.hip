@@ -16,37 +16,55 @@ using namespace sse;
 
 static thread_local std::string g_create_error;
 
-struct isingmc_batch {
-    DevBatch dev{};
+// The launch geometry and modes a batch runs with: the part of plan_batch()'s choice that is read after isingmc_create.  Later calls
+// only re-size lds_words (size_lds) and may give up rvb_split (prepare()).
+struct BatchGeometry {
     uint32_t W = 8, K = 4, mode = SSE_MODE_GENERAL; // mode: SSE_MODE_* (bond decode / where the per-variable tables live)
     uint32_t W_off = 0;                 // waves per replica of the off-diagonal launches; 0 = decide per launch (16 when its tables fit in LDS)
+    bool w8_ok = false;                 // an 8-wave off-diagonal geometry without LDS union-find fits (and the row stride allows it)
+    size_t lds_words_pm_diag = 0;       // +-J decode: LDS of the diagonal launch with its per-wave spin bytes in LDS (0 = they do not fit: mode 4 there too)
+    size_t lds_words_diag = 0, lds_words_fast = 0; // LDS words of the diagonal launch: general kernel, trimmed kernel
+    bool fast_diag = false;             // the diagonal-pass launch uses sse_fast.hip.h (headline geometry: LDS edge tables, 4 waves, N <= 4096)
+    bool lean_cluster = false;          // cluster (+ free spins + sampling) launches use sse_cluster.hip.h when their ids fit its LDS union-find
+    bool defer = false;                 // ... leaving its flips as one byte per slot for the next (trimmed) diagonal launch to apply
+    size_t lds_words_rvb = 0;           // LDS words of a general launch that runs an RVB sweep
+    bool rvb_global = false;            // ISINGMC_CFG_RVB_GLOBAL_TABLES: every RVB sweep is a launch of its own with the tables in HBM (SSE_PASSES_RVB_G)
+    bool rvb_split = false;             // RVB sweeps run as a growth launch + a main launch (sse_rvb_split.hip.h) instead of the fused kernel
+    uint32_t rvb_main_W = 4;            // waves per replica of that main launch
+    size_t lds_words = 0;               // LDS words of the general launch (its union-find ids: DevBatch::lds_ufcap)
+    bool fused_launch = false;          // ISINGMC_CFG_FUSED_LAUNCH: whole timesteps in one kernel (no diagonal-only launches)
+    size_t lds_total_words = 0;         // all of a workgroup's LDS
+    uint32_t uf_ids_limit = 0;          // the caller's test limit on the ids of the LDS union-find
+};
+// All that plan_batch() chooses (isingmc_plan_batch reports it): the geometry, and what isingmc_create sizes its allocations by or
+// hands to the DevBatch, which owns those values from then on
+struct BatchPlan : BatchGeometry {
+    uint32_t Wmax = 0;                  // most waves any launch may use: sizes the row stride, the HBM tables and the union-find scratch
+    uint32_t CH = 0, nchunks = 0, stride = 0; // isingmc_plan_geometry(cap, W, K, Wmax)
+    uint32_t pm_words = 0;              // +-J decode: sign words per bond-table row (0 = another decode)
+    uint32_t tbl_stride = 0;            // bytes per replica of the per-variable tables in HBM (0 = they live in LDS)
+    size_t ufstride = 0;                // words per replica of the union-find scratch in HBM: Wmax N + cap ids and two bit arrays over them
+    uint32_t lds_ufcap = 0;             // ids of the LDS union-find of the first general launch
+};
+
+struct isingmc_batch : BatchGeometry {
+    DevBatch dev{};
     uint32_t last_W_off = 0;
     uint64_t steps_per_launch = 0;
     uint32_t acc_rows = 0;
     uint32_t rvb_updates = 0;
-    bool w8_ok = false;                 // an 8-wave off-diagonal geometry without LDS union-find fits (and the row stride allows it)
     uint32_t *d_acc_row = nullptr;
-    size_t lds_words = 0, lds_words_rvb = 0, lds_words_diag = 0, lds_total_words = 0; // LDS words: general, RVB and diagonal launches; all of LDS
-    uint32_t max_ntrans = 0, uf_ids_limit = 0;
+    uint32_t max_ntrans = 0;
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.f;
     uint32_t last_launches = 0;
-    bool fast_diag = false;             // the diagonal-pass launch uses sse_fast.hip.h (headline geometry: LDS edge tables, 4 waves, N <= 4096)
-    size_t lds_words_fast = 0;
-    bool fused_launch = false;          // ISINGMC_CFG_FUSED_LAUNCH: whole timesteps in one kernel (no diagonal-only launches)
-    size_t lds_words_pm_diag = 0;       // +-J decode: LDS of the diagonal launch with its per-wave spin bytes in LDS (0 = they do not fit: mode 4 there too)
-    bool lean_cluster = false;          // cluster (+ free spins + sampling) launches use sse_cluster.hip.h when their ids fit its LDS union-find
-    bool last_lean = false;             // ... and the last such launch did
-    bool defer = false;                 // ... leaving its flips as one byte per slot for the next (trimmed) diagonal launch to apply
+    bool last_lean = false;             // the last cluster launch used the dedicated kernel
     bool pending = false;               // some replicas' strings in HBM may still wait for their flip bytes (DevBatch::pend says which)
     const double *beta_dev = nullptr;   // isingmc_pt_timesteps: per-replica betas already on the device (used when the caller passes none)
-    bool rvb_split = false;             // RVB sweeps run as a growth launch + a main launch (sse_rvb_split.hip.h) instead of the fused kernel
-    uint32_t rvb_main_W = 4;            // waves per replica of that main launch
-    bool last_rvb_split = false;        // ... and the last RVB sweep did
-    bool rvb_global = false;            // ISINGMC_CFG_RVB_GLOBAL_TABLES: every RVB sweep is a launch of its own with the tables in HBM (SSE_PASSES_RVB_G)
-    bool last_rvb_global = false;       // ... and the last RVB sweep was one
+    bool last_rvb_split = false;        // the last RVB sweep ran as a growth launch + a main launch
+    bool last_rvb_global = false;       // ... as a launch with its tables in HBM
     std::vector<hipEvent_t> evpool;     // per-launch events of the split path (bounded, see run())
     float pass_ms[3] = {0.f, 0.f, 0.f}; // [0] diagonal-only launches, [1] all other launches of the last run, [2] of those: the RVB-sweep launches
     uint32_t pass_launches[3] = {0, 0, 0};
@@ -243,16 +261,28 @@ static int ensure_materialized(isingmc_batch *b) {
     return ISINGMC_OK;
 }
 
-static bool is_tg(const isingmc_batch *b) { return b->mode == SSE_MODE_GLOBAL_TABLES || b->mode == SSE_MODE_PM_GLOBAL_TABLES; }
-static bool is_pm(const isingmc_batch *b) { return b->mode == SSE_MODE_PM_GLOBAL_TABLES; }
-static uint32_t lds_edges(const isingmc_batch *b) { return b->mode == SSE_MODE_LDS_EDGES ? b->dev.E : 0u; } // compact edge table words in LDS
+static bool is_tg(uint32_t mode) { return mode == SSE_MODE_GLOBAL_TABLES || mode == SSE_MODE_PM_GLOBAL_TABLES; }
+static bool is_pm(uint32_t mode) { return mode == SSE_MODE_PM_GLOBAL_TABLES; }
+static bool is_tg(const isingmc_batch *b) { return is_tg(b->mode); }
+static bool is_pm(const isingmc_batch *b) { return is_pm(b->mode); }
+static uint32_t lds_edges(uint32_t mode, const DevBatch &D) { return mode == SSE_MODE_LDS_EDGES ? D.E : 0u; } // compact edge table words in LDS
+static uint32_t lds_edges(const isingmc_batch *b) { return lds_edges(b->mode, b->dev); }
+// the wave counts per replica that the kernels are built for (sweep_w*.hip), and a count's place among them (-1: not one)
+constexpr uint32_t WAVES[5] = {1, 4, 6, 8, 16};
+static int wave_index(uint32_t W) { for (int i = 0; i < 5; ++i) if (WAVES[i] == W) return i; return -1; }
 
 // Dynamic LDS of every kind of launch, read off the carve its kernel lays its LDS out with (the carves are the only statement of
 // the layouts; what the host adds on top — constant-op tables, growth areas, headroom — is policy and stays at the call sites).
-// f(L) on a fresh Lds<W> for the runtime wave count W (1, 4, 6, 8 or 16)
+// f(L) on a fresh Lds<W> for the runtime wave count W (one of WAVES)
 template <class F>
 static size_t with_lds(uint32_t W, F &&f) {
-    return W == 1 ? f(Lds<1>{}) : W == 4 ? f(Lds<4>{}) : W == 6 ? f(Lds<6>{}) : W == 8 ? f(Lds<8>{}) : f(Lds<16>{});
+    switch (wave_index(W)) {
+    case 0: return f(Lds<WAVES[0]>{});
+    case 1: return f(Lds<WAVES[1]>{});
+    case 2: return f(Lds<WAVES[2]>{});
+    case 3: return f(Lds<WAVES[3]>{});
+    default: return f(Lds<WAVES[4]>{});
+    }
 }
 // general / off-diagonal launch at W waves whose LDS union-find holds ufcap ids (tg: per-variable tables in HBM; pm_words: +-J signs)
 static size_t general_lds_words(uint32_t W, const DevBatch &D, uint32_t ledges, bool tg, uint32_t pm_words, uint32_t ufcap) {
@@ -293,25 +323,31 @@ static void give_lds(LaunchCfg &c, DevBatch &d, size_t words) {
 // stays small enough for two workgroups per CU whenever the model allows it.  Replicas that outgrow it use the HBM
 // union-find for that sweep and the host enlarges the table before the next launch.
 struct LdsPlan { uint32_t W, ufcap; size_t words; bool all_ids_fit; };
+// What such a plan is made from: the model's shape (D: N, E, cap, nwords, has_long, pm_words), the batch's mode, all of LDS, the
+// test limit on the ids and the largest transverse-op count seen so far
+struct LdsNeeds { const DevBatch &D; uint32_t mode; size_t total_words; uint32_t uf_ids_limit, max_ntrans; };
+static LdsNeeds lds_needs(const isingmc_batch *b) { return {b->dev, b->mode, b->lds_total_words, b->uf_ids_limit, b->max_ntrans}; }
 // ids that the union-find of a launch at W waves is sized for: W per variable, the transverse ops seen so far, headroom
-static size_t uf_ids_wanted(const isingmc_batch *b, uint32_t W) { return (size_t)W * b->dev.N + b->max_ntrans + b->max_ntrans / 16 + 384; }
-static LdsPlan plan_lds(const isingmc_batch *b, uint32_t W) {
-    const DevBatch &D = b->dev;
-    auto words = [&](size_t ids) { return general_lds_words(W, D, lds_edges(b), is_tg(b), is_pm(b) ? D.pm_words : 0u, (uint32_t)ids); };
+static size_t uf_ids_wanted(const LdsNeeds &n, uint32_t W) { return (size_t)W * n.D.N + n.max_ntrans + n.max_ntrans / 16 + 384; }
+static LdsPlan plan_lds(const LdsNeeds &n, uint32_t W) {
+    const DevBatch &D = n.D;
+    const bool tg = is_tg(n.mode);
+    auto words = [&](size_t ids) { return general_lds_words(W, D, lds_edges(n.mode, D), tg, is_pm(n.mode) ? D.pm_words : 0u, (uint32_t)ids); };
     const size_t ids_max = (size_t)W * D.N + D.cap;
-    const size_t want = uf_ids_wanted(b, W);
+    const size_t want = uf_ids_wanted(n, W);
     size_t ids = want;
-    if (b->uf_ids_limit) ids = b->uf_ids_limit;
-    if (is_tg(b)) ids = 0; // tables in HBM: the union-find lives there too
+    if (n.uf_ids_limit) ids = n.uf_ids_limit;
+    if (tg) ids = 0; // tables in HBM: the union-find lives there too
     if (ids > 65535) ids = 65535;
     if (ids > ids_max) ids = ids_max;
-    while (ids > 0 && words(ids) > b->lds_total_words) ids -= (ids > 64 ? 64 : ids);
+    while (ids > 0 && words(ids) > n.total_words) ids -= (ids > 64 ? 64 : ids);
     LdsPlan p;
     p.W = W; p.ufcap = (uint32_t)ids;
     p.words = words(ids);
-    p.all_ids_fit = !is_tg(b) && words(0) + 64 <= b->lds_total_words && ids >= (want < ids_max ? want : ids_max) && !b->uf_ids_limit;
+    p.all_ids_fit = !tg && words(0) + 64 <= n.total_words && ids >= (want < ids_max ? want : ids_max) && !n.uf_ids_limit;
     return p;
 }
+static LdsPlan plan_lds(const isingmc_batch *b, uint32_t W) { return plan_lds(lds_needs(b), W); }
 static void size_lds(isingmc_batch *b) {
     const LdsPlan p = plan_lds(b, b->W);
     b->dev.lds_ufcap = p.ufcap;
@@ -328,7 +364,7 @@ static LeanPlan plan_lean(const isingmc_batch *b) {
     LeanPlan p{false, 0u, 0};
     if (!b->lean_cluster) return p;
     const size_t ids_max = (size_t)16 * D.N + D.cap;
-    size_t want = uf_ids_wanted(b, 16);
+    size_t want = uf_ids_wanted(lds_needs(b), 16);
     if (want > ids_max) want = ids_max;
     if (want > 65535 || !cluster_ids_fit(D.N, (uint32_t)want - 1u, (uint32_t)want)) return p;
     const size_t words = cluster_lds_words(D.N, D.nwords, D.Nb, (uint32_t)want, D.has_long != 0u);
@@ -534,7 +570,7 @@ static Launch plan_off(const isingmc_batch *b, const Call &c, const Launch &base
         // HBM union-find launch: the LDS behind the fixed regions takes the flip bits of the ids (those the union-find is sized
         // for; a replica with more ids looks its flips up in HBM as before)
         const size_t used = lds_bytes_of(po.words) / 4;
-        const size_t want = (uf_ids_wanted(b, Wo) + 31) / 32;
+        const size_t want = (uf_ids_wanted(lds_needs(b), Wo) + 31) / 32;
         const size_t avail = b->lds_total_words > used + 16 ? b->lds_total_words - used - 16 : 0;
         const size_t fw = want < avail ? want : avail;
         o.words = used + fw; o.flipcap = (uint32_t)(32 * fw);
@@ -632,8 +668,9 @@ static Plan plan_step(const isingmc_batch *b, const Call &c) {
 
 static void report_plan(isingmc_batch *b, const Plan &P) { b->last_lean = P.lean; if (P.W_off) b->last_W_off = P.W_off; }
 static hipError_t launch_sweep(const LaunchCfg &c, const DevBatch &dev, const SweepArgs &a) {
-    return c.W == 1 ? launch_sweep_w1(c, dev, a) : c.W == 4 ? launch_sweep_w4(c, dev, a) : c.W == 6 ? launch_sweep_w6(c, dev, a) :
-           c.W == 8 ? launch_sweep_w8(c, dev, a) : c.W == 16 ? launch_sweep_w16(c, dev, a) : hipErrorInvalidValue;
+    static constexpr decltype(&launch_sweep_w1) of_waves[5] = {launch_sweep_w1, launch_sweep_w4, launch_sweep_w6, launch_sweep_w8, launch_sweep_w16}; // (by wave_index)
+    const int i = wave_index(c.W);
+    return i < 0 ? hipErrorInvalidValue : of_waves[i](c, dev, a);
 }
 // Launch L for `steps` timesteps from step0: the one place where a launch's DevBatch and SweepArgs are made
 static hipError_t issue(isingmc_batch *b, const Call &c, const Launch &L, uint64_t step0, uint64_t steps) {
@@ -716,6 +753,371 @@ static int run(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32_t f
     return ISINGMC_OK;
 }
 
+// ---- isingmc_create in four parts: check_config, build_tables, plan_batch, allocate_and_upload -------------------------------
+// Everything up to the plan reads the config alone and touches no device, so that isingmc_plan_batch can run it on any host.
+static int refuse(int rc, const char *why) { g_create_error = why; return rc; }
+static bool per_replica_J(const isingmc_config *cfg) { return (cfg->flags & ISINGMC_CFG_PER_REPLICA_J) != 0; }
+static double gamma_of(const isingmc_config *cfg, uint32_t row) { return cfg->transverse_r ? cfg->transverse_r[row] : cfg->transverse; }
+static double hfield_of(const isingmc_config *cfg, uint32_t row) { return cfg->longitudinal_r ? cfg->longitudinal_r[row] : cfg->longitudinal; }
+static bool has_longitudinal(const isingmc_config *cfg) { return !cfg->interactions && std::fabs(hfield_of(cfg, 0)) > DBL_EPSILON; } // qmc_ising.rs:230
+
+// The argument checks that isingmc_create makes before it looks for a device (cfg itself is readable: the entry points see to that)
+static int check_config(const isingmc_config *cfg) {
+    const bool generic = cfg->interactions != nullptr;
+    if (generic) {
+        if (cfg->nreplicas == 0 || cfg->nvars == 0 || cfg->ninteractions == 0) return refuse(ISINGMC_EINVAL, "nreplicas, nvars, ninteractions must be > 0");
+        if (per_replica_J(cfg)) return refuse(ISINGMC_EINVAL, "per-replica couplings are not available with generic interactions");
+        for (uint32_t i = 0; i < cfg->ninteractions; ++i) {
+            const isingmc_interaction &it = cfg->interactions[i];
+            if (it.nvars > 2) // qmc_runner.rs:415-680 allows any k; the 32-bit operator word holds two variables
+                return refuse(ISINGMC_ENOTIMPL, "interactions on more than two variables are not implemented (operator word = 2 in + 2 out bits)");
+            if ((it.nvars != 1 && it.nvars != 2) || !it.mat || it.vars[0] >= cfg->nvars || (it.nvars == 2 && (it.vars[1] >= cfg->nvars || it.vars[1] == it.vars[0])))
+                return refuse(ISINGMC_EINVAL, "interaction must act on 1 or 2 distinct variables inside the model and carry a matrix");
+            for (uint32_t k = 0; k < (it.diagonal_only ? (1u << it.nvars) : (1u << (2 * it.nvars))); ++k)
+                if (!(it.mat[k] >= 0.0) || !std::isfinite(it.mat[k])) return refuse(ISINGMC_EINVAL, "interaction matrix entries must be finite and >= 0");
+        }
+    } else if (cfg->nreplicas == 0 || cfg->nvars == 0 || (cfg->nedges != 0 && (!cfg->edges || !cfg->J)))
+        return refuse(ISINGMC_EINVAL, "nreplicas and nvars must be > 0 and edges/J non-null when nedges > 0");
+    if (cfg->capacity == 0) return refuse(ISINGMC_EINVAL, "capacity must be > 0");
+    if (cfg->cutoff0 > cfg->capacity) return refuse(ISINGMC_EINVAL, "cutoff0 exceeds capacity");
+    if (cfg->nvars > SSE_VAR_MASK) return refuse(ISINGMC_EINVAL, "too many variables");
+    if (!generic && !(cfg->transverse >= 0.0)) return refuse(ISINGMC_EINVAL, "transverse field must be >= 0");
+    for (uint32_t e = 0; !generic && e < cfg->nedges; ++e)
+        if (cfg->edges[2 * e] >= cfg->nvars || cfg->edges[2 * e + 1] >= cfg->nvars || cfg->edges[2 * e] == cfg->edges[2 * e + 1])
+            return refuse(ISINGMC_EINVAL, cfg->edges[2 * e] == cfg->edges[2 * e + 1] ? "edge joins a variable to itself (self-loop)" : "edge endpoint out of range");
+    return ISINGMC_OK;
+}
+// The model fields of a DevBatch (its shape and fields; the tables add uniformJ / wJ / wtot, the plan its geometry)
+static DevBatch model_of(const isingmc_config *cfg) {
+    const bool generic = cfg->interactions != nullptr, has_long = has_longitudinal(cfg);
+    DevBatch D{};
+    D.R = cfg->nreplicas; D.N = cfg->nvars; D.E = generic ? 0u : cfg->nedges;
+    D.Nb = generic ? cfg->ninteractions : cfg->nedges + cfg->nvars + (has_long ? cfg->nvars : 0);
+    D.cap = cfg->capacity; D.nwords = (cfg->nvars + 31) / 32;
+    D.seed_lo = (uint32_t)cfg->seed; D.seed_hi = (uint32_t)(cfg->seed >> 32);
+    D.replica_offset = cfg->replica_offset;
+    D.gamma = cfg->transverse; D.wh = 2.0 * std::fabs(cfg->longitudinal); D.hpos = cfg->longitudinal > 0.0 ? 1u : 0u;
+    D.has_long = has_long ? 1u : 0u;
+    D.bond_stride = per_replica_J(cfg) ? D.Nb : 0u;
+    D.rvb_growers = (cfg->flags & ISINGMC_CFG_RVB_SERIAL_GROWTH) ? 0u : 64u;
+    return D;
+}
+
+// The checks behind the device probe that need no plan: fields, bond count, the geometry wishes (plan_batch refuses the rest where it
+// meets them, in the order they always had)
+static int check_config_model(const isingmc_config *cfg) {
+    const bool generic = cfg->interactions != nullptr, perJ = per_replica_J(cfg), has_long = has_longitudinal(cfg);
+    if ((cfg->transverse_r || cfg->longitudinal_r) && (!perJ || generic)) return refuse(ISINGMC_EINVAL, "per-replica fields need ISINGMC_CFG_PER_REPLICA_J (per-replica bond tables)");
+    for (uint32_t r = 0; !generic && r < (perJ ? cfg->nreplicas : 1u); ++r) {
+        if (!(gamma_of(cfg, r) >= 0.0) || !std::isfinite(gamma_of(cfg, r)) || !std::isfinite(hfield_of(cfg, r))) return refuse(ISINGMC_EINVAL, "fields must be finite, transverse field >= 0");
+        if ((std::fabs(hfield_of(cfg, r)) > DBL_EPSILON) != has_long) return refuse(ISINGMC_EINVAL, "longitudinal fields must be all zero or all non-zero within a batch");
+    }
+    if (model_of(cfg).Nb > SSE_MAX_BONDS) return refuse(ISINGMC_EINVAL, "too many bonds");
+    if (wave_index(cfg->waves_per_replica ? cfg->waves_per_replica : 4) < 0) return refuse(ISINGMC_EINVAL, "waves_per_replica must be 1, 4, 6, 8 or 16");
+    const uint32_t K = cfg->slots_per_lane ? cfg->slots_per_lane : 4;
+    if (K != 1 && K != 2 && K != 4) return refuse(ISINGMC_EINVAL, "slots_per_lane must be 1, 2 or 4");
+    return ISINGMC_OK;
+}
+
+// Everything that create uploads, on the host: made from the config alone
+struct Tables {
+    std::vector<BondRec> bonds;          // [nH][Nb], nH = one row, or one per replica (ISINGMC_CFG_PER_REPLICA_J: cfg->J is [R][E])
+    std::vector<double> cum, wtots;      // [nH][Nb] heat-bath cumulative weights; [nH] their totals
+    std::vector<double> offsets;         // [nH] energy offsets (per-replica J only)
+    double offset = 0.0;                 // ... of row 0
+    std::vector<double> mats;            // generic interactions: [Nb][16] in | out<<2
+    bool generic_sym = false;            // ... all of them symmetric under a global spin flip
+    uint32_t uniformJ = 1u; double wJ = 0.0; // one |J| on every edge of every row (the kernels keep 2|J| in a scalar register)
+    std::vector<double> edge_w;          // [E] 2|J| of row 0
+    std::vector<uint32_t> edges_compact; // [E] a | c << 15 | prefers_aligned << 30 (N <= SSE_CE_MAX_VARS, else zeros)
+    std::vector<uint32_t> signs;         // [nH][ceil(E / 32)] bit e = prefers aligned (J < 0): the +-J decode's rows
+    std::vector<uint32_t> adj_start, adj; // [N + 2], [2 E + 1] bonds_for_var (make_classical_bonds, qmc_ising.rs:421-432): edge order
+};
+// bond b = interaction b.  Weights go to mats[b][in | out<<2] (bit 0 = first variable); the reference's index is (out0 out1 in0 in1)
+// with the first variable most significant (Interaction::index_from_state, qmc_runner.rs:666-679).  Kinds only feed the
+// transverse-op counters: a one-variable interaction with four equal entries is a cluster edge (cluster.rs:284-286).
+static void generic_tables(const isingmc_config *cfg, uint32_t Nb, Tables &T) {
+    T.mats.assign((size_t)Nb * 16, 0.0);
+    T.generic_sym = true;
+    double c = 0.0;
+    for (uint32_t i = 0; i < Nb; ++i) {
+        const isingmc_interaction &it = cfg->interactions[i];
+        double *mb = T.mats.data() + (size_t)i * 16;
+        for (uint32_t in = 0; in < (1u << it.nvars); ++in)      // device layout: bit 0 = first variable
+            for (uint32_t out = 0; out < (1u << it.nvars); ++out) {
+                const uint8_t ib[2] = {(uint8_t)(in & 1u), (uint8_t)((in >> 1) & 1u)}, ob[2] = {(uint8_t)(out & 1u), (uint8_t)((out >> 1) & 1u)};
+                (void)isingmc_interaction_at(&it, ib, ob, &mb[in | (out << 2)]);
+            }
+        double maxw = 0.0; // heatbath.rs:130-146 make_bond_weights: largest diagonal element
+        for (uint32_t st = 0; st < (it.nvars == 2 ? 4u : 2u); ++st) maxw = std::max(maxw, mb[st | (st << 2)]);
+        const uint32_t kind = it.nvars == 2 ? SSE_BOND_TWO_SITE
+                              : ((mb[0] == mb[1] && mb[0] == mb[4] && mb[0] == mb[5]) ? SSE_BOND_TRANSVERSE : SSE_BOND_LONGITUDINAL);
+        T.bonds[i].a_info = it.vars[0] | (kind << SSE_INFO_SHIFT);
+        T.bonds[i].c = it.nvars == 2 ? it.vars[1] : SSE_NO_VAR;
+        T.bonds[i].w = maxw;
+        c = (i == 0) ? maxw : maxw + c;
+        T.cum[i] = c;
+        // EVERY weight equals the weight with all spins flipped.  (Not isingmc_interaction_sym_under_ising: like the reference's
+        // Interaction::sym_under_ising, qmc_runner.rs:639-664, that one only compares the entries whose outputs are all 0, and
+        // passes two-variable matrices that break the symmetry elsewhere.)
+        const uint32_t mask = it.nvars == 2 ? 0xFu : 0x5u;
+        for (uint32_t idx = 0; idx < 16; ++idx)
+            if ((idx & ~mask) == 0 && std::fabs(mb[idx] - mb[idx ^ mask]) >= DBL_EPSILON) T.generic_sym = false;
+    }
+    T.wtots[0] = c;
+    T.offset = cfg->energy_offset;
+}
+// Bond-table row hI of an Ising model (qmc_ising.rs:186-205,228-246; weights :863-888; offsets :97-99): edges, transverse bonds,
+// longitudinal bonds when there is a field
+static void ising_row(const isingmc_config *cfg, const DevBatch &D, uint32_t hI, Tables &T) {
+    BondRec *t0 = T.bonds.data() + (size_t)hI * D.Nb;
+    const double *Jh = cfg->J + (size_t)hI * D.E;
+    double off = 0.0;
+    for (uint32_t e = 0; e < D.E; ++e) {
+        const double J = Jh[e];
+        t0[e].a_info = cfg->edges[2 * e] | ((SSE_BOND_TWO_SITE | (J < 0.0 ? SSE_BOND_PREF_BIT : 0u)) << SSE_INFO_SHIFT);
+        t0[e].c = cfg->edges[2 * e + 1];
+        t0[e].w = 2.0 * std::fabs(J);
+        off += std::fabs(J);
+        if (J < 0.0) T.signs[(size_t)hI * ((D.E + 31u) / 32u) + (e >> 5)] |= 1u << (e & 31);
+    }
+    const double gam = gamma_of(cfg, hI), hl = hfield_of(cfg, hI);
+    for (uint32_t v = 0; v < D.N; ++v) {
+        BondRec &t = t0[D.E + v];
+        t.a_info = v | (SSE_BOND_TRANSVERSE << SSE_INFO_SHIFT); t.c = SSE_NO_VAR; t.w = gam;
+    }
+    for (uint32_t v = 0; D.has_long && v < D.N; ++v) {
+        BondRec &t = t0[D.E + D.N + v];
+        t.a_info = v | ((SSE_BOND_LONGITUDINAL | (hl > 0.0 ? SSE_BOND_PREF_BIT : 0u)) << SSE_INFO_SHIFT);
+        t.c = SSE_NO_VAR; t.w = 2.0 * std::fabs(hl);
+    }
+    const double offset = off + (double)D.N * (gam + std::fabs(hl));
+    if (hI == 0) T.offset = offset;
+    if (D.bond_stride) T.offsets[hI] = offset;
+    double c = 0.0;
+    for (uint32_t i = 0; i < D.Nb; ++i) { c = (i == 0) ? t0[0].w : t0[i].w + c; T.cum[(size_t)hI * D.Nb + i] = c; }
+    T.wtots[hI] = c;
+}
+static Tables build_tables(const isingmc_config *cfg, const DevBatch &D) {
+    const bool generic = cfg->interactions != nullptr;
+    const uint32_t nH = D.bond_stride ? D.R : 1u;
+    Tables T;
+    T.bonds.resize((size_t)nH * D.Nb); T.cum.resize((size_t)nH * D.Nb); T.wtots.resize(nH);
+    if (D.bond_stride) T.offsets.resize(nH);
+    T.signs.assign((size_t)nH * ((D.E + 31u) / 32u), 0u);
+    if (generic) generic_tables(cfg, D.Nb, T);
+    else for (uint32_t hI = 0; hI < nH; ++hI) ising_row(cfg, D, hI, T);
+    T.wJ = T.bonds[0].w;
+    for (uint32_t hI = 0; hI < nH && T.uniformJ; ++hI)
+        for (uint32_t e = 0; e < D.E; ++e) if (T.bonds[(size_t)hI * D.Nb + e].w != T.bonds[0].w) { T.uniformJ = 0u; break; }
+    T.edge_w.resize(D.E); T.edges_compact.assign(D.E, 0u);
+    for (uint32_t e = 0; e < D.E; ++e) {
+        const BondRec &t = T.bonds[e];
+        T.edge_w[e] = t.w;
+        if (D.N <= SSE_CE_MAX_VARS)
+            T.edges_compact[e] = (t.a_info & SSE_CE_VAR_MASK) | ((t.c & SSE_CE_VAR_MASK) << 15) | (((t.a_info >> (SSE_INFO_SHIFT + 2)) & 1u) << 30);
+    }
+    std::vector<uint32_t> &as = T.adj_start, &ad = T.adj, fill(D.N, 0u);
+    as.assign(D.N + 2, 0u); ad.resize(2 * (size_t)D.E + 1);
+    for (uint32_t e = 0; e < D.E; ++e) { as[cfg->edges[2 * e] + 1]++; as[cfg->edges[2 * e + 1] + 1]++; }
+    for (uint32_t v = 0; v < D.N; ++v) as[v + 1] += as[v];
+    for (uint32_t e = 0; e < D.E; ++e) {
+        const uint32_t a = cfg->edges[2 * e], c2 = cfg->edges[2 * e + 1];
+        ad[as[a] + fill[a]++] = e;
+        ad[as[c2] + fill[c2]++] = e;
+    }
+    return T;
+}
+
+// Where the per-variable scan tables live when the caller wishes for W_wish waves (0 = no wish) and `ledges` words of compact edge
+// table share the LDS: the wave count to run with, and whether the engine moves the tables to HBM by itself (they do not fit)
+struct TablesHome { uint32_t W; bool hbm; };
+static TablesHome tables_home(const DevBatch &D, uint32_t W_wish, uint32_t ledges, size_t total_words) {
+    auto fixed_lds = [&](uint32_t w) { return general_lds_words(w, D, ledges, false, 0u, 0u); }; // (tables in LDS, no union-find)
+    uint32_t W = W_wish ? W_wish : 4;
+    if (fixed_lds(W) + 4096 <= total_words) return {W, false};
+    if (!W_wish) return {W, true};
+    // explicit geometry: keep the LDS tables if a smaller W makes them fit
+    while (W > 1 && fixed_lds(W) + 4096 > total_words) W = (W == 4) ? 1 : (W == 6 ? 4 : W >> 1);
+    if (fixed_lds(W) + 64 <= total_words) return {W, false};
+    return {W_wish, true};
+}
+// What plan_batch reads: the model's shape (D: N, E, Nb, cap, nwords, has_long, uniformJ), its kind, the caller's flags and geometry
+// wishes, the LDS bytes of a workgroup
+struct PlanInputs {
+    DevBatch D;
+    bool generic, perJ, fields_r; // interaction matrices; per-replica bond tables; per-replica fields among them
+    uint32_t flags, waves_per_replica, slots_per_lane, waves_offdiag, lds_uf_ids_limit, lds_bytes;
+};
+static PlanInputs plan_inputs(const isingmc_config *cfg, const DevBatch &D, uint32_t lds_bytes) {
+    return {D, cfg->interactions != nullptr, per_replica_J(cfg), cfg->transverse_r || cfg->longitudinal_r,
+            cfg->flags, cfg->waves_per_replica, cfg->slots_per_lane, cfg->waves_offdiag, cfg->lds_uf_ids_limit, lds_bytes};
+}
+// Every launch geometry and mode of a batch.  Reads its inputs and nothing else: no device, no batch.  The configs it cannot serve
+// it refuses like the checks do, where their order among them has always been.
+static int plan_batch(const PlanInputs &in, BatchPlan &p) {
+    DevBatch D = in.D; // (gains pm_words below)
+    const uint32_t flags = in.flags;
+    const size_t total_words = (size_t)in.lds_bytes / 4; // all of LDS for one workgroup
+    p = BatchPlan{};
+    p.lds_total_words = total_words; p.uf_ids_limit = in.lds_uf_ids_limit;
+    p.fused_launch = (flags & ISINGMC_CFG_FUSED_LAUNCH) != 0;
+    // default 4 waves per replica: with 16-bit union-find parents the footprint at the headline size stays below half
+    // of the 160 KB LDS, so two workgroups share a CU and overlap each other's barriers (measured best on MI355X)
+    uint32_t W = in.waves_per_replica ? in.waves_per_replica : 4;
+    uint32_t K = in.slots_per_lane ? in.slots_per_lane : 4;
+    // compact edge table staged in LDS when it is small enough (a|c<<15|pref<<30 needs N <= 32768)
+    bool CL = !in.generic && !in.perJ && D.uniformJ && D.N <= SSE_CE_MAX_VARS && (size_t)D.E * 4 <= 48 * 1024 && !(flags & ISINGMC_CFG_NO_LDS_TABLES);
+    // Per-variable scan tables: in LDS while W copies of them fit (with room for a union-find), otherwise in a per-replica
+    // HBM scratch served by L2 / Infinity Cache (MODE 2; ISINGMC_CFG_GLOBAL_TABLES forces it on any model).
+    bool TG = (flags & ISINGMC_CFG_GLOBAL_TABLES) != 0;
+    if (!TG) {
+        TablesHome h = tables_home(D, in.waves_per_replica, CL ? D.E : 0u, total_words);
+        // The tables do not fit next to the compact edge table (a long chain: up to 48 KB of edges): the edge table leaves LDS first
+        // (the general bond table serves the model), and the HBM tables, which need the general bond table, come without it too.
+        if (h.hbm && CL) { CL = false; h = tables_home(D, in.waves_per_replica, 0u, total_words); }
+        W = h.W; TG = h.hbm;
+    }
+    const uint32_t ledges = CL ? D.E : 0u;
+    // (only with the caller's own ISINGMC_CFG_GLOBAL_TABLES)
+    if (TG && CL) return refuse(ISINGMC_EINVAL, "ISINGMC_CFG_GLOBAL_TABLES needs the general bond table: combine it with ISINGMC_CFG_NO_LDS_TABLES");
+    if (TG && K == 2) K = 4;
+    const uint32_t pm_room = TG ? (D.E + 31u) / 32u : 0u; // (room for the +-J decode's signs, decided below)
+    if (general_lds_words(W, D, ledges, TG, pm_room, 0u) + 64 > total_words) return refuse(ISINGMC_ENOTIMPL, "model too large: the spin-state bit arrays alone exceed LDS");
+    // off-diagonal launches may use their own wave count (see plan_off()): explicit, or decided per launch (then up to 16)
+    uint32_t W_off = in.waves_offdiag;
+    // (a check of the wish alone; it stands here, behind the two refusals above, because that has always been its place among them)
+    if (W_off != 0 && wave_index(W_off) < 0) return refuse(ISINGMC_EINVAL, "waves_offdiag must be 0, 1, 4, 6, 8 or 16");
+    if (!W_off && in.waves_per_replica) W_off = W; // an explicit waves_per_replica pins both kinds of launch
+    if (TG) W_off = W;                             // tables in HBM: one geometry for every launch
+    if (W_off && general_lds_words(W_off, D, ledges, TG, 0u, 0u) + 64 > total_words) W_off = W;
+    auto fits_in_lds = [&](uint32_t w) { return !TG && general_lds_words(w, D, ledges, false, 0u, 0u) + 64 <= total_words; };
+    const bool w16_possible = fits_in_lds(16);
+    // (8 waves without an LDS union-find: the geometry of launches whose cluster ids need the 32-bit union-find in HBM anyway)
+    const bool w8_possible = W < 8 && (K == 4 || K == 1) && fits_in_lds(8);
+    p.w8_ok = w8_possible && !W_off;
+    const uint32_t Wmax = W_off ? (W_off > W ? W_off : W) : ((W < 16 && w16_possible) ? 16u : (w8_possible ? 8u : W));
+    p.W = W; p.K = K; p.W_off = W_off; p.Wmax = Wmax;
+    p.mode = TG ? SSE_MODE_GLOBAL_TABLES : (CL ? SSE_MODE_LDS_EDGES : SSE_MODE_GENERAL);
+    // "+-J" decode for large disorder batches (BASELINE configs[4]): every replica its own coupling signs on one graph with uniform
+    // |J|, Gamma, h.  The general decode fetches a 16-byte record per op and pass from a per-replica table of megabytes — one random
+    // HBM sector each time, in a mode that is bound by exactly those; here the variables come from the shared compact edge table
+    // (L2-resident), the sign from 12 KB of LDS.  Default geometry only.
+    if (TG && in.perJ && D.uniformJ && !in.generic && W == 4 && K == 4 && D.N <= SSE_CE_MAX_VARS && !in.fields_r && !(flags & ISINGMC_CFG_NO_PM_DECODE)) {
+        p.mode = SSE_MODE_PM_GLOBAL_TABLES;
+        p.pm_words = D.pm_words = (D.E + 31u) / 32u;
+        // the diagonal launch keeps its per-wave spin bytes in LDS when W * N bytes fit next to the small arrays
+        const size_t words = diag_lds_words(W, D, 0u, false, D.pm_words, true);
+        p.lds_words_pm_diag = (words + 64 <= total_words && !(flags & ISINGMC_CFG_GLOBAL_TABLES)) ? words : 0;
+    }
+    uint32_t geo[4]; // chunk grid and row stride: one function (also exported for the CPU-side bound checks of tests/test_abi_cpu.py)
+    if (isingmc_plan_geometry(D.cap, W, K, Wmax, geo) != ISINGMC_OK) return refuse(ISINGMC_EINVAL, "capacity too large for the row stride");
+    p.CH = geo[0]; p.nchunks = geo[1]; p.stride = geo[2];
+    p.lds_words_diag = diag_lds_words(W, D, ledges, TG, pm_room);
+    p.lds_words_fast = fast_lds_words(D);
+    p.fast_diag = CL && !TG && W == 4 && (K == 4 || K == 2) && D.N <= SSE_FAST_MAX_VARS && !p.fused_launch &&
+                  !(flags & ISINGMC_CFG_NO_FAST_DIAG) && lds_bytes_of(p.lds_words_fast) <= 40 * 1024; // 4 workgroups per CU
+    // the cluster update of that geometry has its own kernel too (16 waves, packed tables; sse_cluster.hip.h)
+    p.lean_cluster = CL && !TG && !in.generic && D.N <= 4095u && !p.fused_launch && !in.waves_offdiag && !in.waves_per_replica &&
+                     !(flags & ISINGMC_CFG_NO_LEAN_CLUSTER);
+    p.defer = p.lean_cluster && p.fast_diag && !(flags & ISINGMC_CFG_NO_DEFERRED_FLIPS);
+    // the RVB pass reuses everything from the scan tables on: launches that run it get enough LDS for its scratch
+    // and constant-op table (other launches keep the smaller footprint, which decides workgroups per CU)
+    p.lds_words_rvb = std::min(rvb_lds_words(W, D, ledges, TG, pm_room), total_words);
+    p.rvb_global = (flags & ISINGMC_CFG_RVB_GLOBAL_TABLES) != 0; // (the two-launch form keeps its tables in LDS: never with this flag)
+    p.rvb_split = !in.generic && !TG && !p.fused_launch && !(flags & ISINGMC_CFG_RVB_FUSED) && !p.rvb_global;
+    // waves of the RVB main launch: as many as keep about 16 waves on a CU (its LDS footprint decides how many replicas share one)
+    const size_t w4 = 4 * (size_t)rvb_main_lds_words(4, D, ledges);
+    const size_t per_cu = w4 ? (size_t)in.lds_bytes / w4 : 0;
+    p.rvb_main_W = per_cu >= 4 ? 4u : (per_cu >= 2 ? 8u : 16u);
+    if (in.waves_per_replica == 4 || in.waves_per_replica == 8 || in.waves_per_replica == 16) p.rvb_main_W = in.waves_per_replica; // an explicit geometry is honoured here too
+    if (TG) p.tbl_stride = (uint32_t)((((size_t)Wmax * D.N * 4 + D.N) + 15) & ~(size_t)15); // 4-byte scan records per (wave, variable)
+    const size_t ids_max = (size_t)Wmax * D.N + D.cap;
+    p.ufstride = ids_max + 2 * ((ids_max + 31) / 32);
+    const LdsPlan first = plan_lds(LdsNeeds{D, p.mode, total_words, p.uf_ids_limit, 0u}, W); // (prepare() sizes again from the ops seen by then)
+    p.lds_words = first.words; p.lds_ufcap = first.ufcap;
+    return ISINGMC_OK;
+}
+// check_config_model, build_tables and plan_batch for a config that passed check_config: what isingmc_create and isingmc_plan_batch share
+static int plan_config(const isingmc_config *cfg, uint32_t lds_bytes, DevBatch &D, Tables &T, BatchPlan &p) {
+    if (const int rc = check_config_model(cfg)) return rc;
+    D = model_of(cfg);
+    T = build_tables(cfg, D);
+    D.uniformJ = T.uniformJ; D.wJ = T.wJ; D.wtot = T.wtots[0];
+    return plan_batch(plan_inputs(cfg, D, lds_bytes), p);
+}
+
+// Apply the plan to the batch, make every allocation and every upload, set the initial state
+#define CREATE_TRY(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
+template <typename T>
+static int copy_up(isingmc_batch *b, T *dst, const T *host, size_t count, const char *what) {
+    if (hipMemcpy(dst, host, sizeof(T) * count, hipMemcpyHostToDevice) == hipSuccess) return ISINGMC_OK;
+    b->err = std::string(what) + " upload failed";
+    return ISINGMC_ENODEVICE;
+}
+// allocate, copy this host array, or fail with "<what> upload failed"
+template <typename T, typename P>
+static int upload(isingmc_batch *b, P &dst, const std::vector<T> &host, const char *what) {
+    T *q = nullptr;
+    CREATE_TRY(dalloc(b, &q, host.size(), false));
+    dst = q;
+    return copy_up(b, q, host.data(), host.size(), what);
+}
+static int allocate_and_upload(isingmc_batch *b, const isingmc_config *cfg, const DevBatch &model, Tables &T, const BatchPlan &plan) {
+    static_cast<BatchGeometry &>(*b) = plan;
+    DevBatch &D = b->dev;
+    D = model;
+    D.CH = plan.CH; D.nchunks = plan.nchunks; D.stride = plan.stride; D.pm_words = plan.pm_words; D.tbl_stride = plan.tbl_stride; D.lds_ufcap = plan.lds_ufcap;
+    b->generic = cfg->interactions != nullptr; b->generic_sym = T.generic_sym;
+    b->per_replica_J = D.bond_stride != 0; b->offset = T.offset; b->offsets = std::move(T.offsets);
+    const size_t R = D.R;
+    CREATE_TRY(dalloc(b, &D.ops, R * D.stride));
+    CREATE_TRY(dalloc(b, &D.state, R * D.nwords));
+    CREATE_TRY(dalloc(b, &D.n, R));
+    CREATE_TRY(dalloc(b, &D.ntrans, R));
+    CREATE_TRY(dalloc(b, &D.cutoff, R));
+    CREATE_TRY(dalloc(b, &D.err, R));
+    CREATE_TRY(dalloc(b, &D.aux, R));
+    CREATE_TRY(dalloc(b, &D.epoch, R));
+    CREATE_TRY(dalloc(b, &D.acc, R * 8));
+    b->acc_rows = D.R;
+    std::vector<uint32_t> ident(R);
+    for (uint32_t i = 0; i < R; ++i) ident[i] = i;
+    CREATE_TRY(dalloc(b, &b->d_acc_row, R));
+    CREATE_TRY(copy_up(b, b->d_acc_row, ident.data(), R, "acc_row"));
+    D.acc_row = b->d_acc_row;
+    CREATE_TRY(dalloc(b, &D.chunks, R * 2 * SSE_MAX_CHUNKS));
+    CREATE_TRY(dalloc(b, &D.segs, R * D.stride, false));
+    if (b->defer) { // flip bytes start (and stay, beyond every cutoff) zero
+        CREATE_TRY(dalloc(b, &D.flipb, R * D.stride));
+        CREATE_TRY(dalloc(b, &D.pend, R));
+    }
+    CREATE_TRY(dalloc(b, &D.dbg, R * 16));
+    if (D.bond_stride) CREATE_TRY(upload(b, D.wtot_r, T.wtots, "weight"));
+    CREATE_TRY(upload(b, D.edge_w, T.edge_w, "edge table"));
+    CREATE_TRY(upload(b, D.edges_compact, T.edges_compact, "edge table"));
+    if (is_pm(b)) CREATE_TRY(upload(b, D.pm_signs, T.signs, "sign")); // coupling signs of every bond-table row
+    CREATE_TRY(upload(b, D.adj_start, T.adj_start, "adjacency"));
+    CREATE_TRY(upload(b, D.adj, T.adj, "adjacency"));
+    CREATE_TRY(dalloc(b, &D.uf_scratch, R * plan.ufstride, false));
+    if (plan.tbl_stride) CREATE_TRY(dalloc(b, &D.tbl, R * D.tbl_stride));
+    CREATE_TRY(dalloc(b, &b->d_beta, R));
+    CREATE_TRY(dalloc(b, &b->d_out, R));
+    CREATE_TRY(dalloc(b, &b->d_vstate, R * D.nwords));
+    CREATE_TRY(dalloc(b, &b->d_ok, R));
+    CREATE_TRY(upload(b, D.bonds, T.bonds, "table"));
+    CREATE_TRY(upload(b, D.cumw, T.cum, "table"));
+    if (b->generic) CREATE_TRY(upload(b, D.mats, T.mats, "matrix"));
+    b->bonds_host = std::move(T.bonds); b->mats_host = std::move(T.mats); // (import_ops, tempering)
+    CREATE_TRY(copy_up(b, D.cutoff, std::vector<uint32_t>(R, cfg->cutoff0).data(), R, "cutoff"));
+    if (hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess) { b->err = "hipEventCreate failed"; return ISINGMC_ENODEVICE; }
+    if (cfg->init_state) return isingmc_set_state(b, UINT32_MAX, cfg->init_state);
+    hipLaunchKernelGGL(init_state_kernel, dim3(D.R), dim3(64), 0, b->stream, D);
+    if (hipDeviceSynchronize() != hipSuccess) { b->err = "init_state_kernel failed"; return ISINGMC_ENODEVICE; }
+    return ISINGMC_OK;
+}
+#undef CREATE_TRY
+
 extern "C" {
 
 int isingmc_interaction_at(const isingmc_interaction *it, const uint8_t *inputs, const uint8_t *outputs, double *out) {
@@ -759,346 +1161,37 @@ int isingmc_plan_geometry(uint32_t capacity, uint32_t W, uint32_t K, uint32_t Wm
 }
 
 int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
-    if (!cfg || !out || cfg->struct_size != sizeof(isingmc_config)) { g_create_error = "bad config pointer or struct_size"; return ISINGMC_EINVAL; }
+    if (!cfg || !out || cfg->struct_size != sizeof(isingmc_config)) return refuse(ISINGMC_EINVAL, "bad config pointer or struct_size");
     *out = nullptr;
-    const bool generic = cfg->interactions != nullptr;
-    if (generic) {
-        if (cfg->nreplicas == 0 || cfg->nvars == 0 || cfg->ninteractions == 0) { g_create_error = "nreplicas, nvars, ninteractions must be > 0"; return ISINGMC_EINVAL; }
-        if (cfg->flags & ISINGMC_CFG_PER_REPLICA_J) { g_create_error = "per-replica couplings are not available with generic interactions"; return ISINGMC_EINVAL; }
-        for (uint32_t i = 0; i < cfg->ninteractions; ++i) {
-            const isingmc_interaction &it = cfg->interactions[i];
-            if (it.nvars > 2) { // qmc_runner.rs:415-680 allows any k; the 32-bit operator word holds two variables
-                g_create_error = "interactions on more than two variables are not implemented (operator word = 2 in + 2 out bits)"; return ISINGMC_ENOTIMPL;
-            }
-            if ((it.nvars != 1 && it.nvars != 2) || !it.mat || it.vars[0] >= cfg->nvars || (it.nvars == 2 && (it.vars[1] >= cfg->nvars || it.vars[1] == it.vars[0]))) {
-                g_create_error = "interaction must act on 1 or 2 distinct variables inside the model and carry a matrix"; return ISINGMC_EINVAL;
-            }
-            for (uint32_t k = 0; k < (it.diagonal_only ? (1u << it.nvars) : (1u << (2 * it.nvars))); ++k)
-                if (!(it.mat[k] >= 0.0) || !std::isfinite(it.mat[k])) { g_create_error = "interaction matrix entries must be finite and >= 0"; return ISINGMC_EINVAL; }
-        }
-    } else
-    if (cfg->nreplicas == 0 || cfg->nvars == 0 || (cfg->nedges != 0 && (!cfg->edges || !cfg->J))) { g_create_error = "nreplicas and nvars must be > 0 and edges/J non-null when nedges > 0"; return ISINGMC_EINVAL; }
-    if (cfg->capacity == 0) { g_create_error = "capacity must be > 0"; return ISINGMC_EINVAL; }
-    if (cfg->cutoff0 > cfg->capacity) { g_create_error = "cutoff0 exceeds capacity"; return ISINGMC_EINVAL; }
-    if (cfg->nvars > SSE_VAR_MASK) { g_create_error = "too many variables"; return ISINGMC_EINVAL; }
-    if (!generic && !(cfg->transverse >= 0.0)) { g_create_error = "transverse field must be >= 0"; return ISINGMC_EINVAL; }
-    for (uint32_t e = 0; !generic && e < cfg->nedges; ++e)
-        if (cfg->edges[2 * e] >= cfg->nvars || cfg->edges[2 * e + 1] >= cfg->nvars || cfg->edges[2 * e] == cfg->edges[2 * e + 1]) {
-            g_create_error = cfg->edges[2 * e] == cfg->edges[2 * e + 1] ? "edge joins a variable to itself (self-loop)" : "edge endpoint out of range";
-            return ISINGMC_EINVAL;
-        }
+    if (const int rc = check_config(cfg)) return rc;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available (this library has no CPU fallback)"; return ISINGMC_ENODEVICE; }
-    isingmc_batch *b = new isingmc_batch();
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return refuse(ISINGMC_ENODEVICE, "no HIP device available (this library has no CPU fallback)");
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    b->device = dev;
-    auto fail = [&](int rc) { g_create_error = b->err; isingmc_destroy(b); return rc; };
-    if (hipSetDevice(dev) != hipSuccess) { b->err = "hipSetDevice failed"; return fail(ISINGMC_ENODEVICE); }
-
-    DevBatch &D = b->dev;
-    const bool perJ_cfg = (cfg->flags & ISINGMC_CFG_PER_REPLICA_J) != 0;
-    if ((cfg->transverse_r || cfg->longitudinal_r) && (!perJ_cfg || generic)) { b->err = "per-replica fields need ISINGMC_CFG_PER_REPLICA_J (per-replica bond tables)"; return fail(ISINGMC_EINVAL); }
-    auto gamma_of = [&](uint32_t row) { return cfg->transverse_r ? cfg->transverse_r[row] : cfg->transverse; };
-    auto hfield_of = [&](uint32_t row) { return cfg->longitudinal_r ? cfg->longitudinal_r[row] : cfg->longitudinal; };
-    const bool has_long = !generic && std::fabs(hfield_of(0)) > DBL_EPSILON; // qmc_ising.rs:230
-    for (uint32_t r = 0; !generic && r < (perJ_cfg ? cfg->nreplicas : 1u); ++r) {
-        if (!(gamma_of(r) >= 0.0) || !std::isfinite(gamma_of(r)) || !std::isfinite(hfield_of(r))) { b->err = "fields must be finite, transverse field >= 0"; return fail(ISINGMC_EINVAL); }
-        if ((std::fabs(hfield_of(r)) > DBL_EPSILON) != has_long) { b->err = "longitudinal fields must be all zero or all non-zero within a batch"; return fail(ISINGMC_EINVAL); }
-    }
-    b->generic = generic;
-    D.R = cfg->nreplicas; D.N = cfg->nvars; D.E = generic ? 0u : cfg->nedges;
-    D.Nb = generic ? cfg->ninteractions : cfg->nedges + cfg->nvars + (has_long ? cfg->nvars : 0);
-    if (D.Nb > SSE_MAX_BONDS) { b->err = "too many bonds"; return fail(ISINGMC_EINVAL); }
-    D.cap = cfg->capacity; D.nwords = (cfg->nvars + 31) / 32;
-    D.seed_lo = (uint32_t)cfg->seed; D.seed_hi = (uint32_t)(cfg->seed >> 32);
-    D.replica_offset = cfg->replica_offset;
-
-    // bond table (qmc_ising.rs:186-205,228-246; weights :863-888; offsets :97-99); one per replica when every
-    // replica has its own couplings (disorder realisations, ISINGMC_CFG_PER_REPLICA_J: cfg->J is [R][E])
-    const bool perJ = (cfg->flags & ISINGMC_CFG_PER_REPLICA_J) != 0;
-    const uint32_t nH = perJ ? D.R : 1u;
-    b->per_replica_J = perJ;
-    std::vector<BondRec> &tab = b->bonds_host;
-    tab.resize((size_t)nH * D.Nb);
-    std::vector<double> cum((size_t)nH * D.Nb), wtots(nH);
-    if (perJ) b->offsets.resize(nH);
-    if (generic) {
-        // bond b = interaction b.  Weights go to mats[b][in | out<<2] (bit 0 = first variable); the reference's index
-        // is (out0 out1 in0 in1) with the first variable most significant (Interaction::index_from_state,
-        // qmc_runner.rs:666-679).  Kinds only feed the transverse-op counters: a one-variable interaction with four
-        // equal entries is a cluster edge (cluster.rs:284-286).
-        b->mats_host.assign((size_t)D.Nb * 16, 0.0);
-        double c = 0.0;
-        for (uint32_t i = 0; i < D.Nb; ++i) {
-            const isingmc_interaction &it = cfg->interactions[i];
-            double *mb = b->mats_host.data() + (size_t)i * 16;
-            for (uint32_t in = 0; in < (1u << it.nvars); ++in)      // device layout: bit 0 = first variable
-                for (uint32_t out = 0; out < (1u << it.nvars); ++out) {
-                    const uint8_t ib[2] = {(uint8_t)(in & 1u), (uint8_t)((in >> 1) & 1u)}, ob[2] = {(uint8_t)(out & 1u), (uint8_t)((out >> 1) & 1u)};
-                    (void)isingmc_interaction_at(&it, ib, ob, &mb[in | (out << 2)]);
-                }
-            double maxw = 0.0; // heatbath.rs:130-146 make_bond_weights: largest diagonal element
-            for (uint32_t st = 0; st < (it.nvars == 2 ? 4u : 2u); ++st) maxw = std::max(maxw, mb[st | (st << 2)]);
-            const uint32_t kind = it.nvars == 2 ? SSE_BOND_TWO_SITE
-                                  : ((mb[0] == mb[1] && mb[0] == mb[4] && mb[0] == mb[5]) ? SSE_BOND_TRANSVERSE : SSE_BOND_LONGITUDINAL);
-            tab[i].a_info = it.vars[0] | (kind << SSE_INFO_SHIFT);
-            tab[i].c = it.nvars == 2 ? it.vars[1] : SSE_NO_VAR;
-            tab[i].w = maxw;
-            c = (i == 0) ? maxw : maxw + c;
-            cum[i] = c;
-        }
-        wtots[0] = c;
-        b->offset = cfg->energy_offset;
-        // Interaction::sym_under_ising (qmc_runner.rs:639-664): every weight equals the weight with all spins flipped
-        b->generic_sym = true;
-        for (uint32_t i = 0; i < D.Nb && b->generic_sym; ++i) {
-            const double *mb = b->mats_host.data() + (size_t)i * 16;
-            const uint32_t mask = cfg->interactions[i].nvars == 2 ? 0xFu : 0x5u;
-            for (uint32_t idx = 0; idx < 16; ++idx)
-                if ((idx & ~mask) == 0 && std::fabs(mb[idx] - mb[idx ^ mask]) >= DBL_EPSILON) { b->generic_sym = false; break; }
-        }
-    }
-    for (uint32_t hI = 0; !generic && hI < nH; ++hI) {
-        BondRec *t0 = tab.data() + (size_t)hI * D.Nb;
-        const double *Jh = cfg->J + (size_t)hI * D.E;
-        double off = 0.0;
-        for (uint32_t e = 0; e < D.E; ++e) {
-            const double J = Jh[e];
-            t0[e].a_info = cfg->edges[2 * e] | ((SSE_BOND_TWO_SITE | (J < 0.0 ? SSE_BOND_PREF_BIT : 0u)) << SSE_INFO_SHIFT);
-            t0[e].c = cfg->edges[2 * e + 1];
-            t0[e].w = 2.0 * std::fabs(J);
-            off += std::fabs(J);
-        }
-        const double gam = gamma_of(hI), hl = hfield_of(hI);
-        for (uint32_t v = 0; v < D.N; ++v) {
-            BondRec &t = t0[D.E + v];
-            t.a_info = v | (SSE_BOND_TRANSVERSE << SSE_INFO_SHIFT); t.c = SSE_NO_VAR; t.w = gam;
-        }
-        if (has_long)
-            for (uint32_t v = 0; v < D.N; ++v) {
-                BondRec &t = t0[D.E + D.N + v];
-                t.a_info = v | ((SSE_BOND_LONGITUDINAL | (hl > 0.0 ? SSE_BOND_PREF_BIT : 0u)) << SSE_INFO_SHIFT);
-                t.c = SSE_NO_VAR; t.w = 2.0 * std::fabs(hl);
-            }
-        const double offset = off + (double)D.N * (gam + std::fabs(hl));
-        if (hI == 0) b->offset = offset;
-        if (perJ) b->offsets[hI] = offset;
-        double c = 0.0;
-        for (uint32_t i = 0; i < D.Nb; ++i) { c = (i == 0) ? t0[0].w : t0[i].w + c; cum[(size_t)hI * D.Nb + i] = c; }
-        wtots[hI] = c;
-    }
-    D.wtot = wtots[0];
-    D.bond_stride = perJ ? D.Nb : 0u;
-
-    // launch geometry: W waves per replica, all of LDS for one workgroup
+    if (hipSetDevice(dev) != hipSuccess) return refuse(ISINGMC_ENODEVICE, "hipSetDevice failed");
     int max_lds = 0;
     if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || max_lds <= 0) max_lds = 65536;
-    const size_t total_words = (size_t)max_lds / 4;
-    // default 4 waves per replica: with 16-bit union-find parents the footprint at the headline size stays below half
-    // of the 160 KB LDS, so two workgroups share a CU and overlap each other's barriers (measured best on MI355X)
-    uint32_t W = cfg->waves_per_replica ? cfg->waves_per_replica : 4;
-    uint32_t K = cfg->slots_per_lane ? cfg->slots_per_lane : 4;
-    if (W != 1 && W != 4 && W != 6 && W != 8 && W != 16) { b->err = "waves_per_replica must be 1, 4, 6, 8 or 16"; return fail(ISINGMC_EINVAL); }
-    if (K != 1 && K != 2 && K != 4) { b->err = "slots_per_lane must be 1, 2 or 4"; return fail(ISINGMC_EINVAL); }
-    // compact edge table staged in LDS when it is small enough (a|c<<15|pref<<30 needs N <= 32768)
-    // uniform |J| lets the kernels keep the two-site weight in a scalar register
-    D.uniformJ = 1u; D.wJ = tab[0].w;
-    for (uint32_t hI = 0; hI < nH && D.uniformJ; ++hI)
-        for (uint32_t e = 0; e < D.E; ++e) if (tab[(size_t)hI * D.Nb + e].w != tab[0].w) { D.uniformJ = 0u; break; }
-    b->fused_launch = (cfg->flags & ISINGMC_CFG_FUSED_LAUNCH) != 0;
-    D.rvb_growers = (cfg->flags & ISINGMC_CFG_RVB_SERIAL_GROWTH) ? 0u : 64u;
-    bool CL = !generic && !perJ && D.uniformJ && D.N <= SSE_CE_MAX_VARS && (size_t)D.E * 4 <= 48 * 1024 && !(cfg->flags & ISINGMC_CFG_NO_LDS_TABLES);
-    uint32_t ledges = CL ? D.E : 0u;
-    // Per-variable scan tables: in LDS while W copies of them fit (with room for a union-find), otherwise in a per-replica
-    // HBM scratch served by L2 / Infinity Cache (MODE 2; ISINGMC_CFG_GLOBAL_TABLES forces it on any model).
-    bool TG = (cfg->flags & ISINGMC_CFG_GLOBAL_TABLES) != 0;
-    // (words of the general launch at w waves, tables in LDS, no union-find)
-    auto fixed_lds = [&](uint32_t w) { return general_lds_words(w, D, ledges, false, 0u, 0u); };
-    // the engine's own move of the tables to HBM (the caller did not ask for it): true when they do not fit at the geometry asked for
-    auto tables_to_hbm = [&]() {
-        W = cfg->waves_per_replica ? cfg->waves_per_replica : 4;
-        if (fixed_lds(W) + 4096 <= total_words) return false;
-        if (!cfg->waves_per_replica) return true;
-        // explicit geometry: keep the LDS tables if a smaller W makes them fit (previous behaviour)
-        while (W > 1 && fixed_lds(W) + 4096 > total_words) W = (W == 4) ? 1 : (W == 6 ? 4 : W >> 1);
-        if (fixed_lds(W) + 64 <= total_words) return false;
-        W = cfg->waves_per_replica;
-        return true;
-    };
-    if (!TG && tables_to_hbm()) {
-        // The tables do not fit next to the compact edge table (a long chain: up to 48 KB of edges): the edge table leaves LDS first
-        // (the general bond table serves the model), and the HBM tables, which need the general bond table, come without it too.
-        if (CL) { CL = false; ledges = 0u; TG = tables_to_hbm(); }
-        else TG = true;
-    }
-    // (only with the caller's own ISINGMC_CFG_GLOBAL_TABLES)
-    if (TG && CL) { b->err = "ISINGMC_CFG_GLOBAL_TABLES needs the general bond table: combine it with ISINGMC_CFG_NO_LDS_TABLES"; return fail(ISINGMC_EINVAL); }
-    if (TG && K == 2) K = 4;
-    const uint32_t pm_room = TG ? (D.E + 31u) / 32u : 0u; // (room for the +-J decode's signs, decided below)
-    if (general_lds_words(W, D, ledges, TG, pm_room, 0u) + 64 > total_words) { b->err = "model too large: the spin-state bit arrays alone exceed LDS"; return fail(ISINGMC_ENOTIMPL); }
-    // off-diagonal launches may use their own wave count (see run()): explicit, or decided per launch (then up to 16)
-    uint32_t W_off = cfg->waves_offdiag;
-    if (W_off != 0 && W_off != 1 && W_off != 4 && W_off != 6 && W_off != 8 && W_off != 16) { b->err = "waves_offdiag must be 0, 1, 4, 6, 8 or 16"; return fail(ISINGMC_EINVAL); }
-    if (!W_off && cfg->waves_per_replica) W_off = W; // an explicit waves_per_replica pins both kinds of launch
-    if (TG) W_off = W;                               // tables in HBM: one geometry for every launch
-    if (W_off && general_lds_words(W_off, D, ledges, TG, 0u, 0u) + 64 > total_words) W_off = W;
-    const bool w16_possible = !TG && fixed_lds(16) + 64 <= total_words;
-    // (8 waves without an LDS union-find: the geometry of launches whose cluster ids need the 32-bit union-find in HBM anyway)
-    const bool w8_possible = !TG && W < 8 && (K == 4 || K == 1) && fixed_lds(8) + 64 <= total_words;
-    b->w8_ok = w8_possible && !W_off;
-    const uint32_t Wmax = W_off ? (W_off > W ? W_off : W) : ((W < 16 && w16_possible) ? 16u : (w8_possible ? 8u : W));
-    const size_t ids_max = (size_t)Wmax * D.N + D.cap;
-    b->W = W; b->K = K; b->mode = TG ? SSE_MODE_GLOBAL_TABLES : (CL ? SSE_MODE_LDS_EDGES : SSE_MODE_GENERAL); b->W_off = W_off;
-    // "+-J" decode for large disorder batches (BASELINE configs[4]): every replica its own coupling signs on one graph with uniform
-    // |J|, Gamma, h.  The general decode fetches a 16-byte record per op and pass from a per-replica table of megabytes — one random
-    // HBM sector each time, in a mode that is bound by exactly those; here the variables come from the shared compact edge table
-    // (L2-resident), the sign from 12 KB of LDS.  Default geometry only.
-    const bool PMJ = TG && perJ && D.uniformJ && !generic && W == 4 && K == 4 && D.N <= SSE_CE_MAX_VARS && !cfg->transverse_r && !cfg->longitudinal_r &&
-                     !(cfg->flags & ISINGMC_CFG_NO_PM_DECODE);
-    if (PMJ) {
-        b->mode = SSE_MODE_PM_GLOBAL_TABLES;
-        D.pm_words = (D.E + 31u) / 32u;
-        // the diagonal launch keeps its per-wave spin bytes in LDS when W * N bytes fit next to the small arrays
-        const size_t words = diag_lds_words(W, D, 0u, false, D.pm_words, true);
-        b->lds_words_pm_diag = (words + 64 <= total_words && !(cfg->flags & ISINGMC_CFG_GLOBAL_TABLES)) ? words : 0;
-    }
-    { // chunk grid and row stride: one function (also exported for the CPU-side bound checks of tests/test_abi_cpu.py)
-        uint32_t geo[4];
-        if (isingmc_plan_geometry(D.cap, W, K, Wmax, geo) != ISINGMC_OK) { b->err = "capacity too large for the row stride"; return fail(ISINGMC_EINVAL); }
-        D.CH = geo[0]; D.nchunks = geo[1]; D.stride = geo[2];
-    }
-    b->lds_words_diag = diag_lds_words(W, D, ledges, TG, pm_room); b->lds_total_words = total_words; b->uf_ids_limit = cfg->lds_uf_ids_limit;
-    b->lds_words_fast = fast_lds_words(D);
-    b->fast_diag = CL && !TG && W == 4 && (K == 4 || K == 2) && D.N <= SSE_FAST_MAX_VARS && !b->fused_launch &&
-                   !(cfg->flags & ISINGMC_CFG_NO_FAST_DIAG) && lds_bytes_of(b->lds_words_fast) <= 40 * 1024; // 4 workgroups per CU
-    // the cluster update of that geometry has its own kernel too (16 waves, packed tables; sse_cluster.hip.h)
-    b->lean_cluster = CL && !TG && !generic && D.N <= 4095u && !b->fused_launch && !cfg->waves_offdiag && !cfg->waves_per_replica &&
-                      !(cfg->flags & ISINGMC_CFG_NO_LEAN_CLUSTER);
-    { // the RVB pass reuses everything from the scan tables on: launches that run it get enough LDS for its scratch
-      // and constant-op table (other launches keep the smaller footprint, which decides workgroups per CU)
-        const size_t want = rvb_lds_words(W, D, ledges, TG, pm_room);
-        b->lds_words_rvb = want < total_words ? want : total_words;
-    }
-    b->rvb_global = (cfg->flags & ISINGMC_CFG_RVB_GLOBAL_TABLES) != 0; // (the two-launch form keeps its tables in LDS: never with this flag)
-    b->rvb_split = !generic && !TG && !is_pm(b) && !b->fused_launch && !(cfg->flags & ISINGMC_CFG_RVB_FUSED) && !b->rvb_global;
-    { // waves of the RVB main launch: as many as keep about 16 waves on a CU (its LDS footprint decides how many replicas share one)
-        const size_t w4 = 4 * (size_t)rvb_main_lds_words(4, D, ledges);
-        const size_t per_cu = w4 ? (size_t)max_lds / w4 : 0;
-        b->rvb_main_W = per_cu >= 4 ? 4u : (per_cu >= 2 ? 8u : 16u);
-    }
-    if (cfg->waves_per_replica == 4 || cfg->waves_per_replica == 8 || cfg->waves_per_replica == 16) b->rvb_main_W = cfg->waves_per_replica; // an explicit geometry is honoured here too
-    size_lds(b);
-    D.gamma = cfg->transverse; D.wh = 2.0 * std::fabs(cfg->longitudinal); D.hpos = cfg->longitudinal > 0.0 ? 1u : 0u;
-    D.has_long = has_long ? 1u : 0u;
-
-    int rc;
-    if ((rc = dalloc(b, &D.ops, (size_t)D.R * D.stride))) return fail(rc);
-    if ((rc = dalloc(b, &D.state, (size_t)D.R * D.nwords))) return fail(rc);
-    if ((rc = dalloc(b, &D.n, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &D.ntrans, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &D.cutoff, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &D.err, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &D.aux, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &D.epoch, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &D.acc, (size_t)D.R * 8))) return fail(rc);
-    b->acc_rows = D.R;
-    if ((rc = dalloc(b, &b->d_acc_row, D.R))) return fail(rc);
-    {
-        std::vector<uint32_t> ident(D.R);
-        for (uint32_t i = 0; i < D.R; ++i) ident[i] = i;
-        if (hipMemcpy(b->d_acc_row, ident.data(), sizeof(uint32_t) * D.R, hipMemcpyHostToDevice) != hipSuccess) { b->err = "acc_row upload failed"; return fail(ISINGMC_ENODEVICE); }
-        D.acc_row = b->d_acc_row;
-    }
-    if ((rc = dalloc(b, &D.chunks, (size_t)D.R * 2 * SSE_MAX_CHUNKS))) return fail(rc);
-    if ((rc = dalloc(b, &D.segs, (size_t)D.R * D.stride, false))) return fail(rc);
-    b->defer = b->lean_cluster && b->fast_diag && !(cfg->flags & ISINGMC_CFG_NO_DEFERRED_FLIPS);
-    if (b->defer) { // flip bytes start (and stay, beyond every cutoff) zero
-        if ((rc = dalloc(b, &D.flipb, (size_t)D.R * D.stride))) return fail(rc);
-        if ((rc = dalloc(b, &D.pend, D.R))) return fail(rc);
-    }
-    if ((rc = dalloc(b, &D.dbg, (size_t)D.R * 16))) return fail(rc);
-    BondRec *dbonds = nullptr; double *dcum = nullptr;
-    if ((rc = dalloc(b, &dbonds, (size_t)nH * D.Nb, false))) return fail(rc);
-    if ((rc = dalloc(b, &dcum, (size_t)nH * D.Nb, false))) return fail(rc);
-    D.bonds = dbonds; D.cumw = dcum;
-    if (perJ) {
-        double *dwt = nullptr;
-        if ((rc = dalloc(b, &dwt, nH, false))) return fail(rc);
-        if (hipMemcpy(dwt, wtots.data(), sizeof(double) * nH, hipMemcpyHostToDevice) != hipSuccess) { b->err = "weight upload failed"; return fail(ISINGMC_ENODEVICE); }
-        D.wtot_r = dwt;
-    }
-    {
-        std::vector<double> ew(D.E);
-        std::vector<uint32_t> ce(D.E, 0u);
-        for (uint32_t e = 0; e < D.E; ++e) {
-            ew[e] = tab[e].w;
-            if (D.N <= SSE_CE_MAX_VARS)
-                ce[e] = (tab[e].a_info & SSE_CE_VAR_MASK) | ((tab[e].c & SSE_CE_VAR_MASK) << 15) | (((tab[e].a_info >> (SSE_INFO_SHIFT + 2)) & 1u) << 30);
-        }
-        double *dew = nullptr; uint32_t *dce = nullptr;
-        if ((rc = dalloc(b, &dew, D.E, false))) return fail(rc);
-        if ((rc = dalloc(b, &dce, D.E, false))) return fail(rc);
-        if (hipMemcpy(dew, ew.data(), sizeof(double) * D.E, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dce, ce.data(), sizeof(uint32_t) * D.E, hipMemcpyHostToDevice) != hipSuccess) { b->err = "edge table upload failed"; return fail(ISINGMC_ENODEVICE); }
-        D.edge_w = dew; D.edges_compact = dce;
-    }
-    if (is_pm(b)) { // coupling signs of every bond-table row: bit e = prefers aligned (J < 0)
-        std::vector<uint32_t> sg((size_t)nH * D.pm_words, 0u);
-        for (uint32_t hI = 0; hI < nH; ++hI)
-            for (uint32_t e = 0; e < D.E; ++e)
-                if ((tab[(size_t)hI * D.Nb + e].a_info >> (SSE_INFO_SHIFT + 2)) & 1u) sg[(size_t)hI * D.pm_words + (e >> 5)] |= 1u << (e & 31);
-        uint32_t *dsg = nullptr;
-        if ((rc = dalloc(b, &dsg, sg.size(), false))) return fail(rc);
-        if (hipMemcpy(dsg, sg.data(), 4 * sg.size(), hipMemcpyHostToDevice) != hipSuccess) { b->err = "sign upload failed"; return fail(ISINGMC_ENODEVICE); }
-        D.pm_signs = dsg;
-    }
-    { // bonds_for_var (make_classical_bonds, qmc_ising.rs:421-432): edge order
-        std::vector<uint32_t> as(D.N + 2, 0u), ad(2 * (size_t)D.E + 1), fill(D.N, 0u);
-        for (uint32_t e = 0; e < D.E; ++e) { as[cfg->edges[2 * e] + 1]++; as[cfg->edges[2 * e + 1] + 1]++; }
-        for (uint32_t v = 0; v < D.N; ++v) as[v + 1] += as[v];
-        for (uint32_t e = 0; e < D.E; ++e) {
-            const uint32_t a = cfg->edges[2 * e], c2 = cfg->edges[2 * e + 1];
-            ad[as[a] + fill[a]++] = e;
-            ad[as[c2] + fill[c2]++] = e;
-        }
-        uint32_t *das = nullptr, *dad = nullptr;
-        if ((rc = dalloc(b, &das, D.N + 2, false))) return fail(rc);
-        if ((rc = dalloc(b, &dad, 2 * (size_t)D.E + 1, false))) return fail(rc);
-        if (hipMemcpy(das, as.data(), sizeof(uint32_t) * (D.N + 2), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dad, ad.data(), sizeof(uint32_t) * (2 * (size_t)D.E + 1), hipMemcpyHostToDevice) != hipSuccess) { b->err = "adjacency upload failed"; return fail(ISINGMC_ENODEVICE); }
-        D.adj_start = das; D.adj = dad;
-    }
-    const size_t ufstride = ids_max + 2 * ((ids_max + 31) / 32);
-    if ((rc = dalloc(b, &D.uf_scratch, (size_t)D.R * ufstride, false))) return fail(rc);
-    if (TG) {
-        D.tbl_stride = (uint32_t)((((size_t)Wmax * D.N * 4 + D.N) + 15) & ~(size_t)15); // 4-byte scan records per (wave, variable)
-        if ((rc = dalloc(b, &D.tbl, (size_t)D.R * D.tbl_stride))) return fail(rc);
-    }
-    if ((rc = dalloc(b, &b->d_beta, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &b->d_out, D.R))) return fail(rc);
-    if ((rc = dalloc(b, &b->d_vstate, (size_t)D.R * D.nwords))) return fail(rc);
-    if ((rc = dalloc(b, &b->d_ok, D.R))) return fail(rc);
-    if (hipMemcpy(dbonds, tab.data(), sizeof(BondRec) * (size_t)nH * D.Nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dcum, cum.data(), sizeof(double) * (size_t)nH * D.Nb, hipMemcpyHostToDevice) != hipSuccess) { b->err = "table upload failed"; return fail(ISINGMC_ENODEVICE); }
-    if (generic) {
-        double *dm = nullptr;
-        if ((rc = dalloc(b, &dm, b->mats_host.size(), false))) return fail(rc);
-        if (hipMemcpy(dm, b->mats_host.data(), sizeof(double) * b->mats_host.size(), hipMemcpyHostToDevice) != hipSuccess) { b->err = "matrix upload failed"; return fail(ISINGMC_ENODEVICE); }
-        D.mats = dm;
-    }
-    std::vector<uint32_t> cut(D.R, cfg->cutoff0);
-    if (hipMemcpy(D.cutoff, cut.data(), sizeof(uint32_t) * D.R, hipMemcpyHostToDevice) != hipSuccess) { b->err = "cutoff upload failed"; return fail(ISINGMC_ENODEVICE); }
-    if (hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess) { b->err = "hipEventCreate failed"; return fail(ISINGMC_ENODEVICE); }
-
-    if (cfg->init_state) {
-        rc = isingmc_set_state(b, UINT32_MAX, cfg->init_state);
-        if (rc) return fail(rc);
-    } else {
-        hipLaunchKernelGGL(init_state_kernel, dim3(D.R), dim3(64), 0, b->stream, D);
-        if (hipDeviceSynchronize() != hipSuccess) { b->err = "init_state_kernel failed"; return fail(ISINGMC_ENODEVICE); }
-    }
+    DevBatch model; Tables tables; BatchPlan plan;
+    if (const int rc = plan_config(cfg, (uint32_t)max_lds, model, tables, plan)) return rc;
+    isingmc_batch *b = new isingmc_batch();
+    b->device = dev;
+    if (const int rc = allocate_and_upload(b, cfg, model, tables, plan)) { g_create_error = b->err; isingmc_destroy(b); return rc; }
     *out = b;
+    return ISINGMC_OK;
+}
+
+// The plan isingmc_create would make for cfg on a device whose workgroups have lds_bytes of LDS, or the code and message it would
+// refuse cfg with.  Host only: no device is looked for, nothing is allocated.  Slots: include/isingmc_hip.h.
+int isingmc_plan_batch(const isingmc_config *cfg, uint32_t lds_bytes, uint32_t out[32]) {
+    if (!cfg || !out || cfg->struct_size != sizeof(isingmc_config)) return refuse(ISINGMC_EINVAL, "bad config pointer or struct_size");
+    if (const int rc = check_config(cfg)) return rc;
+    DevBatch model; Tables tables; BatchPlan p;
+    if (const int rc = plan_config(cfg, lds_bytes, model, tables, p)) return rc;
+    const uint32_t slots[32] = {p.W, p.K, p.mode, p.W_off, p.Wmax, p.w8_ok, p.CH, p.nchunks, p.stride, p.pm_words, (uint32_t)p.lds_words_pm_diag,
+                                (uint32_t)p.lds_words_diag, (uint32_t)p.lds_words_fast, p.fast_diag, p.lean_cluster, p.defer, (uint32_t)p.lds_words_rvb,
+                                p.rvb_global, p.rvb_split, p.rvb_main_W, p.tbl_stride, (uint32_t)p.ufstride, (uint32_t)((uint64_t)p.ufstride >> 32),
+                                (uint32_t)p.lds_words, p.lds_ufcap, model.nwords, model.Nb};
+    std::copy(slots, slots + 32, out);
     return ISINGMC_OK;
 }
 
@@ -1233,12 +1326,19 @@ static void host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t o
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// f64::powi as Rust lowers it (compiler-rt __powidf2): squaring sequence, reciprocal for negative exponents
-static double host_powi(double x, int64_t n) {
+// f64::powi as Rust lowers it (compiler-rt __powidf2): squaring sequence, reciprocal for negative exponents.  Multiplications
+// and one division only: the host and the device give the same bits (as does the oracle, which multiplies in the same order)
+__host__ __device__ static inline double pt_powi(double x, int64_t n) {
     uint64_t m = n < 0 ? (uint64_t)(-n) : (uint64_t)n;
     double r = 1.0;
     while (m) { if (m & 1u) r *= x; x *= x; m >>= 1; }
     return n < 0 ? 1.0 / r : r;
+}
+// The swap test of a pair of neighbouring temperatures t, t + 1 (swap_on_chunks, tempering_container.rs:296-298): the walker at t
+// holds n_a ops, the one at t + 1 n_b; rel = the product of their relative weights under each other's Hamiltonian (1 when the
+// Hamiltonians are equal: a multiplication by 1.0 changes no bit); u uniform in [0, 1)
+__host__ __device__ static inline bool pt_accept(double beta_t, double beta_t1, uint32_t n_a, uint32_t n_b, double rel, double u) {
+    return pt_powi(beta_t / beta_t1, (int64_t)n_b - (int64_t)n_a) * rel > u;
 }
 
 int isingmc_pt_decide(uint64_t seed, uint64_t step, uint32_t nchains, uint32_t ntemps, const double *betas,
@@ -1258,8 +1358,7 @@ int isingmc_pt_decide(uint64_t seed, uint64_t step, uint32_t nchains, uint32_t n
                 host_philox(ctr, key, o);
                 const double u = (double)o[0] * (1.0 / 4294967296.0);
                 uint32_t &ca = config_at[(size_t)t * nchains + chain], &cb = config_at[(size_t)(t + 1) * nchains + chain];
-                const int64_t dn = (int64_t)n_of_config[cb] - (int64_t)n_of_config[ca];
-                if (host_powi(betas[t] / betas[t + 1], dn) > u) { // swap_on_chunks (:296-298), equal Hamiltonians: f64::powi
+                if (pt_accept(betas[t], betas[t + 1], n_of_config[ca], n_of_config[cb], 1.0, u)) { // (equal Hamiltonians)
                     const uint32_t tmp = ca; ca = cb; cb = tmp;
                     swaps++;
                 }
@@ -1717,12 +1816,6 @@ struct PtDev {
     uint32_t K, T, key0, key1;
     uint64_t step;
 };
-__device__ __forceinline__ double pt_dev_powi_signed(double x, long long n) { // (the multiplication sequence of pt_powi_signed)
-    unsigned long long m = n < 0 ? (unsigned long long)(-n) : (unsigned long long)n;
-    double r = 1.0;
-    while (m) { if (m & 1ull) r *= x; x *= x; m >>= 1; }
-    return n < 0 ? 1.0 / r : r;
-}
 // One tempering step of a rank that owns all temperatures (tempering_container.rs:121-149; the decisions of isingmc_pt_step's host
 // path, same Philox counters): thread k takes chain k — equalise its cutoffs, draw the order coin, walk the two sets of pairs.
 __global__ void pt_decide_kernel(DevBatch B, PtDev P) {
@@ -1744,8 +1837,7 @@ __global__ void pt_decide_kernel(DevBatch B, PtDev P) {
                 const uint32_t la = t * P.K + k, lb = la + P.K;
                 const uint32_t ra = P.at[la], rb = P.at[lb];
                 const double u = (double)philox4x32_10(1u + t, (uint32_t)P.step, k, c3, P.key0, P.key1).x * (1.0 / 4294967296.0);
-                const double p = pt_dev_powi_signed(P.betas[t] / P.betas[t + 1], (long long)B.n[rb] - (long long)B.n[ra]);
-                if (p > u) { P.slot_of[ra] = lb; P.slot_of[rb] = la; P.at[la] = rb; P.at[lb] = ra; swaps++; }
+                if (pt_accept(P.betas[t], P.betas[t + 1], B.n[ra], B.n[rb], 1.0, u)) { P.slot_of[ra] = lb; P.slot_of[rb] = la; P.at[la] = rb; P.at[lb] = ra; swaps++; }
             }
         }
         for (uint32_t t = 0; t < P.T; ++t) {
@@ -1759,14 +1851,6 @@ __global__ void pt_decide_kernel(DevBatch B, PtDev P) {
     if (threadIdx.x == 0) { P.result[0] = s_swaps; *P.total += s_swaps; }
 }
 
-static double pt_powi(double x, uint32_t n) { // x^n by squaring (the oracle uses the same multiplication sequence)
-    double r = 1.0;
-    while (n) { if (n & 1u) r *= x; x *= x; n >>= 1; }
-    return r;
-}
-// f64::powi for the swap test's temperature factor (tempering_container.rs:296): the same squaring sequence, the reciprocal
-// for a negative exponent (compiler-rt __powidf2, which Rust's powi lowers to)
-static double pt_powi_signed(double x, int64_t n) { return n < 0 ? 1.0 / pt_powi(x, (uint32_t)(-n)) : pt_powi(x, (uint32_t)n); }
 // GraphWeights::relative_weight (tempering_traits.rs:126-155): the weight of a configuration under the Hamiltonian `to` relative
 // to the one it lives in (`from`).  Rows are [E] couplings, then Gamma, then h: product over the edges of (J_to / J_from)^count in
 // edge order, times (Gamma_to / Gamma_from)^(transverse ops), times (h_to / h_from)^(longitudinal ops) when h_from != 0
@@ -2092,9 +2176,7 @@ int isingmc_pt_step(isingmc_batch *b, uint64_t *nswaps) {
         uint32_t o[4];
         host_philox(ctr, key, o);
         const double u = (double)o[0] * (1.0 / 4294967296.0);
-        double p = pt_powi_signed(P->betas[t] / P->betas[t + 1], (int64_t)nb2 - (int64_t)na); // swap_on_chunks (:296-298): powi
-        if (P->hams_differ) p *= ra * rb;
-        return p > u;
+        return pt_accept(P->betas[t], P->betas[t + 1], na, nb2, P->hams_differ ? ra * rb : 1.0, u);
     };
     struct Wire { uint32_t n; uint32_t pad; double rel; };
     for (int phase = 0; phase < 2; ++phase) {

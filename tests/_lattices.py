@@ -104,3 +104,45 @@ def exact_energy_from_interactions(n, ints, beta):
     ev = np.linalg.eigvalsh(H)
     wts = np.exp(-beta * (ev - ev.min()))
     return float((ev * wts).sum() / wts.sum())
+
+
+# ---- the size ladder of tests/test_gpu_shape_edges.py: one model on each side of every gate of isingmc_create / run() ----
+def chain(n, jfun):
+    """Periodic chain of n >= 3 sites; two sites: one bond; one site: no edge at all."""
+    if n == 1:
+        return []
+    if n == 2:
+        return [((0, 1), jfun(0))]
+    return [((i, (i + 1) % n), jfun(i)) for i in range(n)]
+
+
+def uni_chain(i):   # uniform |J|, mixed signs
+    return -1.0 if i % 3 == 0 else 1.0
+
+
+def mix_chain(i):   # four magnitudes, mixed signs: the general bond table
+    return (0.5 + 0.25 * (i % 4)) * (-1.0 if i % 3 == 0 else 1.0)
+
+
+def uni_rect(i, j, d):
+    return -1.0 if (i + 2 * j + d) % 3 == 0 else 1.0
+
+
+def mix_rect(i, j, d):
+    return (0.5 + 0.25 * ((i + j) % 4)) * (-1.0 if (i + 2 * j + d) % 3 == 0 else 1.0)
+
+
+SMALL = [1, 2, 31, 32, 33, 63, 64, 65, 127, 129, 1023, 1025, 2047]
+UNIFORM_CHAINS = SMALL + [4071, 4072, 4095, 4096, 4097, 8480, 8481, 11041, 11042, 12288, 12289]
+UNIFORM_RECTS = [(31, 33), (45, 91), (64, 64), (17, 241), (64, 96), (65, 95)]
+MIXED_CHAINS = [1, 2, 31, 33, 65, 129, 1025, 4095, 4096, 4097, 8481, 11041, 11042]
+MIXED_RECTS = [(45, 91), (17, 241)]
+# (name, edges, nvars, h)
+LADDER = ([(f"chain{n}", chain(n, uni_chain), n, 0.0) for n in UNIFORM_CHAINS] +
+          [(f"rect{x}x{y}", rect_periodic(x, y, uni_rect), x * y, 0.0) for x, y in UNIFORM_RECTS] +
+          [(f"mixchain{n}", chain(n, mix_chain), n, 0.0) for n in MIXED_CHAINS] +
+          [(f"mixrect{x}x{y}", rect_periodic(x, y, mix_rect), x * y, 0.0) for x, y in MIXED_RECTS] +
+          [(f"chain{n}_long", chain(n, uni_chain), n, 0.2) for n in (1, 33, 1025, 4096, 11042)] +
+          [("rect17x241_long", rect_periodic(17, 241, uni_rect), 4097, -0.15), ("mixchain4097_long", chain(4097, mix_chain), 4097, 0.2)])
+LADDER_IDS = [c[0] for c in LADDER]
+assert len(set(LADDER_IDS)) == len(LADDER)

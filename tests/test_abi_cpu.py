@@ -369,3 +369,135 @@ def test_dedicated_cluster_kernel_lds_layout_and_gate():
                 assert plan(N, 0, 65535, S)[11] == 0 and plan(N, 1, 65535, S)[11] == 0, (N, S)
     for w in range(85, 92):  # the control row (ring of 8 at beta = 200) stays with the kernel
         assert plan(8, 0, 65535, 32 * w)[11] == 1
+
+
+def _plan_cases():
+    with open(os.path.join(ROOT, "tests", "golden", "batch_plans.json")) as f:
+        return json.load(f)
+
+
+def _first_lds(plan, nvars, cap, total_words, uf_ids_limit, has_long):
+    """lds_words / lds_ufcap of a fresh batch as plan_lds sizes them (no transverse op seen yet), from the recorded pair of the
+    parent, which laid out every model as one without a longitudinal field: its words = F + (ids + 1) / 2 (16-bit parents), so F,
+    the launch's LDS without a union-find, follows; a field adds two bit arrays of (ids + 31) / 32 words (Lds::carve).  ids = W N +
+    384 (or the test limit; 0 with the tables in HBM), at most 65535 and W N + cap, less in steps of 64 while the launch exceeds LDS."""
+    import _plan_cases as pc
+    p = dict(zip(pc.SLOTS, plan))
+    F = p["lds_words"] - (p["lds_ufcap"] + 1) // 2
+    words = lambda i: F + (2 * ((i + 31) // 32) if has_long else 0) + (i + 1) // 2
+    ids = uf_ids_limit or p["W"] * nvars + 384
+    if p["mode"] in (pc.MODE_GLOBAL_TABLES, pc.MODE_PM_GLOBAL_TABLES):
+        ids = 0
+    ids = min(ids, 65535, p["W"] * nvars + cap)
+    while ids > 0 and words(ids) > total_words:
+        ids -= min(ids, 64)
+    return words(ids), ids
+
+
+def test_plan_batch_gives_the_recorded_plans():
+    """isingmc_plan_batch (check_config, build_tables and the plan_batch that isingmc_create itself calls) against the plans that
+    the commit before create was taken apart printed on an MI355X for the same configs (tests/golden/batch_plans.json, recorded
+    with profiles/r07_parent_plan_print.patch): every rung of the size ladder, every cfg flag, the explicit geometries, the
+    capacity-2^20 lattice, the 32^3 +-J pair, generic interactions, per-replica fields.  Every slot is equal, but for the first
+    lds_words / lds_ufcap of models with a longitudinal field ("field" in the file): that commit sized those before it had noted
+    the field; they are held to _first_lds.  (On the cases without a field _first_lds must give back the recorded pair: that checks its
+    choice of the ids, the clamps and the 64-step loop, before it is applied here; the word count without a union-find it takes from
+    the record itself.)"""
+    import isingmontecarlo_amd as im
+    import _plan_cases as pc
+    gold = _plan_cases()
+    assert gold["slots"] == pc.SLOTS and len(gold["cases"]) >= 70
+    i_words, i_ufcap = pc.SLOTS.index("lds_words"), pc.SLOTS.index("lds_ufcap")
+    fields = 0
+    for case in gold["cases"]:
+        cfg, keep = pc.config_of(im, case)
+        rc, got = pc.plan_batch(im, cfg, gold["lds_bytes"])
+        assert rc == 0, (case["name"], rc, im.load_library().isingmc_last_error(None))
+        want = list(case["plan"])
+        assert len(want) == 32 and _first_lds(want, cfg.nvars, cfg.capacity, gold["lds_bytes"] // 4, cfg.lds_uf_ids_limit, False) == (want[i_words], want[i_ufcap]), case["name"]
+        if case.get("field"):
+            fields += 1
+            want[i_words], want[i_ufcap] = _first_lds(want, cfg.nvars, cfg.capacity, gold["lds_bytes"] // 4, cfg.lds_uf_ids_limit, True)
+        assert got == want, (case["name"], [(s, g, w) for s, g, w in zip(pc.SLOTS, got, want) if g != w])
+    assert fields >= 8
+
+
+def test_plan_batch_invariants():
+    """What every plan must satisfy, whatever the recorded values say."""
+    import isingmontecarlo_amd as im
+    import _plan_cases as pc
+    lib = im.load_library()
+    gold = _plan_cases()
+    total = gold["lds_bytes"] // 4
+    geo = (C.c_uint32 * 4)()
+    seen = {k: set() for k in ("fast_diag", "defer", "lean_cluster", "rvb_split", "rvb_global", "mode")}
+    for case in gold["cases"]:
+        cfg, keep = pc.config_of(im, case)
+        rc, out = pc.plan_batch(im, cfg, gold["lds_bytes"])
+        assert rc == 0 and out[len(pc.SLOTS):] == [0] * (32 - len(pc.SLOTS)), case["name"]
+        p = dict(zip(pc.SLOTS, out))
+        for k in ("lds_words_pm_diag", "lds_words_diag", "lds_words_rvb", "lds_words"):
+            assert p[k] <= total, (case["name"], k, p[k])
+        if p["fast_diag"]:
+            assert p["lds_words_fast"] <= total, case["name"]
+        assert lib.isingmc_plan_geometry(cfg.capacity, p["W"], p["K"], p["Wmax"], geo) == 0
+        assert [p["CH"], p["nchunks"], p["stride"]] == [int(x) for x in geo[:3]], case["name"]
+        lds_edges = p["mode"] == pc.MODE_LDS_EDGES
+        hbm = p["mode"] in (pc.MODE_GLOBAL_TABLES, pc.MODE_PM_GLOBAL_TABLES)
+        assert p["mode"] in (pc.MODE_GENERAL, pc.MODE_LDS_EDGES, pc.MODE_GLOBAL_TABLES, pc.MODE_PM_GLOBAL_TABLES)
+        assert bool(p["tbl_stride"]) == hbm and p["W_off"] <= p["Wmax"] >= p["W"], case["name"]
+        if p["fast_diag"]:
+            assert lds_edges and p["W"] == 4, case["name"]
+        if p["defer"]:
+            assert p["lean_cluster"] and p["fast_diag"], case["name"]
+        if hbm:
+            assert p["W_off"] == p["W"] and not lds_edges and p["lds_ufcap"] == 0, case["name"]
+        if p["mode"] == pc.MODE_PM_GLOBAL_TABLES:
+            assert hbm and p["W"] == 4 and p["K"] == 4 and p["pm_words"] == (cfg.nedges + 31) // 32, case["name"]
+        else:
+            assert p["pm_words"] == 0 and p["lds_words_pm_diag"] == 0, case["name"]
+        if p["rvb_split"]:
+            assert not p["rvb_global"] and not (cfg.flags & im.CFG_FUSED_LAUNCH) and not cfg.interactions and not hbm, case["name"]
+        for k in seen:
+            seen[k].add(p[k])
+    assert all(len(v) >= 2 for v in seen.values()) and len(seen["mode"]) == 4, seen
+
+
+# (what is wrong, changes to the case, changes to the model, code, words of the message)
+_CONFIG_ERRORS_BEHIND_THE_PROBE = [
+    ("fields without the flag", dict(without_per_replica_flag=True), dict(transverse_r=[1.0, 1.0, 1.0]), -1, b"per-replica fields need ISINGMC_CFG_PER_REPLICA_J (per-replica bond tables)"),
+    ("mixed fields", {}, dict(longitudinal_r=[0.2, 0.0, 0.2]), -1, b"longitudinal fields must be all zero or all non-zero within a batch"),
+    ("field not finite", {}, dict(transverse_r=[1.0, float("inf"), 1.0]), -1, b"fields must be finite, transverse field >= 0"),
+    ("waves_per_replica 5", dict(waves_per_replica=5), {}, -1, b"waves_per_replica must be 1, 4, 6, 8 or 16"),
+    ("slots_per_lane 3", dict(slots_per_lane=3), {}, -1, b"slots_per_lane must be 1, 2 or 4"),
+    ("waves_offdiag 5", dict(waves_offdiag=5), {}, -1, b"waves_offdiag must be 0, 1, 4, 6, 8 or 16"),
+    ("global tables next to the LDS edge table", dict(flags=8), {}, -1, b"ISINGMC_CFG_GLOBAL_TABLES needs the general bond table: combine it with ISINGMC_CFG_NO_LDS_TABLES"),
+    ("bit arrays beyond LDS", dict(lds_bytes=1024), {}, -5, b"model too large: the spin-state bit arrays alone exceed LDS"),
+    ("row stride", dict(capacity=0xFFFFFFFF, cutoff=16), {}, -1, b"capacity too large for the row stride"),
+]
+
+
+def test_config_errors_behind_the_device_probe_are_reachable_without_a_device():
+    """The checks isingmc_create makes once it has a device, through isingmc_plan_batch: code and message.  Where there is no
+    device, create still answers ENODEVICE for the same configs (those checks stay behind the probe)."""
+    import torch
+    import isingmontecarlo_amd as im
+    import _plan_cases as pc
+    lib = im.load_library()
+    base = dict(model=["ferro", 4], nreplicas=3, capacity=4096)
+    model = pc.model_of(base["model"])
+    cfg, keep = pc.config_of(im, base)
+    assert pc.plan_batch(im, cfg, 160 * 1024)[0] == 0
+    for what, case_changes, model_changes, code, message in _CONFIG_ERRORS_BEHIND_THE_PROBE:
+        case = dict(base, **case_changes)
+        cfg, keep = pc.config_of(im, case, dict(model, **model_changes))
+        rc, out = pc.plan_batch(im, cfg, case.get("lds_bytes", 160 * 1024))
+        assert rc == code and lib.isingmc_last_error(None) == message, (what, rc, lib.isingmc_last_error(None))
+        if not torch.cuda.is_available() and "lds_bytes" not in case:
+            h = C.c_void_p()
+            assert lib.isingmc_create(C.byref(cfg), C.byref(h)) == -2 and not h.value, what
+            assert b"no HIP device" in lib.isingmc_last_error(None), what
+    # a config error in front of the probe keeps its place there
+    cfg, keep = pc.config_of(im, dict(base, cutoff=5000))
+    assert pc.plan_batch(im, cfg, 160 * 1024)[0] == -1 and lib.isingmc_last_error(None) == b"cutoff0 exceeds capacity"
+    assert lib.isingmc_plan_batch(None, 160 * 1024, None) == -1

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import _lattices as lat
+from _lattices import chain, uni_chain, LADDER, LADDER_IDS
 from test_gpu_parity import make_pair, assert_same
 
 pytestmark = pytest.mark.gpu
@@ -27,47 +28,6 @@ FLAG_LOOP, FLAG_HEATBATH, FLAG_RVB = 1, 4, 8
 # does not fit: the ladder runs them with the tables in LDS up to the bond-map gate (4097) and through
 # ISINGMC_CFG_RVB_GLOBAL_TABLES, the documented way for larger models, beyond it
 RVB_LDS_MAX_VARS = 4097
-
-
-def chain(n, jfun):
-    """Periodic chain of n >= 3 sites; two sites: one bond; one site: no edge at all."""
-    if n == 1:
-        return []
-    if n == 2:
-        return [((0, 1), jfun(0))]
-    return [((i, (i + 1) % n), jfun(i)) for i in range(n)]
-
-
-def uni_chain(i):   # uniform |J|, mixed signs
-    return -1.0 if i % 3 == 0 else 1.0
-
-
-def mix_chain(i):   # four magnitudes, mixed signs: the general bond table
-    return (0.5 + 0.25 * (i % 4)) * (-1.0 if i % 3 == 0 else 1.0)
-
-
-def uni_rect(i, j, d):
-    return -1.0 if (i + 2 * j + d) % 3 == 0 else 1.0
-
-
-def mix_rect(i, j, d):
-    return (0.5 + 0.25 * ((i + j) % 4)) * (-1.0 if (i + 2 * j + d) % 3 == 0 else 1.0)
-
-
-SMALL = [1, 2, 31, 32, 33, 63, 64, 65, 127, 129, 1023, 1025, 2047]
-UNIFORM_CHAINS = SMALL + [4071, 4072, 4095, 4096, 4097, 8480, 8481, 11041, 11042, 12288, 12289]
-UNIFORM_RECTS = [(31, 33), (45, 91), (64, 64), (17, 241), (64, 96), (65, 95)]
-MIXED_CHAINS = [1, 2, 31, 33, 65, 129, 1025, 4095, 4096, 4097, 8481, 11041, 11042]
-MIXED_RECTS = [(45, 91), (17, 241)]
-# (name, edges, nvars, h)
-LADDER = ([(f"chain{n}", chain(n, uni_chain), n, 0.0) for n in UNIFORM_CHAINS] +
-          [(f"rect{x}x{y}", lat.rect_periodic(x, y, uni_rect), x * y, 0.0) for x, y in UNIFORM_RECTS] +
-          [(f"mixchain{n}", chain(n, mix_chain), n, 0.0) for n in MIXED_CHAINS] +
-          [(f"mixrect{x}x{y}", lat.rect_periodic(x, y, mix_rect), x * y, 0.0) for x, y in MIXED_RECTS] +
-          [(f"chain{n}_long", chain(n, uni_chain), n, 0.2) for n in (1, 33, 1025, 4096, 11042)] +
-          [("rect17x241_long", lat.rect_periodic(17, 241, uni_rect), 4097, -0.15), ("mixchain4097_long", chain(4097, mix_chain), 4097, 0.2)])
-LADDER_IDS = [c[0] for c in LADDER]
-assert len(set(LADDER_IDS)) == len(LADDER)
 
 
 def rung_parameters(nvars):
@@ -214,6 +174,35 @@ def test_every_gate_is_straddled():
             seen[k].add(info[k])
         g.close()
     assert all(v == {False, True} for v in seen.values()), seen
+
+
+def test_plan_batch_agrees_with_the_batch_created():
+    """isingmc_plan_batch, given the LDS bytes this device reports, against launch_info() of the batch isingmc_create makes from
+    the same config: on both sides of the gates that move the edge table and then the per-variable tables out of LDS (chains),
+    and on the 64 x 64 lattice."""
+    import torch
+    import isingmontecarlo_amd as im
+    import _plan_cases as pc
+    lds_bytes = torch.cuda.get_device_properties(0).shared_memory_per_block
+    models = [(f"chain{n}", chain(n, uni_chain), n) for n in (4096, 4097, 8480, 8481, 11041, 11042, 12289)] + [("rect64x64", lat.two_d_ferro(64), 4096)]
+    seen = set()
+    for name, edges, nvars in models:
+        case = dict(nreplicas=1, capacity=4096, cutoff=64)
+        cfg, keep = pc.config_of(im, case, dict(edges=edges, nvars=nvars, transverse=1.0, longitudinal=0.0))
+        rc, out = pc.plan_batch(im, cfg, lds_bytes)
+        assert rc == 0, name
+        p = dict(zip(pc.SLOTS, out))
+        g = im.QmcIsingGraph(edges, 1.0, 0.0, 64, 17, nreplicas=1, capacity=4096, nvars=nvars)
+        info = g.launch_info()
+        g.close()
+        hbm = p["mode"] in (pc.MODE_GLOBAL_TABLES, pc.MODE_PM_GLOBAL_TABLES)
+        got = (p["W"], p["K"], p["nwords"], p["mode"] == pc.MODE_LDS_EDGES, hbm, bool(p["fast_diag"]), (4 * p["lds_words_diag"] + 7) & ~7)
+        want = (info["waves_per_replica"], info["slots_per_lane"], info["state_words"], info["lds_edge_table"],
+                info["global_tables"], info["fast_diagonal"], info["lds_bytes_diagonal"])
+        assert got == want, (name, got, want)
+        assert ((4 * p["lds_words"] + 7) & ~7, p["lds_ufcap"]) == (info["lds_bytes"], info["lds_uf_ids"]), name
+        seen.add((info["lds_edge_table"], info["global_tables"]))
+    assert seen == {(True, False), (False, False), (False, True)}, seen
 
 
 @pytest.mark.parametrize("n", [33, 65, 129])

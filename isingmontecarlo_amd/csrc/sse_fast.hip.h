@@ -10,12 +10,16 @@
 //   * the W = 4 per-wave copies of the propagated spins are the four BYTES of one 32-bit entry per variable, so an
 //     off-diagonal op reaches the copies of all later (or all earlier) waves with one ds_xor_b32 instead of a loop of W - 1
 //     predicated atomics;
-//   * candidates are told apart by wave masks only (insert / removal), never by f64 selects: every lane evaluates both
-//     inequalities of the rule, the masks pick; the f64 expressions are exactly those of the general pass and of the oracle;
+//   * the acceptance rule is exact integer arithmetic (sse_accept.h): per round of the fixed point one 32 x 32 + 64 multiply-add
+//     with a sign test (insert) and one integer compare (remove); every lane evaluates both, and a lane that is no candidate
+//     carries a constant that never passes, so the two ballots are the accepted masks themselves.  The integer rule equals the
+//     oracle's f64 expressions for cutoffs up to 2^21; batches with a larger capacity run the f64 rounds (F64 = true), whose
+//     expressions are exactly those of the general pass and of the oracle;
 //   * no scalar-register spills: the kernel holds nothing but the diagonal pass (and the short directed loop behind it).
 // Requirements (checked by the host, isingmc_hip.hip): uniform |J| (LDS edge tables), N <= 4096 variables, 4 waves per
 // replica, Metropolis rule, two launches per timestep.
 #pragma once
+#include "sse_accept.h"
 
 namespace sse {
 
@@ -43,7 +47,10 @@ __device__ __forceinline__ uint32_t bfi32(uint32_t mask, uint32_t a, uint32_t b)
 }
 
 struct FastLds {
-    uint32_t o_nb;   // [4][2] f64 per class: beta*Nb*weight * 2^32 and beta*Nb*weight * 2^-32 (the 2^-32 of the uniform folded in)
+    uint32_t o_nb;   // [4] 16 bytes per class, num = beta*Nb*weight: u64 2^63 - ceil(num * 2^32) (sse_accept.h; F64 rounds: f64 num * 2^32)
+                     // and f64 num * 2^-32 (the 2^-32 of the uniform folded in)
+    uint32_t o_xch;  // [2][4] per-wave (operator-count change << 1) | changed of a round, double buffered by round parity: the
+                     // two 16-byte aligned groups inside the 16 words of the general pass' o_tot / o_chg (no LDS of its own)
     uint32_t o_tab;  // [Nb] packed bond entries
     uint32_t o_spin; // [N] u32: byte w = wave w's copy of the propagated spin (bit 0) + in-row event marker (bits 1..7)
     uint32_t o_dummy; // [64] one word per lane: target of the stores / atomics of lanes that have nothing to store
@@ -54,8 +61,10 @@ struct FastLds {
 template <int W>
 __host__ __device__ __forceinline__ FastLds fast_carve(const Lds<W> &L, const DevBatch &B) {
     FastLds F;
+    static_assert(4 * W >= 3 + 8, "o_xch: eight words behind an alignment gap of up to three, inside o_tot + o_chg");
     uint32_t base = (L.o_edges + 3u) & ~3u; // 16-byte aligned: the class constants are read as one b128
     F.o_nb = base; base += 16;
+    F.o_xch = (L.o_tot + 3u) & ~3u; // 16-byte aligned: a round reads its four words as one b128 (o_tot, o_chg: [2][W] each, adjacent)
     F.o_tab = base; base += B.Nb;
     F.o_spin = base; base += B.N;
     F.o_dummy = base; base += 64;
@@ -74,7 +83,7 @@ __device__ __forceinline__ uint32_t fast_entry(const DevBatch &B, uint32_t b, ui
     return v | (v << 12) | ((B.hpos ? 0x8u : 0x1u) << 24) | (1u << 28) | (SSE_FAST_CLASS_H << 30);
 }
 
-template <int K>
+template <int K, bool F64>
 __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L, const FastLds &F, uint32_t r, const Rng &rng, double beta,
                                               uint32_t M, int &n_io, int &ntrans_io, uint32_t &gr, uint32_t fbmask) {
     constexpr int W = 4, NT = W * 64;
@@ -105,26 +114,30 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
     // Predicated LDS stores and atomics are written branch-free: lanes that have nothing to do are pointed at a per-lane dummy
     // word instead (an address select costs two integer instructions; an exec-masked store costs a compare, a mask in two
     // scalar registers and an exec save / restore).
-    const uint32_t dummy_w = F.o_dummy + (uint32_t)lane; // word index of this lane's dummy word
+    const uint32_t dummy_b = 4u * (F.o_dummy + (uint32_t)lane); // byte address of this lane's dummy word
     // all-ones iff the op word is off-diagonal (CL: only transverse-field ops can be: bit 0 of in ^ out)
     auto evmask32 = [](uint32_t wd) -> uint32_t { return 0u - ((wd ^ (wd >> 2)) & 1u); };
-    // flip the spin of the off-diagonal ops among K words in the copies selected by `mask`
-    auto propagate = [&](const uint32_t (&wd)[K], uint32_t mask) {
+    // Each op word is decoded ONCE, when it is prefetched: byte address of the spin entry that an off-diagonal op flips, or of
+    // the lane's dummy word.  The register travels with the word into the next tile and serves both propagations and phase 2
+    // (an address different from the dummy is also the only "is off-diagonal" test they need).
+    const uint32_t spin_b = 4u * (F.o_spin - 1u - E); // (entry of the variable of transverse bond b: o_spin + b - E, b = (word >> 4) - 1)
+    auto decode = [&](uint32_t wd) -> uint32_t { return bfi32(evmask32(wd), spin_b + 4u * (wd >> 4), dummy_b); };
+    // flip the spin of the off-diagonal ops among K decoded words in the copies selected by `mask`
+    auto propagate = [&](const uint32_t (&vb)[K], uint32_t mask) {
         if (mask == 0u) return; // wave-uniform
 #pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const uint32_t v = F.o_spin + (wd[j] >> 4) - 1u - E;
-            atomicXor(&lds_raw[bfi32(evmask32(wd[j]), v, dummy_w)], mask);
-        }
+        for (int j = 0; j < K; ++j) atomicXor(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(lds_raw) + vb[j]), mask);
     };
 
-    uint32_t wnext[K];
+    uint32_t wnext[K], vnext[K];
 #pragma unroll
-    for (int j = 0; j < K; ++j) wnext[j] = ld_word((uint32_t)(wave * 64 * K + j * 64 + lane));
-    propagate(wnext, m_later);
+    for (int j = 0; j < K; ++j) { wnext[j] = ld_word((uint32_t)(wave * 64 * K + j * 64 + lane)); vnext[j] = decode(wnext[j]); }
+    propagate(vnext, m_later);
     __syncthreads();
     const uint32_t lane2 = 2u * (uint32_t)lane;
     const uint32_t vM = vgpr_copy_u32(M), vM1 = vgpr_copy_u32(M + 1u), vzero = vgpr_copy_u32(0u);
+    const uint32_t vnever_hi = vgpr_copy_u32((uint32_t)(SSE_ACCEPT_NEVER_INSERT >> 32)), vnever_thr = vgpr_copy_u32((uint32_t)SSE_ACCEPT_NEVER_REMOVE);
+    uint32_t ch = (uint32_t)(wave * 64 * K) / B.CH, chpos = (uint32_t)(wave * 64 * K) % B.CH; // chunk of this wave's share of the tile, and its offset in it
 
     for (uint32_t tile = 0; tile < ntiles; ++tile) {
         // The issue arbiter serves the oldest wave first: of the four workgroups of a CU the first dispatched runs almost as if alone
@@ -134,9 +147,9 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
 #if SSE_ROTATE_PRIO // (0: off — the arbiter's own order, for tools/wg_timeline.py)
         if ((tile & (SSE_ROTATE_PRIO - 1u)) == 0u) sse_set_prio((tile / SSE_ROTATE_PRIO) + blockIdx.x); // (the wave's slot on its SIMD, HW_ID.WAVE_ID, as the phase: no better)
 #endif
-        uint32_t word[K];
+        uint32_t word[K], vcur[K];
 #pragma unroll
-        for (int j = 0; j < K; ++j) word[j] = wnext[j];
+        for (int j = 0; j < K; ++j) { word[j] = wnext[j]; vcur[j] = vnext[j]; }
         const uint32_t pbase = tile * TS + (uint32_t)(wave * 64 * K + lane);
         {
             const uint32_t pn = (tile + 1 < ntiles ? pbase + TS : pbase);
@@ -145,10 +158,16 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
         }
         const bool partial = tile * TS + TS > M; // wave-uniform: only the last tile can hold slots >= M
 
-        double un[K], nb[K];
         uint32_t cbv[K], neww[K], ent[K], bnd[K], rr1[K];
-        uint64_t insm[K], remm[K], acc[K];
-        // Lane predicates that have to survive the rounds are wave masks (insert candidates, removal candidates, accepted);
+        uint64_t acci[K], accr[K]; // accepted inserts / removals of the round before
+        // operands of the rule: integer rounds (sse_accept.h) ...
+        uint32_t chi[K]; // (high word of the insert constant; candidates of one class share the low word: clo)
+        uint32_t clo[K];
+        int32_t thr[K];
+        // ... or f64 rounds, with the candidate masks that they have to apply
+        double un[K], nb[K];
+        uint64_t insm[K], remm[K];
+        // Lane predicates that have to survive the rounds are wave masks (accepted inserts, accepted removals);
         // everything else is recomputed from the op word with integer arithmetic when needed — the pass is short of scalar
         // registers, and a spilled mask costs a v_readlane per half and use.
         // ---- phase 1, all rows at once (nothing here depends on the spin tables): random numbers, bond, packed table entry
@@ -176,13 +195,13 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
             const uint32_t va = e & 0xFFFu, vc = (e >> 12) & 0xFFFu;
             const uint32_t adr_a = spin_my + 4u * va, adr_c = spin_my + 4u * vc;
             const uint32_t mark = markhi | inb;
-            const uint32_t ev32 = evmask32(word[j]);
-            const uint32_t adr_w = bfi32(ev32, adr_a, 4u * dummy_w); // where this lane stores: its variable's byte, or its dummy
+            const uint32_t adr_w = vcur[j] + (uint32_t)wave; // where this lane stores: its variable's byte (= adr_a), or its dummy
+            const uint64_t evm = sse_ballot(vcur[j] != dummy_b); // the off-diagonal ops of the row
             LDS8(adr_w) = (uint8_t)mark;
             SSE_WAVE_FENCE();
             const uint32_t ea = LDS8(adr_a), ec = LDS8(adr_c);
             uint32_t sa, sc;
-            const uint64_t dup = sse_ballot(((ea ^ mark) & ev32) != 0u); // an off-diagonal op whose marker was overwritten
+            const uint64_t dup = sse_ballot(ea != mark) & evm; // an off-diagonal op whose marker was overwritten
             if (!dup) {
                 sa = (ea ^ ((ea + lane2) >> 8)) & 1u;
                 sc = (ec ^ ((ec + lane2) >> 8)) & 1u;
@@ -191,7 +210,7 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
             } else { // two off-diagonal ops of this row on one variable (rare): resolve in lane order
                 sa = ea & 1u; sc = ec & 1u;
                 bool seen_a = false, seen_c = false;
-                uint64_t m = sse_ballot(ev32 != 0u);
+                uint64_t m = evm;
                 while (m) {
                     const int Ls = __ffsll((long long)m) - 1;
                     m &= m - 1;
@@ -211,63 +230,86 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
             const uint32_t e = ent[j], wd = word[j];
             const uint32_t okbit = (e >> (24u + sub0[j])) & 1u; // a diagonal op on this bond has weight in this spin state
             const uint32_t sub = sub0[j] & (e >> 28) & 3u;
-            const double2 nbp = *reinterpret_cast<const double2 *>(&lds_raw[F.o_nb + 4u * (e >> 30)]);
-            const double u = (double)rr1[j]; // the uniform is u * 2^-32: the power of two sits in the two table constants (exact)
-            insm[j] = sse_ballot(okbit > wd); // empty slot (word 0) and okbit 1
-            if (partial) insm[j] &= sse_ballot(pbase + (uint32_t)(j * 64) < M);
-            remm[j] = sse_ballot((wd & ~evmask32(wd)) != 0u); // occupied and diagonal
-            // insert:  (u 2^-32) * den < num   <=>  u * den < num * 2^32  (u is converted again in every round: one instruction
-            // against two registers per row held across the rounds)
-            un[j] = u * nbp.y;  // remove:  (u 2^-32) * num < den   with  u * (num 2^-32) == (u 2^-32) * num  bit for bit
-            nb[j] = nbp.x;
-            cbv[j] = sel64(insm[j], vM, vM1);
-            neww[j] = sel64(insm[j], ((bnd[j] + 1u) << 4) | sub | (sub << 2), vzero); // what an accepted candidate leaves in the slot
-            acc[j] = 0ull;
+            const uint4 cls = *reinterpret_cast<const uint4 *>(&lds_raw[F.o_nb + 4u * (e >> 30)]);
+            const double num_lo = __hiloint2double((int)cls.w, (int)cls.z); // num * 2^-32
+            uint64_t im = sse_ballot(okbit > wd); // insert candidates: empty slot (word 0) and okbit 1
+            if (partial) im &= sse_ballot(pbase + (uint32_t)(j * 64) < M);
+            const uint64_t rm = sse_ballot(wd != 0u) & ~sse_ballot(vcur[j] != dummy_b); // removal candidates: occupied and diagonal
+            if constexpr (F64) {
+                // insert:  (u 2^-32) * den < num   <=>  u * den < num * 2^32  (u is converted again in every round: one
+                // instruction against two registers per row held across the rounds)
+                // remove:  (u 2^-32) * num < den   with  u * (num 2^-32) == (u 2^-32) * num  bit for bit
+                un[j] = (double)rr1[j] * num_lo;
+                nb[j] = __hiloint2double((int)cls.y, (int)cls.x);
+                insm[j] = im; remm[j] = rm;
+            } else {
+                // the candidate masks end here: who is no candidate gets the operand that never passes (2^63 in the high word
+                // of the insert constant: whatever the low word, rr1 * den + it stays below 2^64 and keeps the sign bit)
+                clo[j] = cls.x;
+                chi[j] = sel64(im, cls.y, vnever_hi);
+                thr[j] = (int32_t)sel64(rm, (uint32_t)sse_accept_remove_threshold(rr1[j], num_lo), vnever_thr);
+            }
+            cbv[j] = sel64(im, vM, vM1);
+            neww[j] = sel64(im, ((bnd[j] + 1u) << 4) | sub | (sub << 2), vzero); // what an accepted candidate leaves in the slot
+            acci[j] = 0ull; accr[j] = 0ull;
         }
 
         // ---- fixed point on the live operator count (see diagonal_pass) ----
         int npref[K];
 #pragma unroll
         for (int j = 0; j < K; ++j) npref[j] = n_start;
-        int tot_all = 0, base = 0;
+        int tot_all = 0, base = 0, wtot = 0;
         bool first = true;
         for (;;) {
-            int wtot = 0;
-            bool changed = first;
+            wtot = 0;
+            uint64_t diff = 0ull; // lanes whose acceptance changed in this round
 #pragma unroll
             for (int j = 0; j < K; ++j) {
-                const double t = (double)(int)(cbv[j] - (uint32_t)npref[j]);
-                const uint64_t lt_ins = sse_ballot((double)rr1[j] * t < nb[j]);
-                const uint64_t lt_rem = sse_ballot(un[j] < t);
-                const uint64_t a = (lt_ins & insm[j]) | (lt_rem & remm[j]);
-                changed |= a != acc[j];
-                acc[j] = a;
-                wtot += popc64(a & insm[j]) - popc64(a & remm[j]);
+                const int t = (int)(cbv[j] - (uint32_t)npref[j]);
+                uint64_t ai, ar;
+                if constexpr (F64) {
+                    const double td = (double)t;
+                    ai = sse_ballot((double)rr1[j] * td < nb[j]) & insm[j];
+                    ar = sse_ballot(un[j] < td) & remm[j];
+                } else {
+                    ai = sse_ballot(sse_accept_insert(rr1[j], (uint32_t)t, ((uint64_t)chi[j] << 32) | clo[j]));
+                    ar = sse_ballot(sse_accept_remove(t, thr[j]));
+                }
+                diff |= (ai ^ acci[j]) | (ar ^ accr[j]);
+                acci[j] = ai; accr[j] = ar;
+                wtot += popc64(ai) - popc64(ar);
             }
-            const int buf = gr & 1;
-            if (lane == 0) { LDSI(L.o_tot, buf * W + wave) = wtot; LDSW(L.o_chg, buf * W + wave) = changed ? 1u : 0u; }
+            // one word per wave and round: every wave reads the four of them back at once
+            const bool changed = first | (diff != 0ull);
+            const uint32_t xch = F.o_xch + 4u * (gr & 1u);
+            if (lane == 0) LDSW(xch, wave) = ((uint32_t)wtot << 1) | (changed ? 1u : 0u);
             __syncthreads();
             if (first) {
                 // this tile's off-diagonal ops -> copies of the earlier waves (every reader of this tile is done); the next
                 // tile's -> copies of the later waves (visible behind the next barrier, before anybody decodes that tile)
-                propagate(word, m_earlier);
-                if (tile + 1 < ntiles) propagate(wnext, m_later);
+                propagate(vcur, m_earlier);
+#pragma unroll
+                for (int j = 0; j < K; ++j) vnext[j] = decode(wnext[j]);
+                if (tile + 1 < ntiles) propagate(vnext, m_later);
             }
-            base = 0; tot_all = 0; uint32_t anychg = 0;
+            const uint4 xw = *reinterpret_cast<const uint4 *>(&lds_raw[xch]);
+            const int x4[W] = {__builtin_amdgcn_readfirstlane((int)xw.x), __builtin_amdgcn_readfirstlane((int)xw.y),
+                               __builtin_amdgcn_readfirstlane((int)xw.z), __builtin_amdgcn_readfirstlane((int)xw.w)};
+            base = 0; tot_all = 0;
 #pragma unroll
             for (int w2 = 0; w2 < W; ++w2) {
-                const int t = __builtin_amdgcn_readfirstlane(LDSI(L.o_tot, buf * W + w2));
+                const int t = x4[w2] >> 1;
                 if (w2 < wave) base += t;
                 tot_all += t;
-                anychg |= (uint32_t)__builtin_amdgcn_readfirstlane((int)LDSW(L.o_chg, buf * W + w2)) & 1u;
             }
+            const uint32_t anychg = (uint32_t)(x4[0] | x4[1] | x4[2] | x4[3]) & 1u;
             gr++;
             if (!first && !anychg) break;
             first = false;
             int run = n_start + base;
 #pragma unroll
             for (int j = 0; j < K; ++j) {
-                const uint64_t im = acc[j] & insm[j], rm = acc[j] & remm[j];
+                const uint64_t im = acci[j], rm = accr[j];
                 const int ci = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(im >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)im, (uint32_t)run));
                 const int cr = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, 0u));
                 npref[j] = ci - cr;
@@ -275,25 +317,26 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
             }
         }
         // ---- commit ----
-        int dn = 0, dtr = 0;
+        const int dn = wtot; // of the last round: the masks it left are the accepted ones
+        int dtr = 0;
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            const uint32_t fw = sel64(acc[j], neww[j], word[j]);
+            const uint32_t fw = sel64(acci[j] | accr[j], neww[j], word[j]);
             row_st(ops, pbase + (uint32_t)(j * 64), fw);
-            const uint64_t im = acc[j] & insm[j], rm = acc[j] & remm[j];
             const uint64_t trm = sse_ballot((ent[j] >> 30) == SSE_FAST_CLASS_G); // the bond at stake is a transverse-field bond
-            dn += popc64(im) - popc64(rm);
-            dtr += popc64(im & trm) - popc64(rm & trm);
+            dtr += popc64(acci[j] & trm) - popc64(accr[j] & trm);
         }
         ntrans += dtr;
         if (lane == 0 && (dtr | dn)) { // the 64*K slots of a wave's share of a tile lie inside one chunk
-            const uint32_t ch = (tile * TS + (uint32_t)(wave * 64 * K)) / B.CH;
             if (dn) atomicAdd(&LDSW(L.o_chn, ch), (uint32_t)dn);
             if (dtr) atomicAdd(&LDSW(L.o_chtr, ch), (uint32_t)dtr);
         }
         n_start += tot_all;
+        // chunk of this wave's share of the next tile (TS is a few chunks at the most: CH is a multiple of 256)
+        chpos += TS;
+        while (chpos >= B.CH) { chpos -= B.CH; ch++; }
     }
-    __syncthreads();
+    __syncthreads(); // (also: every wave has read the last round's exchange words, which share their LDS with o_tot)
     if (lane == 0) LDSI(L.o_tot, wave) = ntrans;
     __syncthreads();
     int dt = 0;
@@ -306,7 +349,8 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
 
 // One launch = the diagonal sweep (and, if asked for, the directed loop behind it) of every replica: the first of the two
 // launches of a timestep (isingmc_hip.hip run()), for the geometry above.  PHASE only tags the symbol (see sweep_kernel).
-template <int K, int PHASE>
+// F64: the rounds of the acceptance rule in f64 (batches whose capacity exceeds SSE_ACCEPT_MAX_DEN, launch_sweep_fast).
+template <int K, int PHASE, bool F64>
 __global__ __launch_bounds__(256, 4) void sweep_fast_kernel(DevBatch B, SweepArgs A) {
     constexpr int W = 4, NT = W * 64;
     Lds<W> L;
@@ -325,7 +369,8 @@ __global__ __launch_bounds__(256, 4) void sweep_fast_kernel(DevBatch B, SweepArg
         const double beta_nb = beta * (double)B.Nb;
         const double w = tid == 0 ? B.wJ : (tid == 1 ? B.gamma : (tid == 2 ? B.wh : 0.0));
         const double num = beta_nb * w; // the general pass' nbond, then scaled by exact powers of two
-        *reinterpret_cast<double *>(&lds_raw[F.o_nb + 4u * (uint32_t)tid]) = num * 4294967296.0;
+        if constexpr (F64) *reinterpret_cast<double *>(&lds_raw[F.o_nb + 4u * (uint32_t)tid]) = num * 4294967296.0;
+        else *reinterpret_cast<uint64_t *>(&lds_raw[F.o_nb + 4u * (uint32_t)tid]) = sse_accept_insert_const(num);
         *reinterpret_cast<double *>(&lds_raw[F.o_nb + 4u * (uint32_t)tid + 2u]) = num * (1.0 / 4294967296.0);
     }
     __syncthreads();
@@ -340,7 +385,7 @@ __global__ __launch_bounds__(256, 4) void sweep_fast_kernel(DevBatch B, SweepArg
         if (err) break;
         if (A.domask & SSE_DO_DIAG) {
             const Rng rng = make_rng(B, r, epoch);
-            diagonal_fast<K>(B, L, F, r, rng, beta, M, n, ntrans, gr, step == 0 ? fbmask : 0u);
+            diagonal_fast<K, F64>(B, L, F, r, rng, beta, M, n, ntrans, gr, step == 0 ? fbmask : 0u);
             epoch++;
             a5 += M;
             if (A.domask & SSE_DO_GROW) { // qmc_ising.rs:786, qmc_runner.rs:197

@@ -49,6 +49,17 @@ __device__ __forceinline__ void lds_cas32(uint32_t addr, uint32_t expect, uint32
     (void)__hip_atomic_compare_exchange_strong((sse_lds_u32 *)(uintptr_t)addr, &expect, val, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// A 16-bit LDS load used as a 32-bit value: ds_read_u16 clears the upper half of its register.  The empty asm hides the origin of
+// the value, so the compiler neither compares in 16 bits nor re-masks a second, zero-extended copy of it.
+__device__ __forceinline__ uint32_t lds_ld16(uint32_t addr) {
+    uint32_t v = LDS16B(addr);
+    asm("" : "+v"(v));
+    return v;
+}
+// word of o_misc that the lanes of a predicated LDS store with nothing to store are pointed at (sse_fast.hip.h, "Predicated LDS
+// stores and atomics are written branch-free"): this kernel uses words 0-2 of the 16, nothing ever reads this one
+#define SSE_CL_MISC_DUMMY 12u
+
 struct ClLds { // word offsets into lds_raw
     uint32_t o_tab;    // [Nb + 1]   packed bond entries, at word 0 (the index is the op word >> 4)
     uint32_t o_state;  // [nwords]
@@ -86,14 +97,6 @@ static inline __host__ __device__ bool cl_ids_fit(uint32_t N, uint32_t S, uint32
 static inline __host__ __device__ uint32_t cl_list_cap(uint32_t N, uint32_t S) {
     const size_t tab = (size_t)SSE_CLW * (N + 1), bits = ((size_t)S + 31) / 32;
     return bits < tab ? (uint32_t)(2 * (tab - bits)) : 0u;
-}
-
-__device__ __forceinline__ uint32_t cl_entry(const DevBatch &B, uint32_t b, uint32_t ce) {
-    if (b < B.E) return (ce & SSE_CE_VAR_MASK) | (((ce >> 15) & SSE_CE_VAR_MASK) << 13) | SSE_CLE_TWO;
-    const uint32_t s1 = b - B.E;
-    if (s1 < B.N) return s1 | (s1 << 13) | SSE_CLE_CUT;
-    const uint32_t v = s1 - B.N;
-    return v | (v << 13) | SSE_CLE_LONG;
 }
 
 // union on trees that only the calling wave touches (see uf_union_wave); returns the surviving root.  Both walks to the roots
@@ -151,14 +154,25 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     SSE_STAMP_INIT;
     // ---- initialisation ----
     for (uint32_t i = tid; i < nwords; i += NT) { LDSW(L.o_state, i) = B.state[(size_t)r * nwords + i]; LDSW(L.o_touch, i) = 0u; }
-    for (uint32_t i = tid; i <= B.Nb; i += NT)
-        LDSW(L.o_tab, i) = i == 0u ? (N | (N << 13)) : cl_entry(B, i - 1u, i - 1u < B.E ? B.edges_compact[i - 1u] : 0u);
+    // bond entries, one loop per kind of bond (bonds [0, E): two-site, [E, E + N): transverse field, then the longitudinal ones): entry 1 + b of bond b, entry 0 = the empty slot
+    if (tid == 0) LDSW(L.o_tab, 0u) = N | (N << 13);
+    for (uint32_t i = tid; i < B.E; i += NT) {
+        const uint32_t ce = B.edges_compact[i];
+        LDSW(L.o_tab, 1u + i) = (ce & SSE_CE_VAR_MASK) | (((ce >> 15) & SSE_CE_VAR_MASK) << 13) | SSE_CLE_TWO;
+    }
+    for (uint32_t v = tid; v < N; v += NT) {
+        const uint32_t vv = v | (v << 13);
+        LDSW(L.o_tab, 1u + B.E + v) = vv | SSE_CLE_CUT;
+        if (1u + B.E + N + v <= B.Nb) LDSW(L.o_tab, 1u + B.E + N + v) = vv | SSE_CLE_LONG;
+    }
     for (uint32_t i = tid; i < 2 * SSE_MAX_CHUNKS; i += NT) LDSW(L.o_chn, i) = B.chunks[(size_t)r * 2 * SSE_MAX_CHUNKS + i];
     if (tid == 0) { LDSW(L.o_misc, MISC_NCLUST) = 0u; LDSW(L.o_misc, MISC_ANYFROZEN) = 0u; LDSW(L.o_misc, MISC_LOOP_A) = 0u; }
     // per-wave tables: the segment a variable is in when the wave's range begins = the placeholder id of (wave, variable)
-    for (uint32_t i = tid; i < (uint32_t)W * (N + 1u); i += NT) {
-        const uint32_t w2 = i / (N + 1u), v = i - w2 * (N + 1u);
-        LDSW(L.o_ent, i) = v == N ? S : (w2 == 0u ? v : N + C + (w2 - 1u) * N + v); // (the dummy variable of empty slots carries the null id S)
+    // (wave w fills table w: the variable is the running index, the placeholder base is a scalar)
+    {
+        const uint32_t tb = L.o_ent + (uint32_t)wave * (N + 1u), id0 = wave == 0 ? 0u : N + C + (uint32_t)(wave - 1) * N;
+        for (uint32_t v = (uint32_t)lane; v < N; v += 64u) LDSW(tb, v) = id0 + v;
+        if (lane == 0) LDSW(tb, N) = S; // (the dummy variable of empty slots carries the null id S)
     }
     for (uint32_t i = tid; i < S / 2u + 1u; i += NT) LDSW(L.o_parent, i) = (2u * i) | ((2u * i + 1u) << 16); // parent[i] = i for i <= S
     if constexpr (HAS_LONG) for (uint32_t i = tid; i < (S + 31u) / 32u; i += NT) uf.bits_clear(i);
@@ -176,6 +190,9 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     const uint32_t lds0 = (uint32_t)(uintptr_t)(sse_lds_u32 *)lds_raw; // LDS address of the dynamic region
     const uint32_t ent_b = lds0 + 4u * (L.o_ent + (uint32_t)wave * (N + 1u)); // LDS address of this wave's table
     const uint32_t par_b = lds0 + 4u * L.o_parent;
+    // Predicated LDS stores of the scan and of the union block are written branch-free (see SSE_CL_MISC_DUMMY): an address select
+    // on the mask the code has anyway, instead of an exec save / restore around every store
+    const uint32_t dummy_b = vgpr_copy_u32(lds0 + 4u * (L.o_misc + SSE_CL_MISC_DUMMY));
 
     SSE_STAMP(0);
     // ---- build: label every leg, union through the two-site ops (cluster.rs:193-271) ----
@@ -225,7 +242,8 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                 const uint32_t kown = __builtin_amdgcn_mbcnt_hi((uint32_t)(cutm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cutm, 0u));
                 // In-row ordering: the cut lanes publish 1 + their rank inside the row in the marker byte of their variable's entry,
                 // every lane reads once; a cut on the leg's variable precedes the lane iff its rank is below the lane's own count.
-                if (iscut) LDS8B(aa + 2u) = (uint8_t)(kown + 1u);
+                const uint32_t acut = iscut ? aa : dummy_b; // the entry a cut lane writes: marker now, its new segment below
+                LDS8B(acut + 2u) = (uint8_t)(kown + 1u);
                 SSE_WAVE_FENCE();
                 const uint32_t ea = LDS32B(aa), ec = LDS32B(ac);
                 LDS8B(aa + 3u) = (uint8_t)1; LDS8B(ac + 3u) = (uint8_t)1; // touched flag (byte 3): plain stores with an immediate offset, nothing waits for them
@@ -236,7 +254,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                     seg_a = ((qa - 1u) < kown) ? cutnext + (qa - 1u) : seg_a; // qa == 0: no cut on the variable in this row
                     seg_c = ((qc - 1u) < kown) ? cutnext + (qc - 1u) : seg_c;
                     SSE_WAVE_FENCE();
-                    if (iscut) LDS32B(aa) = (cutnext + kown) | SSE_CL_TOUCHED; // the segment the cut opens; clears the marker
+                    LDS32B(acut) = (cutnext + kown) | SSE_CL_TOUCHED; // the segment the cut opens; clears the marker
                 } else { // two cuts of this row on one variable (rare): lane order decides
                     const uint32_t va = e[j] & 0x1FFFu, vc = (e[j] >> 13) & 0x1FFFu;
                     bool lastcut = iscut;
@@ -253,7 +271,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                         idL++;
                     }
                     SSE_WAVE_FENCE();
-                    if (iscut) LDS8B(aa + 2u) = (uint8_t)0;
+                    LDS8B(acut + 2u) = (uint8_t)0;
                     if (iscut & lastcut) LDS16B(aa) = (uint16_t)(cutnext + kown); // the last cut wins
                     SSE_WAVE_FENCE();
                 }
@@ -283,12 +301,13 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                     // SSE_CL_FIND_LEVELS hops up from each representative, straight-line (a representative is a root or close to one: it was
                     // a root when it was written); nodes found below a root are re-pointed at it on the way (they are not roots, so
                     // no link of this batch can be undone by that)
-                    const uint32_t pa = LDS16B(par_b + 2u * ua[j]), pc = LDS16B(par_b + 2u * uc[j]);
-                    uint32_t ga = LDS16B(par_b + 2u * pa), gc = LDS16B(par_b + 2u * pc);
-                    uint32_t ta = LDS16B(par_b + 2u * ga), tc = LDS16B(par_b + 2u * gc);
+                    const uint32_t xa = par_b + 2u * ua[j], xc = par_b + 2u * uc[j]; // (each parent address: one shift-and-add)
+                    const uint32_t pa = lds_ld16(xa), pc = lds_ld16(xc);
+                    uint32_t ga = lds_ld16(par_b + 2u * pa), gc = lds_ld16(par_b + 2u * pc);
+                    uint32_t ta = lds_ld16(par_b + 2u * ga), tc = lds_ld16(par_b + 2u * gc);
 #pragma unroll
                     for (int lv = 3; lv < SSE_CL_FIND_LEVELS; ++lv) { // (further levels: the candidate root moves one hop up)
-                        const uint32_t na = LDS16B(par_b + 2u * ta), nc = LDS16B(par_b + 2u * tc);
+                        const uint32_t na = lds_ld16(par_b + 2u * ta), nc = lds_ld16(par_b + 2u * tc);
                         ga = ta; gc = tc; ta = na; tc = nc;
                     }
                     const bool found = (ta == ga) & (tc == gc); // ga / gc are roots (also when the chain is shorter: a root is its own parent)
@@ -296,11 +315,12 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                     const bool link = found & differ;
                     uint32_t lo = min(ga, gc);
                     const uint32_t hi = max(ga, gc);
-                    if (found & (pa != ga)) { LDS16B(par_b + 2u * ua[j]) = (uint16_t)ga; }
-                    if (found & (pc != gc)) { LDS16B(par_b + 2u * uc[j]) = (uint16_t)gc; }
-                    if (link) LDS16B(par_b + 2u * hi) = (uint16_t)lo;
+                    const uint32_t xh = par_b + 2u * hi;
+                    LDS16B((found & (pa != ga)) ? xa : dummy_b) = (uint16_t)ga;
+                    LDS16B((found & (pc != gc)) ? xc : dummy_b) = (uint16_t)gc;
+                    LDS16B(link ? xh : dummy_b) = (uint16_t)lo;
                     SSE_WAVE_FENCE();
-                    const uint32_t chk = LDS16B(par_b + 2u * hi);
+                    const uint32_t chk = lds_ld16(xh);
 #ifdef SSE_CL_UNION_COUNTERS // (a diagnostic build of its own: the counters cost the union block a quarter of its time)
                     if (wave == 3) { // why rows reach the serial routine
                         const uint64_t nf = sse_ballot(!found), cf = sse_ballot(found & link & (chk != lo)), nd = sse_ballot(true);
@@ -531,11 +551,12 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
         }
     }
     // p=0 state follows the initial segment of each touched variable
-    for (uint32_t i = tid; i < nwords; i += NT) {
-        uint32_t x = 0;
-        const uint32_t t = LDSW(L.o_touch, i);
-        for (uint32_t j = 0; j < 32 && i * 32 + j < N; ++j) x |= (uf.get(i * 32 + j) & 1u) << j;
-        LDSW(L.o_state, i) ^= (x & t);
+    // (one variable per thread: a wave's ballot is two whole state words, lanes 0 and 1 take one each)
+    for (uint32_t v0 = (uint32_t)wave * 64u; v0 < N; v0 += NT) {
+        const uint32_t v = v0 + (uint32_t)lane;
+        const uint64_t fm = sse_ballot(v < N && (uf.get(v) & 1u) != 0u);
+        const uint32_t i = (v0 >> 5) + (uint32_t)lane;
+        if (lane < 2 && i < nwords) LDSW(L.o_state, i) ^= (lane ? (uint32_t)(fm >> 32) : (uint32_t)fm) & LDSW(L.o_touch, i);
     }
     __syncthreads();
     SSE_STAMP(5);
@@ -545,15 +566,17 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     // ---- free spins (qmc_ising.rs:780-784) ----
     if (A.domask & SSE_DO_FREE) {
         const Rng rngf = make_rng(B, r, epoch);
-        for (uint32_t i = tid; i < nwords; i += NT) {
-            const uint32_t t = LDSW(L.o_touch, i);
-            uint32_t s = LDSW(L.o_state, i);
-            for (uint32_t j = 0; j < 32 && i * 32 + j < N; ++j)
-                if (!((t >> j) & 1u)) {
-                    const uint4 o = rngf.draw(SSE_TAG_FREE, i * 32 + j);
-                    s = (s & ~(1u << j)) | ((o.x >> 31) << j);
-                }
-            LDSW(L.o_state, i) = s;
+        for (uint32_t v0 = (uint32_t)wave * 64u; v0 < N; v0 += NT) { // (same layout: an untouched variable draws, a touched one keeps its bit)
+            const uint32_t v = v0 + (uint32_t)lane;
+            const bool isfree = v < N && !((LDSW(L.o_touch, v >> 5) >> (v & 31u)) & 1u);
+            uint32_t bit = 0u;
+            if (isfree) bit = rngf.draw(SSE_TAG_FREE, v).x >> 31;
+            const uint64_t fm = sse_ballot(isfree), bm = sse_ballot(bit != 0u);
+            const uint32_t i = (v0 >> 5) + (uint32_t)lane;
+            if (fm != 0ull && lane < 2 && i < nwords) {
+                const uint32_t f = lane ? (uint32_t)(fm >> 32) : (uint32_t)fm, b = lane ? (uint32_t)(bm >> 32) : (uint32_t)bm;
+                LDSW(L.o_state, i) = (LDSW(L.o_state, i) & ~f) | b;
+            }
         }
         __syncthreads();
         epoch++;

@@ -99,6 +99,14 @@ static inline __host__ __device__ uint32_t cl_list_cap(uint32_t N, uint32_t S) {
     return bits < tab ? (uint32_t)(2 * (tab - bits)) : 0u;
 }
 
+// lane `l` (a constant) of v := the wave-uniform x; the other lanes keep their value
+// This clang has no builtin for it, so the LLVM intrinsic is declared by name.  Not inline assembly: the compiler must see the
+// instruction, because on gfx950 a VALU read of a scalar register needs two wait states behind the VALU write of it, and the
+// v_cmp of a ballot can stand right in front of the v_writelane that reads its mask (the compiler then inserts the s_nop or
+// schedules around it).  The lane select is a constant once the row loop is unrolled: an immediate of the instruction.
+extern "C" __device__ int sse_cl_llvm_writelane(int, int, int) __asm("llvm.amdgcn.writelane.i32");
+__device__ __forceinline__ uint32_t cl_writelane(uint32_t v, uint32_t x, int l) { return (uint32_t)sse_cl_llvm_writelane((int)x, l, (int)v); }
+
 // union on trees that only the calling wave touches (see uf_union_wave); returns the surviving root.  Both walks to the roots
 // advance together (two independent LDS reads per step instead of two walks one after the other), and the two start nodes are
 // re-pointed at their roots (they are not roots themselves when they differ from them)
@@ -204,9 +212,12 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     {
         uint32_t cutnext = N + cutbase; // id of the next cut of this range
         uint32_t wnext[K], idpend[K / 2];
-        uint4 mpend[K]; // deferred flips: the cut mask and the two-site mask of every row (the same in all lanes; lane 0 stores them)
+        // deferred flips: the cut mask and the two-site mask of every row are wave-uniform; dword c of row j's uint4 is collected in
+        // lane 4 j + c of one register (v_writelane) and lanes 0 .. 4 K - 1 store the tile's masks with one dword store each
+        uint32_t mpend = 0u;
+        uint32_t *mskw = reinterpret_cast<uint32_t *>(msk);
 #pragma unroll
-        for (int j = 0; j < K; ++j) { wnext[j] = row_ld(ops, pbeg + (uint32_t)(j * 64 + lane)); mpend[j] = make_uint4(0u, 0u, 0u, 0u); }
+        for (int j = 0; j < K; ++j) wnext[j] = row_ld(ops, pbeg + (uint32_t)(j * 64 + lane));
 #pragma unroll
         for (int j = 0; j < K / 2; ++j) idpend[j] = 0u;
         uint32_t pprev = pbeg;
@@ -221,10 +232,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                 // whole tile to complete, not for stores issued a moment ago (first tile: a dummy store that the next one overwrites)
 #pragma unroll
                 for (int j = 0; j < K; j += 2) if (!SSE_DBG(B, 1u)) row_st(ids, (pprev >> 1) + (uint32_t)(j * 32 + lane), idpend[j / 2]);
-                if (DEFER) { if (lane == 0) {
-#pragma unroll
-                    for (int j = 0; j < K; ++j) msk[(pprev >> 6) + (uint32_t)j] = mpend[j];
-                } }
+                if (DEFER) { if (lane < 4 * K) row_st(mskw, (pprev >> 6) * 4u + (uint32_t)lane, mpend); }
                 pprev = p0;
                 const uint32_t pn0 = p0 + TS < pend ? p0 + TS : p0;
 #pragma unroll
@@ -279,8 +287,11 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                     if (e[j] & SSE_CLE_LONG) uf.frozen_or(seg_a >> 5, 1u << (seg_a & 31)); // qmc_ising.rs:759-775
                 cutnext += (uint32_t)popc64(cutm);
                 if (DEFER) { // (without a longitudinal field every op that is not a cut is a two-site op: the cut mask alone will do)
-                    mpend[j].x = (uint32_t)cutm; mpend[j].y = (uint32_t)(cutm >> 32);
-                    if constexpr (HAS_LONG) { const uint64_t twom = sse_ballot((e[j] & SSE_CLE_TWO) != 0u); mpend[j].z = (uint32_t)twom; mpend[j].w = (uint32_t)(twom >> 32); }
+                    mpend = cl_writelane(mpend, (uint32_t)cutm, 4 * j); mpend = cl_writelane(mpend, (uint32_t)(cutm >> 32), 4 * j + 1);
+                    if constexpr (HAS_LONG) { // (without one, dwords 2 and 3 of a row stay 0)
+                        const uint64_t twom = sse_ballot((e[j] & SSE_CLE_TWO) != 0u);
+                        mpend = cl_writelane(mpend, (uint32_t)twom, 4 * j + 2); mpend = cl_writelane(mpend, (uint32_t)(twom >> 32), 4 * j + 3);
+                    }
                 }
                 ua[j] = seg_a; uc[j] = seg_c; // (one-variable ops and empty slots: seg_c == seg_a, no union below)
             }
@@ -342,10 +353,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
         if (pbeg < pend) {
 #pragma unroll
             for (int j = 0; j < K; j += 2) row_st(ids, (pprev >> 1) + (uint32_t)(j * 32 + lane), idpend[j / 2]);
-            if (DEFER) { if (lane == 0) {
-#pragma unroll
-                for (int j = 0; j < K; ++j) msk[(pprev >> 6) + (uint32_t)j] = mpend[j];
-            } }
+            if (DEFER) { if (lane < 4 * K) row_st(mskw, (pprev >> 6) * 4u + (uint32_t)lane, mpend); }
         }
     }
     __syncthreads();
@@ -367,30 +375,27 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     }
     __syncthreads();
     SSE_STAMP(2);
-    // ---- flatten: parent[i] := exact root; frozen marks move to the roots ----
-    for (uint32_t i = tid; i < S; i += NT) {
-        const uint32_t root = uf_find_ro(uf, i);
-        uf.set(i, root);
-        if constexpr (HAS_LONG)
-            if ((uf.frozen_get(i >> 5) >> (i & 31)) & 1u) { uf.froot_or(root >> 5, 1u << (root & 31)); LDSW(L.o_misc, MISC_ANYFROZEN) = 1u; }
-    }
-    // the per-wave tables are dead: their words now hold the flip bits (S bits) and, behind them, the list of roots (u16)
+    // ---- flatten: parent[i] := exact root; frozen marks move to the roots.  The same pass lists the roots: the per-wave tables are
+    // dead behind the barrier above, their words now hold the flip bits (S bits) and, behind them, the list of roots (u16); the
+    // touched bits are complete as well.  A root's entry is its own id from the joins on and nobody rewrites it, so "my find ends
+    // at myself" is final here (only exact roots are ever stored in this pass: uf_find_ro) ----
     const uint32_t o_bits = L.o_ent, o_list = L.o_ent + (S + 31u) / 32u;
     const uint32_t list_cap = cl_list_cap(N, S);
-    for (uint32_t i = tid; i < (S + 31u) / 32u; i += NT) LDSW(o_bits, i) = 0u;
-    __syncthreads();
-    SSE_STAMP(3);
-    // ---- coins: one Philox draw per root (= per cluster, keyed by the canonical label = smallest id), cluster.rs:111-137 ----
-    const Rng rng = make_rng(B, r, epoch);
     uint32_t myclusters = 0;
     for (uint32_t i0 = 0; i0 < S; i0 += NT) { // whole waves iterate together (ballot below)
         const uint32_t i = i0 + tid;
         const bool inr = i < S;
-        const uint32_t root = inr ? uf.get(i) : 0xFFFFFFFFu;
-        const bool isroot = inr & (root == i);
-        if (isroot & (i < N + C)) {
-            const bool touched = (i >= N) || ((LDSW(L.o_touch, i >> 5) >> (i & 31)) & 1u);
-            if (touched) myclusters++;
+        bool isroot = false;
+        if (inr) {
+            const uint32_t root = uf_find_ro(uf, i);
+            uf.set(i, root);
+            if constexpr (HAS_LONG)
+                if ((uf.frozen_get(i >> 5) >> (i & 31)) & 1u) { uf.froot_or(root >> 5, 1u << (root & 31)); LDSW(L.o_misc, MISC_ANYFROZEN) = 1u; }
+            isroot = root == i;
+            if (isroot & (i < N + C)) {
+                const bool touched = (i >= N) || ((LDSW(L.o_touch, i >> 5) >> (i & 31)) & 1u);
+                if (touched) myclusters++;
+            }
         }
         const uint64_t m = sse_ballot(isroot);
         if (m) {
@@ -401,7 +406,11 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
             if (isroot && pos < list_cap) LDSH(o_list, pos) = (uint16_t)i;
         }
     }
+    for (uint32_t i = tid; i < (S + 31u) / 32u; i += NT) LDSW(o_bits, i) = 0u;
     __syncthreads();
+    SSE_STAMP(3);
+    // ---- coins: one Philox draw per root (= per cluster, keyed by the canonical label = smallest id), cluster.rs:111-137 ----
+    const Rng rng = make_rng(B, r, epoch);
     const uint32_t nroots = LDSW(L.o_misc, MISC_LOOP_A);
     if (nroots <= list_cap) { // uniform: every thread read the same counter
         for (uint32_t k = tid; k < nroots; k += NT) {

@@ -12,6 +12,10 @@ Parts are found by shape, not by label (labels move with every change):
     it and that branch's target);
   * initialisation loops: every innermost loop in front of the kernel's first barrier, in program order (state and touch words,
     bond entries, chunk counts, per-wave tables, parent table);
+  * loops between the scan and the apply pass (range joins, flatten, coins): every outermost barrier-free loop behind the build
+    loop and in front of the first apply loop, in program order, named by what it holds: a returning compare-and-swap
+    (ds_cmpst_rtn: the range joins), a returning add (ds_add_rtn: the root list's append), Philox rounds (the coin draws), LDS
+    reads and writes only (flip bits, state tail), writes only (zeroing);
   * apply loops: the innermost loops behind the build loop that hold global loads, global stores and LDS reads and no Philox:
     the deferred one stores bytes (global_store_byte), the in-place one dwords.
 Counts are of the text of a span, rarely taken paths included.  A static figure; executed counts come from the SQ_INSTS_*
@@ -100,6 +104,18 @@ def main():
     for k, s in enumerate(init):
         row(f"initialisation loop {k}", ops[s[0]:s[1]])
     row("initialisation, all loops", [o for s in init for o in ops[s[0]:s[1]]])
+    # between the scan and the apply pass: outermost barrier-free loops, in program order
+    is_apply = lambda s: innermost(s) and has(s, "global_load") and has(s, "global_store") and has(s, "ds_read") and not philox(s)
+    first_apply = min((s[0] for s in spans if s[0] >= build[1] and is_apply(s)), default=len(ops))
+    post = [s for s in spans if build[1] <= s[0] and s[1] <= first_apply and not has(s, "s_barrier") and not has(s, "global_load")]
+    post = [s for s in post if not any(t != s and t[0] <= s[0] and s[1] <= t[1] for t in post)]
+    for s in post:
+        traits = [n for n, pre in (("joins", "ds_cmpst_rtn"), ("root list", "ds_add_rtn")) if has(s, pre)] + (["coins"] if philox(s) else [])
+        if not traits:
+            traits = ["LDS reads and writes"] if has(s, "ds_read") else ["writes only"]
+        row("post-scan loop: " + " + ".join(traits), ops[s[0]:s[1]])
+    row("post-scan loops, all", [o for s in post for o in ops[s[0]:s[1]]])
+    print(f"  barriers in the kernel: {ops.count('s_barrier')}, instructions in the kernel: {len(ops)}")
     for s in spans:
         if s[0] >= build[1] and innermost(s) and has(s, "global_load") and has(s, "global_store") and has(s, "ds_read") and not philox(s):
             row("apply loop, deferred (one tile)" if has(s, "global_store_byte") else "apply loop, in place (one tile)", ops[s[0]:s[1]])

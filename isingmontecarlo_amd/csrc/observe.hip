@@ -3,19 +3,13 @@
 namespace sse {
 hipError_t launch_record_series(hipStream_t stream, const uint32_t *rec, uint32_t R, uint32_t nwords, uint32_t T, const ObsGroups &G, uint32_t *out) {
     const size_t lds = 4 * obs_series_lds_words(nwords);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&record_series_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(record_series_kernel, dim3((T + OBS_TILE - 1) / OBS_TILE, R), dim3(OBS_SERIES_WAVES * 64), lds, stream, rec, R, nwords, T, G, out);
-    return hipGetLastError();
+    return launch_lds(record_series_kernel, dim3((T + OBS_TILE - 1) / OBS_TILE, R), dim3(OBS_SERIES_WAVES * 64), lds, stream, rec, R, nwords, T, G, out);
 }
 hipError_t launch_bit_autocorr(hipStream_t stream, const uint32_t *series, uint32_t R, uint32_t ngroups, uint32_t T, double *out) {
     const size_t lds = 4 * (obs_autocorr_lds_words(T) + 2);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bit_autocorr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
     // OBS_LAGS lags per lane: whole waves for a quarter of the lags while the series is short, one pass per 4096 lags when it is long
     uint32_t threads = ((T + OBS_LAGS - 1u) / OBS_LAGS + 63u) / 64u * 64u;
     if (threads > OBS_MAX_THREADS) threads = OBS_MAX_THREADS;
-    hipLaunchKernelGGL(bit_autocorr_kernel, dim3(R), dim3(threads), lds, stream, series, ngroups, T, out);
-    return hipGetLastError();
+    return launch_lds(bit_autocorr_kernel, dim3(R), dim3(threads), lds, stream, series, ngroups, T, out);
 }
 } // namespace sse

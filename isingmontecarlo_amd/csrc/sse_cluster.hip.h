@@ -2,7 +2,7 @@
 // instruction count (round 3).
 //
 // Same algorithm, same ids, same Philox counters and bit-identical results as sse::cluster_pass<16, K, CL = true, UF_GLOBAL = false>
-// (sse_device.hip.h, which stays the general implementation: every other geometry, HBM union-find, HBM tables, generic
+// (sse_cluster_pass.hip.h, which stays the general implementation: every other geometry, HBM union-find, HBM tables, generic
 // interactions).  Reference: ClusterUpdater::flip_each_cluster_rng (qmc_traits/cluster.rs:36-172) + expand_whole_cluster
 // (:193-271), the longitudinal weight function of qmc_ising.rs:759-775, then the free-spin step and the sampling of
 // qmc_ising.rs:780-786 / qmc_stepper.rs:149-161.
@@ -25,6 +25,7 @@
 // Replicas whose ids do not fit the LDS union-find of this launch (or that hold no op / no cut) are left untouched and flagged
 // in B.aux; the host follows up with the general kernel restricted to flagged replicas (isingmc_hip.hip run()).
 #pragma once
+#include "sse_cluster_pass.hip.h" // the union-find and free_spin_pass
 
 namespace sse {
 

@@ -20,6 +20,7 @@
 // replica, Metropolis rule, two launches per timestep.
 #pragma once
 #include "sse_accept.h"
+#include "sse_loop.hip.h"
 
 namespace sse {
 
@@ -30,13 +31,6 @@ namespace sse {
 #define SSE_FAST_CLASS_J 0u
 #define SSE_FAST_CLASS_G 1u
 #define SSE_FAST_CLASS_H 2u
-
-// v_cndmask on a wave mask held in scalar registers: mask bit of the lane set ? a : b
-__device__ __forceinline__ uint32_t sel64(uint64_t mask, uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(mask));
-    return r;
-}
 
 // bitfield insert: (a & mask) | (b & ~mask)
 // (as an instruction: written in C the optimiser turns it back into compare + select, the very thing it is here to avoid)

@@ -12,7 +12,7 @@
 //                          which is the reference's centred, unit-norm autocorrelation (autocorrelations.rs:99-133)
 //                          with every step up to the one division in integers.
 #pragma once
-#include "sse_device.hip.h" // ObsGroups, the OBS_* constants, the LDS sizes and the launch prototypes
+#include "sse_launch.h" // ObsGroups, the OBS_* constants, the LDS sizes and the launch prototypes
 
 namespace sse {
 

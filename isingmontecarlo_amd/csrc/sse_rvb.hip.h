@@ -1,4 +1,4 @@
-// sse_rvb.hip.h — resonating-valence-bond update on gfx950 (included by sse_device.hip.h).
+// sse_rvb.hip.h — resonating-valence-bond update on gfx950 (sse::sweep_kernel, sse_sweep.hip.h; as two launches: sse_rvb_split.hip.h).
 //
 // Reference: RvbUpdater::rvb_update_with_ising_weight (src/sse/qmc_traits/rvb.rs:88-290) with build_cluster
 // (:1054-1123), find_overlapping_starts (:1125-1158), find_constants (:1160-1187), calculate_flip_prob
@@ -16,6 +16,7 @@
 // and one lane then replays the (short) sequential rule over the gathered list.  All scratch lives in the LDS
 // region that the cluster pass uses for its union-find (the two passes never overlap).
 #pragma once
+#include "sse_core.hip.h"
 
 namespace sse {
 

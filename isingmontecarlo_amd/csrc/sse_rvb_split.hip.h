@@ -1,4 +1,4 @@
-// sse_rvb_split.hip.h — the RVB sweep as two launches (included by sweep_rvb.hip after sse_device.hip.h).
+// sse_rvb_split.hip.h — the RVB sweep as two launches (instantiated by sweep_rvb.hip).
 //
 // Reference: RvbUpdater::rvb_update_with_ising_weight (src/sse/qmc_traits/rvb.rs:88-290); the pieces are those of
 // sse_rvb.hip.h.  The growth of an attempt (start, build_cluster, sub-variables, toggles, windows: rvb.rs:88-232,
@@ -15,6 +15,7 @@
 //
 // Results are those of rvb_pass bit for bit (same functions, same draws).
 #pragma once
+#include "sse_rvb.hip.h"
 
 namespace sse {
 

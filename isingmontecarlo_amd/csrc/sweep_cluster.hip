@@ -1,14 +1,11 @@
 // Instantiations of sse::cluster_kernel (sse_cluster.hip.h): the cluster-update launch of the headline geometry.
 #include "../../include/isingmc_hip.h"
-#include "sse_device.hip.h"
 #include "sse_cluster.hip.h"
+#include "sse_launch.h"
 namespace sse {
 template <int K, bool HL, int PHASE>
 static hipError_t launch_cluster_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&cluster_kernel<K, HL, PHASE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((cluster_kernel<K, HL, PHASE>), dim3(B.R), dim3(SSE_CLW * 64), c.lds_bytes, c.stream, B, A);
-    return hipGetLastError();
+    return launch_lds(cluster_kernel<K, HL, PHASE>, dim3(B.R), dim3(SSE_CLW * 64), c.lds_bytes, c.stream, B, A);
 }
 size_t cluster_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) { ClLds L; L.carve(N, nwords, Nb, ufcap, has_long); return L.end; }
 bool cluster_ids_fit(uint32_t N, uint32_t S, uint32_t ufcap) { return cl_ids_fit(N, S, ufcap); }

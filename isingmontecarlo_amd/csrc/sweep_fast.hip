@@ -1,12 +1,10 @@
 // Instantiations of sse::sweep_fast_kernel (sse_fast.hip.h): the diagonal-pass launch of the headline geometry.
-#include "sse_device.hip.h"
+#include "sse_fast.hip.h"
+#include "sse_launch.h"
 namespace sse {
 template <int K, int PHASE, bool F64>
 static hipError_t launch_fast_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_fast_kernel<K, PHASE, F64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((sweep_fast_kernel<K, PHASE, F64>), dim3(B.R), dim3(256), c.lds_bytes, c.stream, B, A);
-    return hipGetLastError();
+    return launch_lds(sweep_fast_kernel<K, PHASE, F64>, dim3(B.R), dim3(256), c.lds_bytes, c.stream, B, A);
 }
 hipError_t launch_sweep_fast(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     if (c.W != 4 || c.mode != SSE_MODE_LDS_EDGES) return hipErrorInvalidValue;

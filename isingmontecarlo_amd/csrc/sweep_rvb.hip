@@ -1,20 +1,14 @@
 // Instantiations of sse::rvb_grow_kernel / sse::rvb_main_kernel (sse_rvb_split.hip.h): the RVB sweep as two launches.
-#include "sse_device.hip.h"
+#include "sse_launch.h"
 #include "sse_rvb_split.hip.h"
 namespace sse {
 template <bool CL>
 static hipError_t launch_grow_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rvb_grow_kernel<CL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((rvb_grow_kernel<CL>), dim3(B.R), dim3(1024), c.lds_bytes, c.stream, B, A);
-    return hipGetLastError();
+    return launch_lds(rvb_grow_kernel<CL>, dim3(B.R), dim3(1024), c.lds_bytes, c.stream, B, A);
 }
 template <int W, bool CL>
 static hipError_t launch_main_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rvb_main_kernel<W, CL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((rvb_main_kernel<W, CL>), dim3(B.R), dim3(W * 64), c.lds_bytes, c.stream, B, A);
-    return hipGetLastError();
+    return launch_lds(rvb_main_kernel<W, CL>, dim3(B.R), dim3(W * 64), c.lds_bytes, c.stream, B, A);
 }
 uint32_t rvb_grow_table_start(const DevBatch &B, uint32_t ledges) { Lds<16> L; RvbLds R; L.carve(B.N, B.nwords, 0u, ledges, 0u); rvb_carve_grow<16>(R, L, B); return R.o_cps; }
 template <int W>

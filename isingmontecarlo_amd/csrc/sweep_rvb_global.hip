@@ -3,7 +3,7 @@
 // scratch (DevBatch::rvb_tbl) instead of LDS — any model, whatever its size or its number of constant ops (ISINGMC_CFG_RVB_GLOBAL_TABLES).
 // Two bond decodes: the LDS edge table (MODE 1) and the general 16-byte records (every other model: the host allocates the records of every
 // bond-table row in every mode, the +-J decode's batches included).
-#include "sse_device.hip.h"
+#include "sse_sweep.hip.h"
 namespace sse {
 hipError_t launch_rvb_global(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     if (!B.rvb_tbl || c.W != 16 || c.K != 4 || c.passes != SSE_PASSES_RVB_G) return hipErrorInvalidValue;

@@ -1,11 +1,12 @@
-// batch.hip.h — the batch behind the C ABI (include/isingmc_hip.h) as the host-side translation units share it: isingmc_hip.hip (creation,
-// the sweep driver, the accessors), pt.hip (parallel tempering) and record.hip (the sample record).
+// batch.hip.h — the batch behind the C ABI (include/isingmc_hip.h) as the host-side translation units share it: create.hip (creation),
+// driver.hip (the sweep driver), isingmc_hip.hip (the accessors), pt.hip (parallel tempering) and record.hip (the sample record).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
 #include <vector>
 #include "../../include/isingmc_hip.h"
+#include "lds_plan.h"
 #include "sse_batch.h"
 
 // The launch geometry and modes a batch runs with: the part of plan_batch()'s choice that is read after isingmc_create.  Later calls
@@ -84,7 +85,26 @@ struct isingmc_batch : BatchGeometry {
 
 namespace sse {
 
-int ensure_materialized(isingmc_batch *b);   // isingmc_hip.hip: apply the flip bytes that replicas' strings still wait for
+// the LDS questions of lds_plan.h asked of a batch
+inline bool is_tg(const isingmc_batch *b) { return is_tg(b->mode); }
+inline bool is_pm(const isingmc_batch *b) { return is_pm(b->mode); }
+inline uint32_t lds_edges(const isingmc_batch *b) { return lds_edges(b->mode, b->dev); }
+inline LdsNeeds lds_needs(const isingmc_batch *b) { return {b->dev, b->mode, b->lds_total_words, b->uf_ids_limit, b->max_ntrans}; }
+inline LdsPlan plan_lds(const isingmc_batch *b, uint32_t W) { return plan_lds(lds_needs(b), W); }
+
+// count elements of device memory that live as long as the batch
+template <typename T>
+int dalloc(isingmc_batch *b, T **p, size_t count, bool zero = true) {
+    void *q = nullptr;
+    size_t bytes = (count ? count : 1) * sizeof(T);
+    HIP_TRY(b, hipMalloc(&q, bytes));
+    b->allocs.push_back(q);
+    if (zero) HIP_TRY(b, hipMemset(q, 0, bytes));
+    *p = reinterpret_cast<T *>(q);
+    return ISINGMC_OK;
+}
+
+int ensure_materialized(isingmc_batch *b);   // driver.hip: apply the flip bytes that replicas' strings still wait for
 hipError_t record_append(isingmc_batch *b);  // record.hip: the p = 0 states of a sampled step go to the sample record
 void pt_free(isingmc_batch *b);              // pt.hip: release the tempering state, if any
 

@@ -103,6 +103,18 @@ struct SweepArgs {
                            // sse::sweep_fast_kernel: apply the pending flip bytes of a replica while loading its string
 };
 
+// DevBatch::err[r]: why replica r stopped (0 = it did not; sticky until isingmc_clear_errors).  The kernels set these, check_errors()
+// (driver.hip) turns them into return codes and messages.  4 was never used.
+enum SseErr : uint32_t {
+    SSE_ERR_CAPACITY = 1,   // cutoff n + n/2 exceeds the op-string capacity
+    SSE_ERR_COUNT = 2,      // directed loop: n disagrees with the op-string
+    SSE_ERR_LOOP_OPEN = 3,  // directed loop still open at its vertex bound
+    SSE_ERR_RVB_LDS = 5,    // RVB: the launch's LDS does not hold the fixed scratch
+    SSE_ERR_RVB_TABLE = 6,  // RVB: the constant-op table does not fit in LDS
+    SSE_ERR_RVB_SETS = 7,   // RVB: a cluster's sets outgrew their LDS areas
+    SSE_ERR_SCAN_RANGE = 8, // cluster scan: more than 65534 transverse ops inside one wave's range
+};
+
 // MODE of a kernel: how bonds are decoded and where the per-variable tables live
 // (3 / 4: the "+-J" decode — every replica its own coupling SIGNS on a shared graph with uniform |J| and fields: a bond's variables
 // come from the shared compact edge table in global memory (L2-resident), its sign from a per-replica bit array in LDS, its weight

@@ -23,7 +23,7 @@
 //     update: 4 + 2 (build) + 4 + 2 + 4 (apply) = 16 B per slot against 20 B before and 12 B algorithmic;
 //   * the apply pass runs over the same wave -> range partition as the build: a wave only re-reads ids it stored itself.
 // Replicas whose ids do not fit the LDS union-find of this launch (or that hold no op / no cut) are left untouched and flagged
-// in B.aux; the host follows up with the general kernel restricted to flagged replicas (isingmc_hip.hip run()).
+// in B.aux; the host follows up with the general kernel restricted to flagged replicas (driver.hip run()).
 #pragma once
 #include "sse_cluster_pass.hip.h" // the union-find and free_spin_pass
 

@@ -290,7 +290,7 @@ __device__ __forceinline__ uint32_t cluster_pass(const DevBatch &B, const Lds<W>
             for (uint32_t c = min(w2 * q, used); c < min(w2 * q + q, used); ++c) cuts += LDSW(L.o_chtr, c);
             bad |= (cuts >= 65535u);
         }
-        if (bad) { err = 8u; return 0u; }
+        if (bad) { err = SSE_ERR_SCAN_RANGE; return 0u; }
     }
     const uint32_t C = (uint32_t)ntrans;            // one id per cut (transverse op)
     const uint32_t S = N + C + (uint32_t)(W - 1) * N; // + artificial range-boundary placeholders

@@ -16,7 +16,7 @@
 //     oracle's f64 expressions for cutoffs up to 2^21; batches with a larger capacity run the f64 rounds (F64 = true), whose
 //     expressions are exactly those of the general pass and of the oracle;
 //   * no scalar-register spills: the kernel holds nothing but the diagonal pass (and the short directed loop behind it).
-// Requirements (checked by the host, isingmc_hip.hip): uniform |J| (LDS edge tables), N <= 4096 variables, 4 waves per
+// Requirements (checked by the host, create.hip): uniform |J| (LDS edge tables), N <= 4096 variables, 4 waves per
 // replica, Metropolis rule, two launches per timestep.
 #pragma once
 #include "sse_accept.h"
@@ -342,7 +342,7 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
 }
 
 // One launch = the diagonal sweep (and, if asked for, the directed loop behind it) of every replica: the first of the two
-// launches of a timestep (isingmc_hip.hip run()), for the geometry above.  PHASE only tags the symbol (see sweep_kernel).
+// launches of a timestep (driver.hip run()), for the geometry above.  PHASE only tags the symbol (see sweep_kernel).
 // F64: the rounds of the acceptance rule in f64 (batches whose capacity exceeds SSE_ACCEPT_MAX_DEN, launch_sweep_fast).
 template <int K, int PHASE, bool F64>
 __global__ __launch_bounds__(256, 4) void sweep_fast_kernel(DevBatch B, SweepArgs A) {
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256, 4) void sweep_fast_kernel(DevBatch B, SweepArg
             a5 += M;
             if (A.domask & SSE_DO_GROW) { // qmc_ising.rs:786, qmc_runner.rs:197
                 const uint32_t want = (uint32_t)n + (uint32_t)n / 2u;
-                if (want > M) { if (want > B.cap) { err = 1u; break; } M = want; }
+                if (want > M) { if (want > B.cap) { err = SSE_ERR_CAPACITY; break; } M = want; }
             }
         }
         if (A.domask & SSE_DO_LOOP) {

@@ -60,7 +60,7 @@ __device__ __forceinline__ uint32_t loop_pass(const DevBatch &B, const Lds<W> &L
     }
     __syncthreads();
     const uint32_t p0 = LDSW(L.o_misc, MISC_LOOP_A);
-    if (p0 == 0xFFFFFFFFu) { err = 2u; return 0u; } // n inconsistent with the op-string
+    if (p0 == 0xFFFFFFFFu) { err = SSE_ERR_COUNT; return 0u; } // n inconsistent with the op-string
     // the word at the current vertex travels with the walk: the search below hands over the word it found together with the
     // distance (one 64-bit LDS minimum), so a vertex costs one round trip to the op-string instead of three
     const uint32_t o64 = (L.o_misc + 7u) & ~1u; // an 8-byte aligned pair inside o_misc[6, 9)
@@ -167,7 +167,7 @@ __device__ __forceinline__ uint32_t loop_pass(const DevBatch &B, const Lds<W> &L
             __syncthreads();
             if (found != 0xFFFFFFFFu) break;
         }
-        if (found == 0xFFFFFFFFu) { err = 2u; finished = true; break; }
+        if (found == 0xFFFFFFFFu) { err = SSE_ERR_COUNT; finished = true; break; }
         uint32_t q = forward ? p + found : p + M - found;
         const bool wrapped = forward ? (q >= M) : (found > p);
         if (q >= M) q -= M;
@@ -181,7 +181,7 @@ __device__ __forceinline__ uint32_t loop_pass(const DevBatch &B, const Lds<W> &L
         if (q == p0 && nrel == rel0 && nside == side0) { finished = true; break; } // :293
         p = q; rel = nrel; side = nside; cur_word = found_word;
     }
-    if (!finished) err = 3u;
+    if (!finished) err = SSE_ERR_LOOP_OPEN;
     __syncthreads();
     return visited;
 }

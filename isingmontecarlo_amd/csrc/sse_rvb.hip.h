@@ -1029,7 +1029,7 @@ __device__ __forceinline__ bool rvb_replay_prob(const DevBatch &B, const Lds<W> 
             bool ok = true;
             if (sae != SSE_GI_NONE) ok = rvb_update_bonds_w<CL, W, G>(B, L, R, LDSW(R.o_sub, sae), bs, false, lane);
             if (ok && twoe && sce != SSE_GI_NONE) ok = rvb_update_bonds_w<CL, W, G>(B, L, R, LDSW(R.o_sub, sce), bs, false, lane);
-            if (!ok) { LDSW(R.o_ctl, RC_ERR) = 7u; return true; }
+            if (!ok) { LDSW(R.o_ctl, RC_ERR) = SSE_ERR_RVB_SETS; return true; }
             SSE_WAVE_FENCE();
             pos = e + 1u;
             if (pos >= cnt) break; // (also keeps the lane masks away from a shift by 64)
@@ -1180,7 +1180,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
     auto push_adj = [&](uint32_t var, uint32_t pos, double w) {
         if (cl.contains(var, pos, lane)) return;
         const bool ok = pos != SSE_NO_VAR ? bf.add(pos, var, w, lane) : bn.add(var, var, w, lane);
-        if (!ok) lerr = 7u;
+        if (!ok) lerr = SSE_ERR_RVB_SETS;
     };
     push_adj(v0, f0, 1.0);
     uint32_t left = csize;
@@ -1194,7 +1194,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
         uint32_t v, flip;
         if (pick_flips) { const uint32_t idx = bf.pick(u01(o.x), lane); v = bf.var_at(idx); flip = bf.key_at(idx); bf.remove_at(idx); }
         else { const uint32_t idx = bn.pick(u01(o.x), lane); v = bn.key_at(idx); flip = SSE_NO_VAR; bn.remove_at(idx); }
-        if (cl.n >= cl.cap) { lerr = 7u; break; }
+        if (cl.n >= cl.cap) { lerr = SSE_ERR_RVB_SETS; break; }
         cl.push(v, flip);
         const uint32_t vs = RVB_TW(R, R.o_vstart, v), vl = RVB_TW(R, R.o_vstart, v + 1) - vs;
         if (flip != SSE_NO_VAR) {
@@ -1234,7 +1234,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
     // unmarked ones (lane per candidate, the comparison partner is broadcast from LDS)
     const uint32_t ncl = cl.n;
     const uint32_t nc = lerr ? 0u : ncl + bf.n + bn.n;
-    if (nc > A.cap_sub) lerr = 7u;
+    if (nc > A.cap_sub) lerr = SSE_ERR_RVB_SETS;
     if (!lerr) { cl.dump_vars(A.o_tmp, 0u, lane); bf.dump_vars(A.o_tmp, ncl, lane); bn.dump_vars(A.o_tmp, ncl + bf.n, lane); }
     SSE_WAVE_FENCE();
     uint32_t nsub = 0;
@@ -1313,7 +1313,7 @@ __device__ __forceinline__ void rvb_grow(const DevBatch &B, const Lds<W> &L, con
     if (count) LDSW(A.o_wfrom, nwin++) = 0u;
     for (uint32_t i = 0; i < ntog && !lerr; ++i) {
         const uint32_t p = LDSW(A.o_tog, i);
-        if (count == 0) { if (nwin >= A.cap_win) { lerr = 7u; break; } LDSW(A.o_wfrom, nwin++) = p; }
+        if (count == 0) { if (nwin >= A.cap_win) { lerr = SSE_ERR_RVB_SETS; break; } LDSW(A.o_wfrom, nwin++) = p; }
         const uint32_t sv = LDSW(A.o_togs, i); // the toggle is a constant op of this cluster member
         const uint32_t f = LDSW(A.o_sfl, sv) ^ 2u;
         LDSW(A.o_sfl, sv) = f;
@@ -1369,7 +1369,7 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
                     ok = rvb_update_bonds_w<CL, W, G>(B, L, R, LDSW(R.o_sub, base + k), bw, true, lane);
                 }
             }
-            if (!ok) LDSW(R.o_ctl, RC_ERR) = 7u;
+            if (!ok) LDSW(R.o_ctl, RC_ERR) = SSE_ERR_RVB_SETS;
         }
         bool done = false;
         for (;;) {
@@ -1417,7 +1417,7 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
             rvb_state_at<W, CL, UL, BM, G>(B, L, R, r, from, nsub, true); // substate ^= cluster_state (:396-399, :315-318)
             SSE_STAMP(8);
             if (tid == 0 && wi == 0 && from == 0) {
-                if (!rvb_initial_bonds<CL, W, G>(B, L, R, nsub, bs, false)) LDSW(R.o_ctl, RC_ERR) = 7u;
+                if (!rvb_initial_bonds<CL, W, G>(B, L, R, nsub, bs, false)) LDSW(R.o_ctl, RC_ERR) = SSE_ERR_RVB_SETS;
             }
             uint32_t gp = from;
             for (;;) {
@@ -1470,7 +1470,7 @@ __device__ __forceinline__ bool rvb_attempt(const DevBatch &B, const Lds<W> &L, 
                         }
                         bool ok = rvb_update_bonds<CL, W, G>(B, L, R, d.a, bs, false);
                         if (ok && d.c != SSE_NO_VAR) ok = rvb_update_bonds<CL, W, G>(B, L, R, d.c, bs, false);
-                        if (!ok) { LDSW(R.o_ctl, RC_ERR) = 7u; break; }
+                        if (!ok) { LDSW(R.o_ctl, RC_ERR) = SSE_ERR_RVB_SETS; break; }
                     }
                 }
                 if (M == 0u || gp > (until < M ? until : M - 1)) break;
@@ -1500,14 +1500,14 @@ __device__ __forceinline__ uint32_t rvb_pass(const DevBatch &B, const Lds<W> &L,
     RvbLds R0;
     rvb_carve<W, G>(R0, L, B, r);
     if constexpr (G)
-        if (R0.o_free > B.lds_words) { err = 5u; return 0u; } // the launch's LDS does not hold the fixed scratch (host and carve disagree): loud, never cut off
+        if (R0.o_free > B.lds_words) { err = SSE_ERR_RVB_LDS; return 0u; } // the launch's LDS does not hold the fixed scratch (host and carve disagree): loud, never cut off
     if (tid == 0) { LDSW(R0.o_ctl, RC_ERR) = 0u; LDSW(R0.o_ctl, RC_SKIP) = 0u; LDSW(R0.o_ctl, RC_BROKE) = 0u; }
     for (uint32_t i = tid; i < B.E; i += blockDim.x) RVB_TH(R0.tg, R0.o_bix, i) = (uint16_t)0xFFFFu;
     __syncthreads();
     SSE_STAMP_INIT; // diagnostic builds: 6 constants table, 7 growth, 8 states, 9 gathers, 10 replay (probability), 11 accept, 12 replay (mutation)
     const uint32_t C = rvb_find_constants<W, CL, G>(B, L, R0, r, M);
     SSE_STAMP(6);
-    if (C == 0xFFFFFFFFu) { err = 6u; return 0u; } // constant-op table does not fit in LDS
+    if (C == 0xFFFFFFFFu) { err = SSE_ERR_RVB_TABLE; return 0u; } // constant-op table does not fit in LDS
     const uint32_t nzero = LDSW(R0.o_ctl, RC_NZERO);
     uint32_t nsucc = 0;
     // small growth areas behind the used part of the constant-op table (G: behind the scratch): as many as fit, at most one per wave

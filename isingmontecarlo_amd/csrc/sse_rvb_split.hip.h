@@ -179,7 +179,7 @@ __global__ __launch_bounds__(1024, 4) void rvb_grow_kernel(DevBatch B, SweepArgs
     SSE_STAMP_INIT; // diagnostic builds: 6 constants table, 7 growth in the small areas, 13 regrowth in the large one
     const uint32_t C = rvb_find_constants<W, CL>(B, L, R, r, M);
     SSE_STAMP(6);
-    if (C == 0xFFFFFFFFu) { if (tid == 0) prod[GO_ERR] = 6u; return; } // the table does not fit in LDS: the main launch reports it at attempt 0
+    if (C == 0xFFFFFFFFu) { if (tid == 0) prod[GO_ERR] = SSE_ERR_RVB_TABLE; return; } // the table does not fit in LDS: the main launch reports it at attempt 0
     const uint32_t nzero = LDSW(R.o_ctl, RC_NZERO);
     const uint32_t slots0 = (R.o_cps + C + 1u) & ~1u;
     uint32_t P = B.lds_words > slots0 ? (B.lds_words - slots0) / SSE_RVB_SLOT_WORDS : 0u;

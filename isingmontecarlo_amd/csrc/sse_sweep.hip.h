@@ -17,7 +17,7 @@ namespace sse {
 // PASSES selects what is compiled in: SSE_PASSES_ALL = every pass (one launch runs whole timesteps), SSE_PASSES_DIAG =
 // the diagonal pass alone.  The diagonal pass needs half the registers and a quarter of the LDS of the cluster
 // pass, so as its own kernel it runs at twice the occupancy (4 waves per SIMD for W <= 4); the host then issues
-// two launches per timestep (isingmc_hip.hip, run()).  n, cutoff, epoch, chunk counters travel through HBM.
+// two launches per timestep (driver.hip, run()).  n, cutoff, epoch, chunk counters travel through HBM.
 // SSE_PASSES_OFFDIAG is the second of those launches with the diagonal and RVB code left out (fewer live scalars).
 #ifndef SSE_MIN_WAVES_PER_SIMD
 #define SSE_MIN_WAVES_PER_SIMD 1
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(W * 64, (sse_waves_per_simd<W, PASSES>())) void swe
             a5 += M;
             if (A.domask & SSE_DO_GROW) { // qmc_ising.rs:786, qmc_runner.rs:197
                 const uint32_t want = (uint32_t)n + (uint32_t)n / 2u;
-                if (want > M) { if (want > B.cap) { err = 1u; break; } M = want; }
+                if (want > M) { if (want > B.cap) { err = SSE_ERR_CAPACITY; break; } M = want; }
             }
         }
         if constexpr (((PASSES == SSE_PASSES_ALL || PASSES == SSE_PASSES_RVB) && !TG && !PM) || RG) // (RVB keeps its working set in LDS except under RVB_G: refused by the host for MODE 2 models without it)
@@ -133,27 +133,33 @@ __global__ __launch_bounds__(W * 64, (sse_waves_per_simd<W, PASSES>())) void swe
     }
 }
 
-template <int W, int K, int CL, int PHASE, int PASSES>
+template <int W, int K, int MODE, int PHASE, int PASSES>
 hipError_t launch_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
-    return launch_lds(sweep_kernel<W, K, CL, PHASE, PASSES>, dim3(B.R), dim3(W * 64), c.lds_bytes, c.stream, B, A);
+    return launch_lds(sweep_kernel<W, K, MODE, PHASE, PASSES>, dim3(B.R), dim3(W * 64), c.lds_bytes, c.stream, B, A);
 }
-template <int W, int K, int CL>
+// PHASE = 1, the data-preparation symbol, exists in the default geometry K = 4 only: any other K runs PHASE = 0 whatever c.phase says
+template <int W, int K, int MODE, int PASSES>
+hipError_t launch_phase(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
+    if constexpr (K == 4) if (c.phase) return launch_one<W, K, MODE, 1, PASSES>(c, B, A);
+    return launch_one<W, K, MODE, 0, PASSES>(c, B, A);
+}
+template <int W, int K, int MODE>
 hipError_t launch_k(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
-    if (c.passes == SSE_PASSES_DIAG) {
-        if (c.phase && K == 4) return launch_one<W, K, CL, (K == 4 ? 1 : 0), SSE_PASSES_DIAG>(c, B, A);
-        return launch_one<W, K, CL, 0, SSE_PASSES_DIAG>(c, B, A);
-    }
-    if (c.passes == SSE_PASSES_OFFDIAG) {
-        if (c.phase && K == 4) return launch_one<W, K, CL, (K == 4 ? 1 : 0), SSE_PASSES_OFFDIAG>(c, B, A);
-        return launch_one<W, K, CL, 0, SSE_PASSES_OFFDIAG>(c, B, A);
-    }
-    if (c.passes == SSE_PASSES_RVB) {
-        if constexpr (CL != SSE_MODE_GLOBAL_TABLES && CL != SSE_MODE_PM_GLOBAL_TABLES) return launch_one<W, K, CL, 0, SSE_PASSES_RVB>(c, B, A);
+    switch (c.passes) {
+    case SSE_PASSES_DIAG: return launch_phase<W, K, MODE, SSE_PASSES_DIAG>(c, B, A);
+    case SSE_PASSES_OFFDIAG: return launch_phase<W, K, MODE, SSE_PASSES_OFFDIAG>(c, B, A);
+    case SSE_PASSES_RVB:
+        if constexpr (MODE != SSE_MODE_GLOBAL_TABLES && MODE != SSE_MODE_PM_GLOBAL_TABLES) return launch_one<W, K, MODE, 0, SSE_PASSES_RVB>(c, B, A);
         else return hipErrorInvalidValue;
+    default: return launch_phase<W, K, MODE, SSE_PASSES_ALL>(c, B, A);
     }
-    if (c.phase && K == 4) return launch_one<W, K, CL, (K == 4 ? 1 : 0), SSE_PASSES_ALL>(c, B, A); // data-preparation symbol: default geometry only
-    return launch_one<W, K, CL, 0, SSE_PASSES_ALL>(c, B, A);
 }
+// The instantiations of sweep_kernel<W, K, MODE, PHASE, PASSES> that exist; launch_w refuses every other LaunchCfg with hipErrorInvalidValue:
+//   W       1, 4, 6, 8, 16: one translation unit each (sweep_w*.hip)
+//   K, MODE GENERAL and LDS_EDGES with K = 4, 2, 1; GLOBAL_TABLES with K = 4, 1; the two +-J decodes with W = 4, K = 4 alone
+//   PASSES  ALL, DIAG and OFFDIAG for each of those; RVB too where the tables live in LDS (GENERAL, LDS_EDGES); PM_LDS_TABLES is DIAG alone
+//   PHASE   0; and 1 next to it where K = 4 and PASSES is not RVB
+// (sweep_rvb_global.hip adds <16, 4, GENERAL or LDS_EDGES, 0, RVB_G>.)
 template <int W>
 hipError_t launch_w(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     if (c.mode == SSE_MODE_PM_LDS_TABLES || c.mode == SSE_MODE_PM_GLOBAL_TABLES) { // +-J decode: the default geometry of large models only
@@ -161,7 +167,7 @@ hipError_t launch_w(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
             if (c.K != 4) return hipErrorInvalidValue;
             if (c.mode == SSE_MODE_PM_LDS_TABLES) {
                 if (c.passes != SSE_PASSES_DIAG) return hipErrorInvalidValue;
-                return c.phase ? launch_one<4, 4, SSE_MODE_PM_LDS_TABLES, 1, SSE_PASSES_DIAG>(c, B, A) : launch_one<4, 4, SSE_MODE_PM_LDS_TABLES, 0, SSE_PASSES_DIAG>(c, B, A);
+                return launch_phase<4, 4, SSE_MODE_PM_LDS_TABLES, SSE_PASSES_DIAG>(c, B, A);
             }
             return launch_k<4, 4, SSE_MODE_PM_GLOBAL_TABLES>(c, B, A);
         } else return hipErrorInvalidValue;

@@ -7,16 +7,20 @@ template <int K, bool HL, int PHASE>
 static hipError_t launch_cluster_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     return launch_lds(cluster_kernel<K, HL, PHASE>, dim3(B.R), dim3(SSE_CLW * 64), c.lds_bytes, c.stream, B, A);
 }
+// (PHASE = 1, the data-preparation symbol, exists for K = 4 only)
+template <int K, bool HL>
+static hipError_t launch_cluster_phase(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
+    if constexpr (K == 4) if (c.phase) return launch_cluster_one<K, HL, 1>(c, B, A);
+    return launch_cluster_one<K, HL, 0>(c, B, A);
+}
 size_t cluster_lds_words(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t ufcap, bool has_long) { ClLds L; L.carve(N, nwords, Nb, ufcap, has_long); return L.end; }
 bool cluster_ids_fit(uint32_t N, uint32_t S, uint32_t ufcap) { return cl_ids_fit(N, S, ufcap); }
+uint32_t cluster_max_vars() { return SSE_CL_MAX_VARS; }
 hipError_t launch_cluster(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     if (c.mode != SSE_MODE_LDS_EDGES || B.N > SSE_CL_MAX_VARS || !(A.domask & SSE_DO_CLUSTER)) return hipErrorInvalidValue;
     const bool hl = B.has_long != 0u;
-    if (c.K == 4) {
-        if (hl) return c.phase ? launch_cluster_one<4, true, 1>(c, B, A) : launch_cluster_one<4, true, 0>(c, B, A);
-        return c.phase ? launch_cluster_one<4, false, 1>(c, B, A) : launch_cluster_one<4, false, 0>(c, B, A);
-    }
-    if (c.K == 2) return hl ? launch_cluster_one<2, true, 0>(c, B, A) : launch_cluster_one<2, false, 0>(c, B, A);
+    if (c.K == 4) return hl ? launch_cluster_phase<4, true>(c, B, A) : launch_cluster_phase<4, false>(c, B, A);
+    if (c.K == 2) return hl ? launch_cluster_phase<2, true>(c, B, A) : launch_cluster_phase<2, false>(c, B, A);
     return hipErrorInvalidValue;
 }
 } // namespace sse

@@ -6,6 +6,7 @@ template <int K, int PHASE, bool F64>
 static hipError_t launch_fast_one(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     return launch_lds(sweep_fast_kernel<K, PHASE, F64>, dim3(B.R), dim3(256), c.lds_bytes, c.stream, B, A);
 }
+uint32_t fast_max_vars() { return SSE_FAST_MAX_VARS; }
 hipError_t launch_sweep_fast(const LaunchCfg &c, const DevBatch &B, const SweepArgs &A) {
     if (c.W != 4 || c.mode != SSE_MODE_LDS_EDGES) return hipErrorInvalidValue;
     // the integer acceptance rule equals the oracle's f64 expressions while the cutoff stays within SSE_ACCEPT_MAX_DEN; a batch

@@ -2,6 +2,7 @@
 depends on nothing that a translation unit happened to include before it."""
 import glob
 import os
+import re
 import shutil
 import subprocess
 
@@ -15,7 +16,7 @@ HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(_build.CSRC
 def test_the_device_header_is_split():
     assert "sse_device.hip.h" not in HEADERS
     assert {"sse_batch.h", "sse_core.hip.h", "sse_diag.hip.h", "sse_unionfind.hip.h", "sse_cluster_pass.hip.h", "sse_loop.hip.h",
-            "sse_sweep.hip.h", "sse_launch.h", "batch.hip.h"} <= set(HEADERS)
+            "sse_sweep.hip.h", "sse_launch.h", "batch.hip.h", "lds_plan.h"} <= set(HEADERS)
 
 
 def test_the_shared_data_header_is_plain_cpp():
@@ -24,6 +25,34 @@ def test_the_shared_data_header_is_plain_cpp():
                        input='#include "sse_batch.h"\nstatic_assert(sizeof(sse::BondRec) == 16, "one dwordx4 load");\n',
                        cwd=_build.CSRC, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
+
+
+KERNEL_HEADERS = {"sse_fast.hip.h", "sse_rvb.hip.h", "sse_rvb_split.hip.h", "sse_cluster.hip.h", "sse_sweep.hip.h",
+                  "sse_diag.hip.h", "sse_cluster_pass.hip.h", "sse_unionfind.hip.h", "sse_loop.hip.h"}  # the last four: the passes behind sse_sweep.hip.h
+
+
+def _includes(path, seen=None):
+    """Every file of csrc/ that `path` includes, directly or through the headers it includes."""
+    seen = set() if seen is None else seen
+    with open(path) as f:
+        for name in re.findall(r'^\s*#\s*include\s+"([^"/]+)"', f.read(), re.M):
+            if name not in seen:
+                seen.add(name)
+                _includes(os.path.join(_build.CSRC, name), seen)
+    return seen
+
+
+def test_only_kernel_units_and_the_lds_plan_include_kernel_headers():
+    """The host side of the C ABI (creation, driver, accessors, tempering, record) sees the kernels through sse_launch.h and lds_plan.h
+    alone: no kernel header reaches it, not even through another header."""
+    units = sorted(glob.glob(os.path.join(_build.CSRC, "*.hip")))
+    assert {os.path.basename(u) for u in units} == set(_build.SOURCES)
+    for unit in units:
+        name = os.path.basename(unit)
+        if name.startswith("sweep_") or name == "lds_plan.hip":
+            continue
+        assert not (_includes(unit) & KERNEL_HEADERS), (name, sorted(_includes(unit) & KERNEL_HEADERS))
+    assert _includes(os.path.join(_build.CSRC, "lds_plan.hip")) & KERNEL_HEADERS  # (the walk does find them where they are)
 
 
 @pytest.mark.parametrize("header", HEADERS)

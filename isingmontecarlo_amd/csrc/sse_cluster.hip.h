@@ -57,6 +57,13 @@ __device__ __forceinline__ uint32_t lds_ld16(uint32_t addr) {
     asm("" : "+v"(v));
     return v;
 }
+// low half of a word as a value of its own (an instruction of its own: written as a mask, the compiler folds it into the shift of
+// the address that follows and spends an instruction more)
+__device__ __forceinline__ uint32_t cl_low16(uint32_t x) {
+    uint32_t r;
+    asm("v_and_b32 %0, 0xffff, %1" : "=v"(r) : "v"(x));
+    return r;
+}
 // word of o_misc that the lanes of a predicated LDS store with nothing to store are pointed at (sse_fast.hip.h, "Predicated LDS
 // stores and atomics are written branch-free"): this kernel uses words 0-2 of the 16, nothing ever reads this one
 #define SSE_CL_MISC_DUMMY 12u
@@ -451,47 +458,39 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
         uint32_t cutnext = N + cutbase;
         uint8_t *fb = B.flipb + (size_t)r * B.stride;
         // The loop body is short, so the loads run D tiles ahead (one tile per memory round trip would leave the pass waiting):
-        // per tile two dwords of ids per lane and the 64 bytes of row masks, one dword per lane 0..15 (read back with v_readlane)
+        // per tile two dwords of ids per lane and the 64 bytes of row masks, one dword per lane 0..15 (read back with v_readlane).
+        // The tile loop is unrolled D times, so that the D slots of the queue change roles instead of contents, and every access
+        // is (tile base, scalar) + (lane offset, the same in every tile) + (row offset, an immediate): one address per tile for
+        // the ids, one for the masks and one for the stores.
         constexpr int D = 3;
         const uint32_t *mskw = reinterpret_cast<const uint32_t *>(msk);
         uint32_t qid[D][K / 2], qmk[D], bpend[K];
+        const uint32_t lane4 = 4u * (uint32_t)lane, lane15_4 = 4u * (uint32_t)(lane & 15);
         auto issue = [&](int slot, uint32_t pt) { // loads of the tile at pt (clamped to the last tile of the range: values unused beyond it)
             const uint32_t pc = pt < pend ? pt : pbeg;
+            const char *idt = reinterpret_cast<const char *>(ids + (pc >> 1));
+            const char *mkt = reinterpret_cast<const char *>(mskw + (pc >> 6) * 4u);
 #pragma unroll
-            for (int j = 0; j < K; j += 2) qid[slot][j / 2] = row_ld(ids, (pc >> 1) + (uint32_t)(j * 32 + lane));
-            qmk[slot] = row_ld(mskw, (pc >> 6) * 4u + (uint32_t)(lane & 15));
+            for (int j = 0; j < K; j += 2)
+                qid[slot][j / 2] = *reinterpret_cast<const uint32_t *>(idt + (size_t)lane4 + (size_t)(j * 128));
+            qmk[slot] = *reinterpret_cast<const uint32_t *>(mkt + (size_t)lane15_4);
         };
+        auto store = [&](uint32_t pt) { // the flip bytes of the tile at pt
+            uint8_t *fbt = fb + pt;
 #pragma unroll
-        for (int d = 0; d < D; ++d) issue(d, pbeg + (uint32_t)d * TS);
-#pragma unroll
-        for (int j = 0; j < K; ++j) bpend[j] = 0u;
-        uint32_t pprev = pbeg;
-        bool first = true;
-        for (uint32_t p0 = pbeg; p0 < pend; p0 += TS) {
-            uint32_t id2[K / 2];
-#pragma unroll
-            for (int j = 0; j < K / 2; ++j) id2[j] = qid[0][j];
-            const uint32_t mkv = qmk[0];
-#pragma unroll
-            for (int d = 0; d + 1 < D; ++d) {
-#pragma unroll
-                for (int j = 0; j < K / 2; ++j) qid[d][j] = qid[d + 1][j];
-                qmk[d] = qmk[d + 1];
-            }
-            if (!first) {
-#pragma unroll
-                for (int j = 0; j < K; ++j) fb[pprev + (uint32_t)(j * 64 + lane)] = (uint8_t)bpend[j];
-            }
-            first = false;
-            pprev = p0;
-            issue(D - 1, p0 + (uint32_t)D * TS);
+            for (int j = 0; j < K; ++j) fbt[(size_t)(uint32_t)lane + (size_t)(j * 64)] = (uint8_t)bpend[j];
+        };
+        auto tile = [&](int slot) { // flip bytes of the tile whose loads are in `slot`
+            const uint32_t mkv = qmk[slot];
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 const uint64_t cutm = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mkv, 4 * j) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mkv, 4 * j + 1) << 32);
-                const uint32_t own = __builtin_amdgcn_mbcnt_hi((uint32_t)(cutm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cutm, cutnext));
-                const uint32_t idin = (j & 1) ? (id2[j / 2] >> 16) : (id2[j / 2] & 0xFFFFu);
-                const uint32_t f1 = LDS16B(par_b + 2u * idin), f2 = LDS16B(par_b + 2u * own);
-                uint32_t m_other = (0u - f1) & 0xFu; // two-site: all four bits follow the one cluster
+                // the id a cut opens: cutnext + (cuts below the lane); the scalar is added behind the count instead of seeding it
+                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(cutm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cutm, 0u));
+                const uint32_t idw = qid[slot][j / 2];
+                const uint32_t idin = (j & 1) ? (idw >> 16) : cl_low16(idw);
+                const uint32_t f1 = LDS16B(par_b + 2u * idin), f2 = LDS16B(par_b + 2u * (cutnext + below));
+                uint32_t m_other = __umul24(f1, 0xFu); // two-site: all four bits follow the one cluster (a flip is 0 or 1)
                 if constexpr (HAS_LONG) { // longitudinal op: both bits of its variable
                     const uint64_t twom = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mkv, 4 * j + 2) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mkv, 4 * j + 3) << 32);
                     m_other &= sel64(twom, vgpr_copy_u32(0xFu), vgpr_copy_u32(0x5u));
@@ -499,10 +498,25 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                 bpend[j] = sel64(cutm, f1 | (f2 << 2), m_other);
                 cutnext += (uint32_t)popc64(cutm);
             }
-        }
-        if (pbeg < pend) {
+        };
 #pragma unroll
-            for (int j = 0; j < K; ++j) fb[pprev + (uint32_t)(j * 64 + lane)] = (uint8_t)bpend[j];
+        for (int d = 0; d < D; ++d) issue(d, pbeg + (uint32_t)d * TS);
+        // a tile's bytes are stored in front of the next tile's prefetch (see the build loop); the first tile has none in front
+        if (pbeg < pend) {
+            uint32_t p0 = pbeg;
+            for (;;) {
+                bool done = false;
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    if (d > 0 || p0 != pbeg) store(p0 - TS);
+                    tile(d);
+                    issue(d, p0 + (uint32_t)D * TS);
+                    p0 += TS;
+                    if (p0 >= pend) { done = true; break; }
+                }
+                if (done) break;
+            }
+            store(p0 - TS);
         }
     } else
     {

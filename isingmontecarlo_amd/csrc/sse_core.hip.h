@@ -57,6 +57,24 @@ __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
     }
     return make_uint4(c0, c1, c2, c3);
 }
+// Two blocks that differ in their first counter word only, round by round: one chain of round keys serves both (a call of its
+// own would derive them again: 18 s_add, most of them with an s_nop behind for the scalar-write -> vector-read hazard), and the
+// other block's vector instructions stand between a key's add and its first reader.  Same outputs as two philox4x32_10 calls.
+__device__ __forceinline__ void philox4x32_10_x2(uint32_t c0a, uint32_t c0b, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                                 uint4 &oa, uint4 &ob) {
+    uint32_t a0 = c0a, a1 = c1, a2 = c2, a3 = c3, b0 = c0b, b1 = c1, b2 = c2, b3 = c3;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t pa0 = (uint64_t)0xD2511F53u * (uint64_t)a0, pa1 = (uint64_t)0xCD9E8D57u * (uint64_t)a2;
+        const uint64_t pb0 = (uint64_t)0xD2511F53u * (uint64_t)b0, pb1 = (uint64_t)0xCD9E8D57u * (uint64_t)b2;
+        const uint32_t na0 = __builtin_amdgcn_bitop3_b32((uint32_t)(pa1 >> 32), a1, k0, 0x96), na2 = __builtin_amdgcn_bitop3_b32((uint32_t)(pa0 >> 32), a3, k1, 0x96);
+        const uint32_t nb0 = __builtin_amdgcn_bitop3_b32((uint32_t)(pb1 >> 32), b1, k0, 0x96), nb2 = __builtin_amdgcn_bitop3_b32((uint32_t)(pb0 >> 32), b3, k1, 0x96);
+        a0 = na0; a1 = (uint32_t)pa1; a2 = na2; a3 = (uint32_t)pa0;
+        b0 = nb0; b1 = (uint32_t)pb1; b2 = nb2; b3 = (uint32_t)pb0;
+        if (i < 9) { k0 = philox_bump(k0, 0x9E3779B9u); k1 = philox_bump(k1, 0xBB67AE85u); }
+    }
+    oa = make_uint4(a0, a1, a2, a3); ob = make_uint4(b0, b1, b2, b3);
+}
 
 struct Rng {
     uint32_t k0, k1, replica, epoch_lo, epoch_hi24;
@@ -71,6 +89,13 @@ struct Rng {
         }
 #endif
         return philox4x32_10(index, epoch_lo, replica, (tag << 24) | epoch_hi24, k0, k1);
+    }
+    // draw(tag, ia) and draw(tag, ib) with one derivation of the round keys
+    __device__ __forceinline__ void draw2(uint32_t tag, uint32_t ia, uint32_t ib, uint4 &oa, uint4 &ob) const {
+#ifdef SSE_PHASE_TIMING
+        if (dbgx & 2u) { oa = draw(tag, ia); ob = draw(tag, ib); return; }
+#endif
+        philox4x32_10_x2(ia, ib, epoch_lo, replica, (tag << 24) | epoch_hi24, k0, k1, oa, ob);
     }
 };
 __device__ __forceinline__ Rng make_rng(const DevBatch &B, uint32_t r, uint64_t epoch) {

@@ -129,7 +129,7 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
     propagate(vnext, m_later);
     __syncthreads();
     const uint32_t lane2 = 2u * (uint32_t)lane;
-    const uint32_t vM = vgpr_copy_u32(M), vM1 = vgpr_copy_u32(M + 1u), vzero = vgpr_copy_u32(0u);
+    const uint32_t vzero = vgpr_copy_u32(0u);
     const uint32_t vnever_hi = vgpr_copy_u32((uint32_t)(SSE_ACCEPT_NEVER_INSERT >> 32)), vnever_thr = vgpr_copy_u32((uint32_t)SSE_ACCEPT_NEVER_REMOVE);
     uint32_t ch = (uint32_t)(wave * 64 * K) / B.CH, chpos = (uint32_t)(wave * 64 * K) % B.CH; // chunk of this wave's share of the tile, and its offset in it
 
@@ -152,7 +152,7 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
         }
         const bool partial = tile * TS + TS > M; // wave-uniform: only the last tile can hold slots >= M
 
-        uint32_t cbv[K], neww[K], ent[K], bnd[K], rr1[K];
+        uint32_t neww[K], ent[K], bnd[K], rr1[K];
         uint64_t acci[K], accr[K]; // accepted inserts / removals of the round before
         // operands of the rule: integer rounds (sse_accept.h) ...
         uint32_t chi[K]; // (high word of the insert constant; candidates of one class share the low word: clo)
@@ -166,11 +166,15 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
         // registers, and a spilled mask costs a v_readlane per half and use.
         // ---- phase 1, all rows at once (nothing here depends on the spin tables): random numbers, bond, packed table entry
         {
-            uint4 rnd = make_uint4(0, 0, 0, 0);
+            // one Philox block per pair of rows (bit 6 of the slot index is clear on even rows); the two blocks of a K = 4 tile
+            // share one chain of round keys
+            uint4 rnds[K / 2];
+            if constexpr (K == 4) rng.draw2(SSE_TAG_DIAG, pbase, pbase + 128u, rnds[0], rnds[1]);
+            else rnds[0] = rng.draw(SSE_TAG_DIAG, pbase);
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 const uint32_t wd = word[j];
-                if ((j & 1) == 0) rnd = rng.draw(SSE_TAG_DIAG, pbase + (uint32_t)(j * 64)); // bit 6 of the slot index is clear on even rows
+                const uint4 rnd = rnds[j / 2];
                 const uint32_t r0 = (j & 1) ? rnd.z : rnd.x;
                 rr1[j] = (j & 1) ? rnd.w : rnd.y;
                 const uint64_t occm = sse_ballot(wd != 0u);
@@ -228,7 +232,10 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
             const double num_lo = __hiloint2double((int)cls.w, (int)cls.z); // num * 2^-32
             uint64_t im = sse_ballot(okbit > wd); // insert candidates: empty slot (word 0) and okbit 1
             if (partial) im &= sse_ballot(pbase + (uint32_t)(j * 64) < M);
-            const uint64_t rm = sse_ballot(wd != 0u) & ~sse_ballot(vcur[j] != dummy_b); // removal candidates: occupied and diagonal
+            // removal candidates: occupied and diagonal.  A diagonal op's decoded address is the lane's dummy word, an off-diagonal
+            // op's a spin entry, and the spin entries lie below the dummy words (fast_carve): written as a compare of its own, which
+            // is one v_cmp here; the ballot of phase 2 (!= dummy_b) asked again comes back as v_cndmask 0/1 + v_cmp_ne
+            const uint64_t rm = sse_ballot(wd != 0u) & sse_ballot(vcur[j] >= dummy_b);
             if constexpr (F64) {
                 // insert:  (u 2^-32) * den < num   <=>  u * den < num * 2^32  (u is converted again in every round: one
                 // instruction against two registers per row held across the rounds)
@@ -243,15 +250,18 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
                 chi[j] = sel64(im, cls.y, vnever_hi);
                 thr[j] = (int32_t)sel64(rm, (uint32_t)sse_accept_remove_threshold(rr1[j], num_lo), vnever_thr);
             }
-            cbv[j] = sel64(im, vM, vM1);
-            neww[j] = sel64(im, ((bnd[j] + 1u) << 4) | sub | (sub << 2), vzero); // what an accepted candidate leaves in the slot
+            // what an accepted candidate leaves in the slot: ((bnd + 1) << 4) | sub | (sub << 2), as a shift-add and a 24-bit multiply-add
+            // (sub <= 3: 5 * sub stays below 16, so the sum is the or)
+            neww[j] = sel64(im, __umul24(sub, 5u) + ((bnd[j] << 4) + 16u), vzero);
             acci[j] = 0ull; accr[j] = 0ull;
         }
 
         // ---- fixed point on the live operator count (see diagonal_pass) ----
-        int npref[K];
+        // q = M - (live operators in front of the lane's slot): the denominator of an insert; a removal's is q + 1 (no select
+        // between the two: an insert candidate is an empty slot, a removal candidate an occupied one)
+        uint32_t q[K];
 #pragma unroll
-        for (int j = 0; j < K; ++j) npref[j] = n_start;
+        for (int j = 0; j < K; ++j) q[j] = M - (uint32_t)n_start;
         int tot_all = 0, base = 0, wtot = 0;
         bool first = true;
         for (;;) {
@@ -259,15 +269,14 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
             uint64_t diff = 0ull; // lanes whose acceptance changed in this round
 #pragma unroll
             for (int j = 0; j < K; ++j) {
-                const int t = (int)(cbv[j] - (uint32_t)npref[j]);
+                const int t = (int)q[j];
                 uint64_t ai, ar;
                 if constexpr (F64) {
-                    const double td = (double)t;
-                    ai = sse_ballot((double)rr1[j] * td < nb[j]) & insm[j];
-                    ar = sse_ballot(un[j] < td) & remm[j];
+                    ai = sse_ballot((double)rr1[j] * (double)t < nb[j]) & insm[j];
+                    ar = sse_ballot(un[j] < (double)(t + 1)) & remm[j];
                 } else {
                     ai = sse_ballot(sse_accept_insert(rr1[j], (uint32_t)t, ((uint64_t)chi[j] << 32) | clo[j]));
-                    ar = sse_ballot(sse_accept_remove(t, thr[j]));
+                    ar = sse_ballot(sse_accept_remove(t + 1, thr[j]));
                 }
                 diff |= (ai ^ acci[j]) | (ar ^ accr[j]);
                 acci[j] = ai; accr[j] = ar;
@@ -300,14 +309,16 @@ __device__ __forceinline__ void diagonal_fast(const DevBatch &B, const Lds<4> &L
             gr++;
             if (!first && !anychg) break;
             first = false;
-            int run = n_start + base;
+            // q of the next round: M - run - (accepted inserts below the lane) + (accepted removals below it).  The scalar enters
+            // through the subtraction that seeds the second count (an instruction reads one scalar register: a count seeded
+            // with the scalar itself would need a copy into a vector register first)
+            uint32_t mrun = M - (uint32_t)(n_start + base);
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 const uint64_t im = acci[j], rm = accr[j];
-                const int ci = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(im >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)im, (uint32_t)run));
-                const int cr = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, 0u));
-                npref[j] = ci - cr;
-                run += popc64(im) - popc64(rm);
+                const uint32_t ci = __builtin_amdgcn_mbcnt_hi((uint32_t)(im >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)im, 0u));
+                q[j] = __builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, mrun - ci));
+                mrun -= (uint32_t)(popc64(im) - popc64(rm));
             }
         }
         // ---- commit ----

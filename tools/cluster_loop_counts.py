@@ -17,7 +17,8 @@ Parts are found by shape, not by label (labels move with every change):
     (ds_cmpst_rtn: the range joins), a returning add (ds_add_rtn: the root list's append), Philox rounds (the coin draws), LDS
     reads and writes only (flip bits, state tail), writes only (zeroing);
   * apply loops: the innermost loops behind the build loop that hold global loads, global stores and LDS reads and no Philox:
-    the deferred one stores bytes (global_store_byte), the in-place one dwords.
+    the deferred one stores bytes (global_store_byte), the in-place one dwords.  Where the deferred loop is unrolled over the slots
+    of its prefetch queue, the row says how many tiles one iteration holds.
 Counts are of the text of a span, rarely taken paths included.  A static figure; executed counts come from the SQ_INSTS_*
 counters.  The last line is the kernel's register / spill / scratch record from the same file."""
 import re
@@ -118,7 +119,12 @@ def main():
     print(f"  barriers in the kernel: {ops.count('s_barrier')}, instructions in the kernel: {len(ops)}")
     for s in spans:
         if s[0] >= build[1] and innermost(s) and has(s, "global_load") and has(s, "global_store") and has(s, "ds_read") and not philox(s):
-            row("apply loop, deferred (one tile)" if has(s, "global_store_byte") else "apply loop, in place (one tile)", ops[s[0]:s[1]])
+            if has(s, "global_store_byte"):  # a tile is K byte stores: the loop may be unrolled over the slots of its prefetch queue
+                k = int(re.search(r"cluster_kernelILi(\d+)E", name).group(1))
+                tiles = max(1, sum(1 for o in ops[s[0]:s[1]] if o.startswith("global_store_byte")) // k)
+                row("apply loop, deferred (one tile)" if tiles == 1 else f"apply loop, deferred ({tiles} tiles)", ops[s[0]:s[1]])
+            else:
+                row("apply loop, in place (one tile)", ops[s[0]:s[1]])
     # the kernel's metadata record: the keys between the "  - .agpr_count:" lines around its .name
     at = next(i for i, l in enumerate(text) if l.strip().startswith(".name:") and l.split()[-1] == name)
     lo = max(i for i in range(at) if text[i].startswith("  - ."))

@@ -262,7 +262,13 @@ int isingmc_pt_create(isingmc_batch *b, const isingmc_pt_layout *layout);
 /* ncclGetUniqueId (rank 0, then broadcast by the launcher) and ncclCommInitRank for this batch's rank / world */
 int isingmc_pt_nccl_unique_id(isingmc_nccl_id *out);
 int isingmc_pt_attach_nccl(isingmc_batch *b, const isingmc_nccl_id *id);
-/* TemperingContainer::tempering_step (tempering_container.rs:121-149).  *nswaps += swaps whose LOWER temperature this rank owns. */
+/* TemperingContainer::tempering_step (tempering_container.rs:121-149).  *nswaps += swaps whose LOWER temperature this rank owns.
+ * Accumulator rows: a swap inside a rank exchanges the labels of two replicas, so statistics per temperature need the rows to follow
+ * the labels.  They do exactly when the caller has asked for it: isingmc_set_accumulator_rows, called after isingmc_pt_create with
+ * nrows = ntemps * nchains and rows[r] = the slot of replica r (isingmc_pt_get_slots), makes every later isingmc_pt_step (and
+ * isingmc_pt_set_state) keep row = slot, on the device path and on the host path alike.  Any other rows, the default ones (row r for
+ * replica r) included, are left alone by both paths: they then count per replica, i.e. per configuration on a single rank.  A new
+ * isingmc_pt_create or isingmc_set_accumulator_rows call with other rows ends the following. */
 int isingmc_pt_step(isingmc_batch *b, uint64_t *nswaps);
 /* Where the swap decisions are taken.  A rank that owns every temperature of a batch with one Hamiltonian (world == 1, no
  * ISINGMC_CFG_PER_REPLICA_J) decides on the device by default: one small kernel per step equalises the cutoffs of each chain, draws the

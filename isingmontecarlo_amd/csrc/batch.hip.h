@@ -37,6 +37,7 @@ struct isingmc_batch : BatchGeometry {
     uint32_t acc_rows = 0;
     uint32_t rvb_updates = 0;
     uint32_t *d_acc_row = nullptr;
+    bool acc_follow_slots = false;      // the caller passed the tempering slots as accumulator rows: isingmc_pt_step keeps row = slot
     uint32_t max_ntrans = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -107,5 +108,6 @@ int dalloc(isingmc_batch *b, T **p, size_t count, bool zero = true) {
 int ensure_materialized(isingmc_batch *b);   // driver.hip: apply the flip bytes that replicas' strings still wait for
 hipError_t record_append(isingmc_batch *b);  // record.hip: the p = 0 states of a sampled step go to the sample record
 void pt_free(isingmc_batch *b);              // pt.hip: release the tempering state, if any
+int pt_rows_are_slots(isingmc_batch *b, uint32_t nrows, const uint32_t *rows, bool *yes); // pt.hip: are these accumulator rows the replicas' tempering slots?
 
 } // namespace sse

@@ -166,6 +166,7 @@ int isingmc_set_accumulator_rows(isingmc_batch *b, uint32_t nrows, const uint32_
     for (uint32_t r = 0; r < b->dev.R; ++r) if (rows[r] >= nrows) { b->err = "accumulator row out of range"; return ISINGMC_EINVAL; }
     HIP_TRY(b, hipSetDevice(b->device));
     HIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (const int rc = pt_rows_are_slots(b, nrows, rows, &b->acc_follow_slots)) return rc;
     if (nrows != b->acc_rows) {
         uint64_t *na = nullptr;
         int rc = dalloc(b, &na, (size_t)nrows * 8);

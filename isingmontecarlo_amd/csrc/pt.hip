@@ -291,6 +291,7 @@ int isingmc_pt_create(isingmc_batch *b, const isingmc_pt_layout *lay) {
     if (lay->world > 1 && !lay->transport) { b->err = "a transport (or isingmc_pt_attach_nccl) is needed for more than one rank"; return ISINGMC_EINVAL; }
     HIP_TRY(b, hipSetDevice(b->device));
     pt_free(b);
+    b->acc_follow_slots = false; // until the caller passes this layout's slots to isingmc_set_accumulator_rows
     PtState *P = new PtState();
     b->pt = P;
     P->ntemps = lay->ntemps; P->nchains = lay->nchains; P->rank = lay->rank; P->world = lay->world; P->tper = tper;
@@ -442,6 +443,7 @@ int isingmc_pt_set_state(isingmc_batch *b, const uint32_t *slot_of_replica, cons
         HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
     }
     P->step = step; P->total_swaps = total_swaps;
+    if (b->acc_follow_slots) HIP_TRY(b, hipMemcpy(b->d_acc_row, P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
     if (P->dev_decide) return pt_upload_labels(b);
     return ISINGMC_OK;
 }
@@ -457,7 +459,7 @@ int isingmc_pt_step(isingmc_batch *b, uint64_t *nswaps) {
         if (T <= 1) { P->step++; return ISINGMC_OK; }
         PtDev D{};
         D.slot_of = P->d_slot_of; D.at = P->d_at; D.result = P->d_result; D.betas = P->d_betas; D.beta_r = P->d_beta_r; D.total = P->d_total;
-        D.acc_row = b->acc_rows == T * K ? b->d_acc_row : nullptr; // per-slot accumulators (isingmc_set_accumulator_rows with the slots) follow the labels
+        D.acc_row = b->acc_follow_slots ? b->d_acc_row : nullptr; // per-slot accumulators (isingmc_set_accumulator_rows with the slots) follow the labels
         D.K = K; D.T = T; D.key0 = (uint32_t)P->seed; D.key1 = (uint32_t)(P->seed >> 32); D.step = P->step;
         hipLaunchKernelGGL(pt_decide_kernel, dim3(1), dim3(K < 256 ? ((K + 63) / 64) * 64 : 256), 0, b->stream, b->dev, D);
         HIP_TRY(b, hipGetLastError());
@@ -622,6 +624,7 @@ int isingmc_pt_step(isingmc_batch *b, uint64_t *nswaps) {
         for (uint32_t r = 0; r < R; ++r) b->ham_row_host[r] = P->slot_of[r] - t_lo * K;
         HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
     }
+    if (b->acc_follow_slots) HIP_TRY(b, hipMemcpy(b->d_acc_row, P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice)); // as the decision kernel does
     P->step++;
     P->total_swaps += swaps;
     if (nswaps) *nswaps += swaps;
@@ -629,3 +632,15 @@ int isingmc_pt_step(isingmc_batch *b, uint64_t *nswaps) {
 }
 
 } // extern "C"
+
+// isingmc_set_accumulator_rows asks: did the caller pass the tempering slots (an [ntemps * nchains] table, row of replica r = its slot)?
+// Only then do the rows follow the labels in isingmc_pt_step, on the device path and on the host path alike.
+int sse::pt_rows_are_slots(isingmc_batch *b, uint32_t nrows, const uint32_t *rows, bool *yes) {
+    *yes = false;
+    PtState *P = b->pt;
+    if (!P || nrows != P->ntemps * P->nchains) return ISINGMC_OK;
+    if (const int rc = pt_sync_host(b)) return rc;
+    for (uint32_t r = 0; r < b->dev.R; ++r) if (rows[r] != P->slot_of[r]) return ISINGMC_OK;
+    *yes = true;
+    return ISINGMC_OK;
+}

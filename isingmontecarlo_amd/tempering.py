@@ -201,7 +201,6 @@ class NativeTemperingContainer:
                         betas=self.betas.ctypes.data_as(C.POINTER(C.c_double)), seed=int(seed),
                         transport=C.pointer(self._tr) if self.world > 1 else None)
         graph._check(graph._lib.isingmc_pt_create(graph._h, C.byref(lay)))
-        self.total_swaps_local = 0
         self._stale = True
         self._refresh()
 
@@ -220,6 +219,14 @@ class NativeTemperingContainer:
     slot_of = property(lambda self: self._mirror("_slot_of"))
     local_betas = property(lambda self: self._mirror("_local_betas"))
     config_of = property(lambda self: self._mirror("_config_of"))
+
+    @property
+    def total_swaps_local(self):
+        """Swaps this rank has counted (as the owner of the lower temperature), whichever path decided them: the library keeps the
+        count, so steps on the device, steps on the host and a restored checkpoint all add up in one place."""
+        step, sw = C.c_uint64(0), C.c_uint64(0)
+        self.g._check(self.g._lib.isingmc_pt_get_state(self.g._h, C.byref(step), C.byref(sw)))
+        return int(sw.value)
 
     def _mirror(self, name):
         if self._stale:
@@ -307,15 +314,10 @@ class NativeTemperingContainer:
             return None if sw is None else int(sw.value)
         sw = C.c_uint64(0)
         self.g._check(self.g._lib.isingmc_pt_step(self.g._h, C.byref(sw)))
-        self.total_swaps_local += int(sw.value)
         self._refresh()
         return int(sw.value)
 
     def get_total_swaps(self):
-        if self.device_decisions:
-            step, sw = C.c_uint64(0), C.c_uint64(0)
-            self.g._check(self.g._lib.isingmc_pt_get_state(self.g._h, C.byref(step), C.byref(sw)))
-            return int(sw.value)
         if not self.dist:
             return self.total_swaps_local
         import torch
@@ -344,6 +346,5 @@ class NativeTemperingContainer:
         so = np.ascontiguousarray(z["slot_of"].astype(np.uint32)); co = np.ascontiguousarray(z["config_of"].astype(np.uint32))
         self.g._check(self.g._lib.isingmc_pt_set_state(self.g._h, so.ctypes.data_as(C.POINTER(C.c_uint32)), co.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                         int(z["step"]), int(z["swaps"])))
-        self.total_swaps_local = int(z["swaps_local"])
         self._stale = True
         self._refresh()

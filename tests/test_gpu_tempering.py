@@ -81,66 +81,24 @@ def test_native_step_two_ranks_exchange_configurations(oracle, tmp_path):
     assert moved > 0
 
 
-def _powi(x, n):
-    r = 1.0
-    while n:
-        if n & 1:
-            r *= x
-        x *= x
-        n >>= 1
-    return r
-
-
 def test_relative_weights_between_different_hamiltonians(oracle):
     """tempering_container.rs:830-858 test_bondstrength: nine graphs on one chain, couplings j * i / 10 (i = 1..9), the same beta:
-    swaps are decided by GraphWeights::relative_weight alone (tempering_traits.rs:126-155).  Oracle side: configurations
-    (op-string, state, update counter, Philox identity) are moved between replica objects built on the slots' models."""
+    swaps are decided by GraphWeights::relative_weight alone (tempering_traits.rs:126-155).  Oracle side (_pt_reference.py):
+    configurations (op-string, state, update counter, Philox identity) are moved between replica objects built on the slots' models."""
     import isingmontecarlo_amd as im
+    import _pt_reference as ptref
     edges = [((0, 1), 1.0), ((1, 2), 1.0), ((2, 3), 1.0), ((3, 4), 1.0)]
     T, beta, gamma, seed, cap, steps = 9, 10.0, 0.1, 31415, 2048, 12
     J = np.array([[j * i / 10.0 for _, j in edges] for i in range(1, T + 1)])
     betas = np.full(T, beta)
     g = im.QmcIsingGraph(edges, gamma, 0.0, 10, seed, nreplicas=T, capacity=cap, couplings=J)
     tc = im.NativeTemperingContainer(g, betas, 1, seed)
-    e = [list(ab) for ab, _ in edges]
-    models = [oracle.Model(5, e, list(J[t]), gamma, 0.0) for t in range(T)]
-    reps = [oracle.Replica(models[t], cap, 10, seed, t) for t in range(T)]
-    ids = list(range(T))  # configuration identity at each slot
-    key = (seed & 0xFFFFFFFF, seed >> 32)
-    import ctypes as C
-    def philox(idx, step):
-        ctr = (C.c_uint32 * 4)(idx, step, 0, 6 << 24); k = (C.c_uint32 * 2)(*key); o = (C.c_uint32 * 4)()
-        oracle.lib().ora_philox4x32_10(ctr, k, o)
-        return o[0]
-    swaps_ref = 0
+    hams = ptref.SlotHamiltonians(5, [list(ab) for ab, _ in edges], J, gamma, None)
+    ref = ptref.reference_pt(None, betas, 1, seed, cap, 10, steps, 20, hams=hams)
+    reps, ids, swaps_ref = ref.by_slot[0], ref.ids, ref.swaps
     for step in range(steps):
         tc.timesteps(20)
-        for t in range(T):
-            reps[t].timesteps(20, beta)
         tc.tempering_step()
-        # ---- reference formulation with relative weights ----
-        maxcut = max(r.cutoff for r in reps)
-        for r in reps:
-            assert r.set_cutoff(maxcut) == 0
-        a_first = (philox(0, step) >> 31) != 0
-        for phase in range(2):
-            set_a = a_first if phase == 0 else not a_first
-            for t in range(0 if set_a else 1, T - 1, 2):
-                u = philox(1 + t, step) / 4294967296.0
-                ga, gb = reps[t], reps[t + 1]
-                rel_b = 1.0
-                for b_ in range(len(edges)):
-                    rel_b *= _powi(J[t + 1][b_] / J[t][b_], ga.bond_count(b_))
-                rel_a = 1.0
-                for b_ in range(len(edges)):
-                    rel_a *= _powi(J[t][b_] / J[t + 1][b_], gb.bond_count(b_))
-                p = (betas[t] / betas[t + 1]) ** float(gb.n - ga.n) * (rel_b * rel_a)
-                if p > u:
-                    swaps_ref += 1
-                    na = oracle.Replica(models[t], cap, maxcut, seed, ids[t + 1], gb.state()); na.set_ops(gb.ops()); na.set_epoch(gb.epoch)
-                    nb = oracle.Replica(models[t + 1], cap, maxcut, seed, ids[t], ga.state()); nb.set_ops(ga.ops()); nb.set_epoch(ga.epoch)
-                    reps[t], reps[t + 1] = na, nb
-                    ids[t], ids[t + 1] = ids[t + 1], ids[t]
     assert tc.get_total_swaps() == swaps_ref and swaps_ref > 0
     st, n = g.state_ref(), g.get_n()
     for r in range(T):
@@ -180,7 +138,7 @@ def test_relative_weights_with_fields_varying_across_temperatures(oracle):
     differ between the graphs of one chain (the same beta everywhere, so swaps are decided by the three ratios alone:
     bond_ratio * transverse_ratio * longitudinal_ratio, in that order).  Oracle side as in the test above."""
     import isingmontecarlo_amd as im
-    import ctypes as C
+    import _pt_reference as ptref
     edges = [((0, 1), -1.0), ((1, 2), 1.0), ((2, 3), -1.0), ((3, 0), -1.0), ((0, 2), 0.5)]
     T, beta, seed, cap, steps = 8, 3.0, 2718, 4096, 14
     E, N = len(edges), 4
@@ -190,48 +148,12 @@ def test_relative_weights_with_fields_varying_across_temperatures(oracle):
     betas = np.full(T, beta)
     g = im.QmcIsingGraph(edges, 1.0, 0.1, 8, seed, nreplicas=T, capacity=cap, couplings=J, transverse_r=gam, longitudinal_r=hl)
     tc = im.NativeTemperingContainer(g, betas, 1, seed)
-    e = [list(ab) for ab, _ in edges]
-    models = [oracle.Model(N, e, list(J[t]), float(gam[t]), float(hl[t])) for t in range(T)]
-    reps = [oracle.Replica(models[t], cap, 8, seed, t) for t in range(T)]
-    ids = list(range(T))
-    key = (seed & 0xFFFFFFFF, seed >> 32)
-
-    def philox(idx, step):
-        ctr = (C.c_uint32 * 4)(idx, step, 0, 6 << 24); k = (C.c_uint32 * 2)(*key); o = (C.c_uint32 * 4)()
-        oracle.lib().ora_philox4x32_10(ctr, k, o)
-        return o[0]
-
-    def relative_weight(graph, t_from, t_to):
-        w = 1.0
-        for b_ in range(E):
-            w *= _powi(J[t_to][b_] / J[t_from][b_], graph.bond_count(b_))
-        w *= _powi(gam[t_to] / gam[t_from], sum(graph.bond_count(E + v) for v in range(N)))
-        if abs(hl[t_from]) > np.finfo(float).eps:
-            w *= _powi(hl[t_to] / hl[t_from], sum(graph.bond_count(E + N + v) for v in range(N)))
-        return w
-
-    swaps_ref = 0
+    hams = ptref.SlotHamiltonians(N, [list(ab) for ab, _ in edges], J, gam, hl)
+    ref = ptref.reference_pt(None, betas, 1, seed, cap, 8, steps, 10, hams=hams)
+    reps, ids, swaps_ref = ref.by_slot[0], ref.ids, ref.swaps
     for step in range(steps):
         tc.timesteps(10)
-        for t in range(T):
-            reps[t].timesteps(10, beta)
         tc.tempering_step()
-        maxcut = max(r.cutoff for r in reps)
-        for r in reps:
-            assert r.set_cutoff(maxcut) == 0
-        a_first = (philox(0, step) >> 31) != 0
-        for phase in range(2):
-            set_a = a_first if phase == 0 else not a_first
-            for t in range(0 if set_a else 1, T - 1, 2):
-                u = philox(1 + t, step) / 4294967296.0
-                ga, gb = reps[t], reps[t + 1]
-                p = 1.0 * (relative_weight(ga, t, t + 1) * relative_weight(gb, t + 1, t))  # equal betas: (beta_a / beta_b)^dn == 1
-                if p > u:
-                    swaps_ref += 1
-                    na = oracle.Replica(models[t], cap, maxcut, seed, ids[t + 1], gb.state()); na.set_ops(gb.ops()); na.set_epoch(gb.epoch)
-                    nb = oracle.Replica(models[t + 1], cap, maxcut, seed, ids[t], ga.state()); nb.set_ops(ga.ops()); nb.set_epoch(ga.epoch)
-                    reps[t], reps[t + 1] = na, nb
-                    ids[t], ids[t + 1] = ids[t + 1], ids[t]
     assert tc.get_total_swaps() == swaps_ref and 0 < swaps_ref < steps * (T - 1)
     st, n = g.state_ref(), g.get_n()
     for r in range(T):

@@ -9,6 +9,8 @@ import pytest
 
 import _lattices as lat
 import _oracle as O
+import _pt_cases as pc
+import _pt_reference as ptref
 from _pt_backend import OracleBackend
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,18 +22,9 @@ def small_model():
 
 
 def reference_pt(model, betas, nchains, seed, cap, cutoff, nsteps, sweeps_per_step):
-    """The reference formulation: graphs live at (chain, temperature) slots and are swapped (pointer swap)."""
-    T = len(betas)
-    reps = {(t, k): O.Replica(model, cap, cutoff, seed, t * nchains + k) for t in range(T) for k in range(nchains)}
-    by_slot = [[reps[(t, k)] for t in range(T)] for k in range(nchains)]
-    swaps = 0
-    for step in range(nsteps):
-        for k in range(nchains):
-            for t in range(T):
-                by_slot[k][t].timesteps(sweeps_per_step, float(betas[t]))
-        for k in range(nchains):
-            swaps += O.pt_step(by_slot[k], betas, seed, k, step)
-    return by_slot, swaps
+    """The reference formulation: graphs live at (chain, temperature) slots and are swapped (_pt_reference.py)."""
+    ref = ptref.reference_pt(model, betas, nchains, seed, cap, cutoff, nsteps, sweeps_per_step)
+    return ref.by_slot, ref.swaps
 
 
 def test_pt_decide_matches_oracle_step():
@@ -80,6 +73,61 @@ def test_label_swapping_driver_equals_graph_swapping():
     # per-slot accumulators: every slot sampled every sweep
     acc = tc.slot_accumulators()
     assert (acc[:, 1] == 36).all()
+
+
+@pytest.mark.parametrize("c", pc.ALL_CASES, ids=[c["name"] for c in pc.ALL_CASES])
+def test_references_of_the_gpu_cases_swap_where_the_cases_look(c):
+    """The references the GPU tempering tests compare against (tests/_pt_cases.py), alone: every pair of neighbouring temperatures is
+    accepted at least once, the pair across the rank boundary of a two-rank case at least three times, and with per-slot Hamiltonians
+    fewer than all attempts are accepted.  A case that misses one gets another seed or beta window, not a weaker condition."""
+    ref = pc.check_preconditions(c)
+    T, K = len(c["betas"]), c["K"]
+    assert ref.attempts == (T - 1) * K * c["steps"] and sorted(ref.ids.tolist()) == list(range(T * K))
+    assert (ref.acc[:, 1] == c["steps"] * c["sweeps"]).all()  # every slot sampled every sweep
+    if T > 1:
+        assert not np.array_equal(ref.ids, np.arange(T * K))
+
+
+def test_reference_with_slot_hamiltonians_restates_the_single_chain_loop():
+    """_pt_reference with per-slot Hamiltonians and K = 1 against the loop the GPU tests were written with first (one chain,
+    relative weights spelled out in place): the same swaps, the same graphs."""
+    edges = [((0, 1), -1.0), ((1, 2), 1.0), ((2, 3), -1.0), ((3, 0), -1.0), ((0, 2), 0.5)]
+    T, beta, seed, cap, steps, E, N = 8, 3.0, 2718, 4096, 14, 5, 4
+    J = np.array([[j * (1.0 + 0.04 * t) for _, j in edges] for t in range(T)])
+    gam, hl = np.array([0.8 + 0.05 * t for t in range(T)]), np.array([0.30 - 0.02 * t for t in range(T)])
+    e = [list(ab) for ab, _ in edges]
+    hams = ptref.SlotHamiltonians(N, e, J, gam, hl)
+    ref = ptref.reference_pt(None, np.full(T, beta), 1, seed, cap, 8, steps, 10, hams=hams)
+    reps = [O.Replica(hams.models[t], cap, 8, seed, t) for t in range(T)]
+    ids, swaps = list(range(T)), 0
+
+    def weight(graph, t_from, t_to):
+        w = 1.0
+        for b_ in range(E):
+            w *= ptref.powi(J[t_to][b_] / J[t_from][b_], graph.bond_count(b_))
+        w *= ptref.powi(gam[t_to] / gam[t_from], sum(graph.bond_count(E + v) for v in range(N)))
+        return w * ptref.powi(hl[t_to] / hl[t_from], sum(graph.bond_count(E + N + v) for v in range(N)))
+
+    for step in range(steps):
+        for t in range(T):
+            reps[t].timesteps(10, beta)
+        maxcut = max(r.cutoff for r in reps)
+        for r in reps:
+            assert r.set_cutoff(maxcut) == 0
+        a_first = (ptref.philox(seed, 0, step, 0) >> 31) != 0
+        for phase in range(2):
+            for t in range(0 if a_first == (phase == 0) else 1, T - 1, 2):
+                u = ptref.philox(seed, 1 + t, step, 0) / 4294967296.0
+                ga, gb = reps[t], reps[t + 1]
+                if 1.0 * (weight(ga, t, t + 1) * weight(gb, t + 1, t)) > u:
+                    swaps += 1
+                    na = O.Replica(hams.models[t], cap, maxcut, seed, ids[t + 1], gb.state()); na.set_ops(gb.ops()); na.set_epoch(gb.epoch)
+                    nb = O.Replica(hams.models[t + 1], cap, maxcut, seed, ids[t], ga.state()); nb.set_ops(ga.ops()); nb.set_epoch(ga.epoch)
+                    reps[t], reps[t + 1] = na, nb
+                    ids[t], ids[t + 1] = ids[t + 1], ids[t]
+    assert swaps == ref.swaps and 0 < swaps < ref.attempts and ids == ref.ids.tolist()
+    for t in range(T):
+        assert np.array_equal(reps[t].state(), ref.by_slot[0][t].state()) and np.array_equal(reps[t].ops(), ref.by_slot[0][t].ops())
 
 
 def test_timesteps_sample_shapes_and_energy_sum():

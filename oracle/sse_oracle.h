@@ -85,6 +85,16 @@ uint32_t ora_get_bond_count(const ora_replica *r, uint32_t bond);
 void ora_get_accumulators(const ora_replica *r, uint64_t acc[8]);
 void ora_reset_accumulators(ora_replica *r);
 
+/* batch accessors (sse_oracle_batch.c): one call for many replicas; NULL outputs are skipped; acc is [nreplicas][8] */
+void ora_batch_get(ora_replica *const *reps, uint32_t nreplicas, uint32_t *n, uint32_t *cutoff, uint64_t *acc);
+void ora_batch_bond_counts(ora_replica *const *reps, uint32_t nreplicas, uint32_t nbonds, uint32_t *out /* [nreplicas][nbonds] */);
+/* first Philox word of ora_pt_step's decision stream for index 0 .. nidx - 1 and chain 0 .. nchains - 1: out[nidx][nchains] */
+void ora_batch_pt_step(ora_replica **by_slot /* [ntemps][nchains], permuted in place */, const double *betas, uint32_t ntemps,
+                       uint32_t nchains, uint64_t seed, uint64_t step, uint64_t *swaps /* [nchains] */);
+/* the replicas a[i] and b[i] exchange their models (same variables and bonds): their configurations change Hamiltonians */
+void ora_batch_swap_models(ora_replica *const *a, ora_replica *const *b, uint32_t count);
+void ora_pt_words(uint64_t seed, uint64_t step, uint32_t nidx, uint32_t nchains, uint32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,11 @@ def load():
         "ora_reset_accumulators": (None, [vp]),
         "ora_batch_timesteps": (C.c_int, [p(vp), u32, u64, p(f64), u32, u32, C.c_int]),
         "ora_max_threads": (C.c_int, []),
+        "ora_batch_get": (None, [p(vp), u32, p(u32), p(u32), p(u64)]),
+        "ora_batch_bond_counts": (None, [p(vp), u32, u32, p(u32)]),
+        "ora_pt_words": (None, [u64, u64, u32, u32, p(u32)]),
+        "ora_batch_pt_step": (None, [p(vp), p(f64), u32, u32, u64, u64, p(u64)]),
+        "ora_batch_swap_models": (None, [p(vp), p(vp), u32]),
         "ora_philox4x32_10": (None, [p(u32), p(u32), p(u32)]),
         "ora_pt_step": (u64, [p(vp), p(f64), u32, u64, u32, u64]),
         "ora_rvb_update": (u32, [vp, u32]),
@@ -258,6 +263,63 @@ def batch_timesteps(replicas, t, betas, freq=1, flags=0, nthreads=0):
     b = np.ascontiguousarray(np.asarray(betas, dtype=np.float64))
     rc = lib().ora_batch_timesteps(arr, len(replicas), t, _ptr(b, C.c_double), freq, flags, nthreads)
     assert rc == 0
+
+
+def pointers(replicas):
+    """The replicas' handles as a uint64 array: what the batch_* functions below take (index it to reorder)."""
+    return np.array([r.ptr for r in replicas], dtype=np.uint64)
+
+
+def batch_run(ptrs, t, betas, freq=1, flags=0, nthreads=0):
+    """batch_timesteps over a handle array."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    b = np.ascontiguousarray(np.asarray(betas, dtype=np.float64))
+    assert len(b) == len(ptrs)
+    if nthreads == 0:
+        nthreads = min(usable_cores(), len(ptrs))
+    rc = lib().ora_batch_timesteps(ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), len(ptrs), t, _ptr(b, C.c_double), freq, flags, nthreads)
+    assert rc == 0, "oracle: cutoff exceeded capacity"
+
+
+def batch_get(ptrs):
+    """(n[R], cutoff[R], accumulators[R][8]) of the replicas of a handle array, one call."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    n, cut, acc = np.zeros(len(ptrs), dtype=np.uint32), np.zeros(len(ptrs), dtype=np.uint32), np.zeros((len(ptrs), 8), dtype=np.uint64)
+    lib().ora_batch_get(ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), len(ptrs), _ptr(n, C.c_uint32), _ptr(cut, C.c_uint32), _ptr(acc, C.c_uint64))
+    return n, cut, acc
+
+
+def batch_bond_counts(ptrs, nbonds):
+    """Replica.bond_count for bonds 0 .. nbonds - 1 of every replica: [R][nbonds]."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    out = np.zeros((len(ptrs), int(nbonds)), dtype=np.uint32)
+    lib().ora_batch_bond_counts(ptrs.ctypes.data_as(C.POINTER(C.c_void_p)), len(ptrs), int(nbonds), _ptr(out, C.c_uint32))
+    return out
+
+
+def pt_words(seed, step, nidx, nchains):
+    """First Philox word of pt_step's decision stream, [nidx][nchains]: index 0 is the order coin, 1 + t the pair (t, t + 1)."""
+    out = np.zeros((int(nidx), int(nchains)), dtype=np.uint32)
+    lib().ora_pt_words(int(seed), int(step), int(nidx), int(nchains), _ptr(out, C.c_uint32))
+    return out
+
+
+def batch_pt_step(ptrs, betas, nchains, seed, step):
+    """pt_step for every chain of a ladder: `ptrs` (handles, row t*nchains + k) -> (the permuted handles, swaps per chain)."""
+    out = np.array(ptrs, dtype=np.uint64)
+    b = np.ascontiguousarray(np.asarray(betas, dtype=np.float64))
+    assert len(out) == len(b) * int(nchains)
+    sw = np.zeros(int(nchains), dtype=np.uint64)
+    lib().ora_batch_pt_step(out.ctypes.data_as(C.POINTER(C.c_void_p)), _ptr(b, C.c_double), len(b), int(nchains), int(seed), int(step), _ptr(sw, C.c_uint64))
+    return out, sw
+
+
+def swap_models(reps_a, reps_b):
+    """The configurations of reps_a[i] and reps_b[i] change Hamiltonians: the replica objects exchange their models (one graph)."""
+    a, b = pointers(reps_a), pointers(reps_b)
+    lib().ora_batch_swap_models(a.ctypes.data_as(C.POINTER(C.c_void_p)), b.ctypes.data_as(C.POINTER(C.c_void_p)), len(a))
+    for x, y in zip(reps_a, reps_b):
+        x.model, y.model = y.model, x.model
 
 
 def pt_step(by_slot, betas, seed, chain, step):

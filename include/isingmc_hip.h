@@ -374,6 +374,35 @@ int isingmc_plan_cluster_lds(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t 
  *   out[23] LDS of the general launch and out[24] ids of its LDS union-find, both before any sweep has run
  *   out[25] state words per replica        out[26] bonds                        out[27..31] 0 */
 int isingmc_plan_batch(const isingmc_config *cfg, uint32_t lds_bytes, uint32_t out[32]);
+/* Host-only, a device-free test entry: the swap decisions of one phase (0, 1) of isingmc_pt_step's host leg as one rank sees them,
+ * by the function the step itself calls (the rule: csrc/pt_rule.h).  Rank `rank` of `world` owns temperatures [rank * tper,
+ * (rank + 1) * tper) of nchains chains: R = tper * nchains local replicas, local slot ls = (t - rank * tper) * nchains + chain.
+ * Side 0 is the lower neighbour (rank - 1), side 1 the upper one; a side without a neighbour is ignored (pointers may be NULL).
+ * An accepted pair inside the block exchanges the labels of its two replicas (slot_of, at); an accepted pair across a boundary
+ * becomes an item of that side, (replica, word offset of its configuration in the message, cutoff) as the pack kernel takes them, in
+ * chain order on both ranks: the caller moves the configurations (and their operator counts) before the next phase.  Neither a
+ * device nor an isingmc_batch is read, so ranks with two neighbours can be simulated in one process. */
+typedef struct isingmc_pt_wire { /* what neighbours exchange per chain and phase: 16 bytes */
+    uint32_t n, pad; /* operator count of the boundary walker */
+    double rel;      /* its relative weight towards the other side's Hamiltonian; read only when the boundary pair is in the phase */
+} isingmc_pt_wire;
+typedef struct isingmc_pt_phase {
+    uint32_t struct_size; /* = sizeof(isingmc_pt_phase) */
+    uint32_t rank, world, tper, nchains, phase;
+    const double *betas;  /* [world * tper] */
+    uint64_t seed, step;
+    const uint32_t *n;    /* [R] operator count of local replica r */
+    const double *rel;    /* [R] relative weight of replica r towards the partner of its pair in this phase; NULL: all 1 (one Hamiltonian) */
+    const isingmc_pt_wire *from[2]; /* [nchains] what the neighbour of that side sent */
+    const uint32_t *cutoff;         /* [nchains] the chain's (equalised) cutoff */
+    uint32_t fixed_words;           /* words of a configuration in the message besides its cutoff op words */
+    uint32_t *slot_of, *at;         /* in/out [R]: global slot t * nchains + chain of replica r; replica at local slot ls */
+    uint32_t *items[2];             /* out [3 * nchains] per side */
+    uint32_t nitems[2];             /* out */
+    uint64_t words[2];              /* out: words of that side's message */
+    uint64_t nswaps;                /* out: accepted pairs whose LOWER temperature this rank owns */
+} isingmc_pt_phase;
+int isingmc_pt_plan_phase(isingmc_pt_phase *view);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,21 @@ class _PtLayout(C.Structure):
                 ("betas", C.POINTER(C.c_double)), ("seed", C.c_uint64), ("transport", C.POINTER(_PtTransport))]
 
 
+class _PtWire(C.Structure):
+    """include/isingmc_hip.h: isingmc_pt_wire"""
+    _fields_ = [("n", C.c_uint32), ("pad", C.c_uint32), ("rel", C.c_double)]
+
+
+class _PtPhase(C.Structure):
+    """include/isingmc_hip.h: isingmc_pt_phase"""
+    _fields_ = [("struct_size", C.c_uint32), ("rank", C.c_uint32), ("world", C.c_uint32), ("tper", C.c_uint32), ("nchains", C.c_uint32),
+                ("phase", C.c_uint32), ("betas", C.POINTER(C.c_double)), ("seed", C.c_uint64), ("step", C.c_uint64),
+                ("n", C.POINTER(C.c_uint32)), ("rel", C.POINTER(C.c_double)), ("from_", C.POINTER(_PtWire) * 2),
+                ("cutoff", C.POINTER(C.c_uint32)), ("fixed_words", C.c_uint32), ("slot_of", C.POINTER(C.c_uint32)),
+                ("at", C.POINTER(C.c_uint32)), ("items", C.POINTER(C.c_uint32) * 2), ("nitems", C.c_uint32 * 2),
+                ("words", C.c_uint64 * 2), ("nswaps", C.c_uint64)]
+
+
 class _NcclId(C.Structure):
     _fields_ = [("internal", C.c_char * 128)]
 
@@ -135,6 +150,7 @@ SYMBOLS = {
     "isingmc_plan_geometry": (C.c_int, [_u32, _u32, _u32, _u32, _P(_u32)]),
     "isingmc_plan_cluster_lds": (C.c_int, [_u32, _u32, _u32, _u32, _u32, _u32, _P(_u32)]),
     "isingmc_plan_batch": (C.c_int, [_P(_Config), _u32, _P(_u32)]),
+    "isingmc_pt_plan_phase": (C.c_int, [_P(_PtPhase)]),
     "isingmc_record_attach": (C.c_int, [_vp, _u32]),
     "isingmc_record_count": (C.c_int, [_vp, _P(_u32), _P(_u32)]),
     "isingmc_record_clear": (C.c_int, [_vp]),

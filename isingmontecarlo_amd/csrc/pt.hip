@@ -9,17 +9,34 @@
 // identity) through one more grouped send / receive.  Every rank therefore always holds exactly the configurations of its own
 // temperature block, and no collective touches the sweep path.  The transport is RCCL point-to-point on device buffers when a
 // communicator is attached (isingmc_pt_attach_nccl), otherwise the caller's host-staged sendrecv (tests: two ranks on one GPU).
+//
+// The swap rule itself is pt_rule.h.  This file applies it three times: isingmc_pt_decide (a whole ladder on the host),
+// pt_decide_kernel (a rank that owns every temperature) and isingmc_pt_plan_phase (one rank's share of a phase, from plain data:
+// the host leg of isingmc_pt_step calls it, and so do tests that simulate ranks without a device).
 #include "batch.hip.h"
+#include "pt_rule.h"      // the swap rule: decision stream, pt_accept, the walk of a phase
 #include "sse_core.hip.h" // philox4x32_10
 
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <utility>
 #include <dlfcn.h>
 #include <rccl/rccl.h> // types and enum values only (ncclUint32, ncclMax, ncclUniqueId): the library itself is dlopen()ed on first use
 static_assert(sizeof(ncclUniqueId) == sizeof(isingmc_nccl_id), "isingmc_nccl_id must carry an ncclUniqueId");
 
 using namespace sse;
+
+// A rank's two neighbours, [0] the lower and [1] the upper one: what one phase exchanges with each.  (The neighbour's boundary
+// Hamiltonian rows are the halo of PtState::ham.)
+struct PtSide {
+    int peer = -1;                          // rank, -1 = none
+    std::vector<isingmc_pt_wire> sent, got; // [nchains] boundary walkers' operator counts and relative weights
+    std::vector<uint32_t> items;            // [3 * nchains] accepted boundary swaps: (replica, word offset in the message, cutoff)
+    uint32_t nitems = 0;
+    uint64_t words = 0;                     // words of the configuration message
+};
+static_assert(sizeof(isingmc_pt_wire) == 16 && offsetof(isingmc_pt_wire, rel) == 8, "wire format");
 
 struct PtState {
     uint32_t ntemps = 0, nchains = 0, rank = 0, world = 1, tper = 0;
@@ -47,10 +64,12 @@ struct PtState {
     unsigned long long *d_total = nullptr; // total swaps since isingmc_pt_create / set_state
     uint32_t *d_items = nullptr; // [3 * nchains] accepted boundary swaps of one turn: (replica, word offset, cutoff)
     uint32_t *d_small = nullptr; // [4][nchains] staging of the boundary operator counts / cutoffs on the device (RCCL path)
-    // different Hamiltonians per temperature (per-replica couplings): J rows of the neighbouring ranks' boundary slots
+    // different Hamiltonians per temperature (per-replica couplings)
     bool hams_differ = false;
-    std::vector<double> J_prev_last, J_next_first; // [nchains][E]
-    uint32_t *d_counts = nullptr;                  // [R][Nb] bond counts (only when hams_differ)
+    std::vector<double> ham;      // [nchains + R + nchains][E + 2] Hamiltonian row (pt_ham_row) of local slot ls at row nchains + ls; the halo
+                                  // rows are the lower neighbour's last and the upper neighbour's first temperature
+    uint32_t *d_counts = nullptr; // [R][Nb] bond counts (only when hams_differ)
+    PtSide side[2];
     // configuration exchange
     uint32_t *d_pack_s = nullptr, *d_pack_r = nullptr;
     size_t pack_cap_words = 0;
@@ -66,33 +85,6 @@ void sse::pt_free(isingmc_batch *b) {
         if (q) (void)hipFree(q);
     delete P;
     b->pt = nullptr;
-}
-
-// Host-side Philox4x32-10 for the tempering decisions (control logic, not the sweep path).
-static void host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
-    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// f64::powi as Rust lowers it (compiler-rt __powidf2): squaring sequence, reciprocal for negative exponents.  Multiplications
-// and one division only: the host and the device give the same bits (as does the oracle, which multiplies in the same order)
-__host__ __device__ static inline double pt_powi(double x, int64_t n) {
-    uint64_t m = n < 0 ? (uint64_t)(-n) : (uint64_t)n;
-    double r = 1.0;
-    while (m) { if (m & 1u) r *= x; x *= x; m >>= 1; }
-    return n < 0 ? 1.0 / r : r;
-}
-// The swap test of a pair of neighbouring temperatures t, t + 1 (swap_on_chunks, tempering_container.rs:296-298): the walker at t
-// holds n_a ops, the one at t + 1 n_b; rel = the product of their relative weights under each other's Hamiltonian (1 when the
-// Hamiltonians are equal: a multiplication by 1.0 changes no bit); u uniform in [0, 1)
-__host__ __device__ static inline bool pt_accept(double beta_t, double beta_t1, uint32_t n_a, uint32_t n_b, double rel, double u) {
-    return pt_powi(beta_t / beta_t1, (int64_t)n_b - (int64_t)n_a) * rel > u;
 }
 
 // pack / unpack one configuration per workgroup: header (n, ntrans, cutoff, err, epoch lo/hi, rid, 0), p=0 state, chunk counters, op words
@@ -137,11 +129,15 @@ struct PtDev {
     const double *betas;
     double *beta_r;
     unsigned long long *total;
-    uint32_t K, T, key0, key1;
-    uint64_t step;
+    uint32_t K, T;
+    uint64_t seed, step;
 };
-// One tempering step of a rank that owns all temperatures (tempering_container.rs:121-149; the decisions of isingmc_pt_step's host
-// path, same Philox counters): thread k takes chain k — equalise its cutoffs, draw the order coin, walk the two sets of pairs.
+// the draw of pt_rule.h's decision stream in a kernel: the same integers as pt_philox_word
+struct PtKernelDraw {
+    __device__ uint32_t operator()(const PtChain &c, uint32_t index) const { return philox4x32_10(index, c.step_lo, c.chain, c.tag_step_hi, c.key0, c.key1).x; }
+};
+// One tempering step of a rank that owns all temperatures (tempering_container.rs:121-149; pt_rule.h): thread k takes chain k — equalise
+// its cutoffs, draw the order coin, walk the two phases.
 __global__ void pt_decide_kernel(DevBatch B, PtDev P) {
     __shared__ unsigned int s_swaps;
     if (threadIdx.x == 0) s_swaps = 0u;
@@ -151,19 +147,15 @@ __global__ void pt_decide_kernel(DevBatch B, PtDev P) {
         for (uint32_t t = 0; t < P.T; ++t) { const uint32_t c = B.cutoff[P.at[t * P.K + k]]; maxcut = c > maxcut ? c : maxcut; }
         if (maxcut > B.cap) { P.result[1] = 1u; continue; }
         for (uint32_t t = 0; t < P.T; ++t) B.cutoff[P.at[t * P.K + k]] = maxcut;
-        const uint32_t c3 = (SSE_TAG_PT << 24) | (uint32_t)((P.step >> 32) & 0xFFFFFFu);
-        const bool a_first = (philox4x32_10(0u, (uint32_t)P.step, k, c3, P.key0, P.key1).x >> 31) != 0u;
+        const PtChain c = pt_chain(P.seed, P.step, k);
+        const bool a_first = pt_a_first(c, PtKernelDraw{});
         uint32_t swaps = 0;
-        for (int phase = 0; phase < 2; ++phase) {
-            const bool set_a = (phase == 0) ? a_first : !a_first;
-            for (uint32_t t = 0; t + 1 < P.T; ++t) {
-                if ((((t & 1u) == 0u) != set_a)) continue;
+        for (int phase = 0; phase < 2; ++phase)
+            pt_walk_phase(c, a_first, phase, 0u, P.T - 1u, PtKernelDraw{}, [&](uint32_t t, double u) {
                 const uint32_t la = t * P.K + k, lb = la + P.K;
                 const uint32_t ra = P.at[la], rb = P.at[lb];
-                const double u = (double)philox4x32_10(1u + t, (uint32_t)P.step, k, c3, P.key0, P.key1).x * (1.0 / 4294967296.0);
                 if (pt_accept(P.betas[t], P.betas[t + 1], B.n[ra], B.n[rb], 1.0, u)) { P.slot_of[ra] = lb; P.slot_of[rb] = la; P.at[la] = rb; P.at[lb] = ra; swaps++; }
-            }
-        }
+            });
         for (uint32_t t = 0; t < P.T; ++t) {
             const uint32_t r = P.at[t * P.K + k];
             P.beta_r[r] = P.betas[t];
@@ -202,50 +194,86 @@ static void pt_ham_row(const isingmc_batch *b, uint32_t row, double *out) {
     out[E + 1] = b->dev.has_long ? (((t0[E + N].a_info >> (SSE_INFO_SHIFT + 2)) & 1u) ? 0.5 : -0.5) * t0[E + N].w : 0.0;
 }
 
-static int pt_exchange_small(isingmc_batch *b, int peer, const uint32_t *s, uint32_t *r, size_t count) {
+// ---- transport: RCCL on device buffers once a communicator is attached, otherwise the caller's host-staged functions ----
+// `words` u32 to and from `peer` in one exchange: an RCCL group call on the device buffers, or the caller's blocking sendrecv on the
+// host buffers.  The callers stage between host and device on the side that needs it.
+static int pt_sendrecv(isingmc_batch *b, int peer, const uint32_t *dev_s, uint32_t *dev_r, const void *host_s, void *host_r, size_t words) {
     PtState *P = b->pt;
-    if (peer < 0 || peer >= (int)P->world) return ISINGMC_OK;
-    if (P->comm) { // RCCL point-to-point on device buffers, one group call
-        uint32_t *ds = P->d_small, *dr = P->d_small + count;
-        HIP_TRY(b, hipMemcpyAsync(ds, s, 4 * count, hipMemcpyHostToDevice, b->stream));
-        if (P->p_gstart() || P->p_send(ds, count, (int)ncclUint32, peer, P->comm, b->stream) || P->p_recv(dr, count, (int)ncclUint32, peer, P->comm, b->stream) || P->p_gend()) {
+    if (P->comm) {
+        if (P->p_gstart() || P->p_send(dev_s, words, (int)ncclUint32, peer, P->comm, b->stream) || P->p_recv(dev_r, words, (int)ncclUint32, peer, P->comm, b->stream) || P->p_gend()) {
             b->err = "RCCL send/recv failed"; return ISINGMC_ENODEVICE;
         }
-        HIP_TRY(b, hipMemcpyAsync(r, dr, 4 * count, hipMemcpyDeviceToHost, b->stream));
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
         return ISINGMC_OK;
     }
-    if (!P->have_tr || P->tr.sendrecv(P->tr.ctx, peer, s, 4 * count, r, 4 * count)) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
+    if (!P->have_tr || P->tr.sendrecv(P->tr.ctx, peer, host_s, 4 * words, host_r, 4 * words)) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
     return ISINGMC_OK;
 }
+// element-wise maximum of v over all ranks, in place
+static int pt_allreduce_max(isingmc_batch *b, std::vector<uint32_t> &v) {
+    PtState *P = b->pt;
+    if (P->comm) {
+        HIP_TRY(b, hipMemcpyAsync(P->d_small, v.data(), 4 * v.size(), hipMemcpyHostToDevice, b->stream));
+        if (P->p_allreduce(P->d_small, P->d_small, v.size(), (int)ncclUint32, (int)ncclMax, P->comm, b->stream)) { b->err = "ncclAllReduce failed"; return ISINGMC_ENODEVICE; }
+        HIP_TRY(b, hipMemcpyAsync(v.data(), P->d_small, 4 * v.size(), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+    } else if (P->tr.allreduce_max_u32(P->tr.ctx, v.data(), v.size())) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
+    return ISINGMC_OK;
+}
+// the side a rank talks to in turn 0 and 1 of an exchange: even ranks talk to their upper neighbour first (the host-staged transport is blocking)
+static PtSide &pt_turn_side(PtState *P, int turn) { return P->side[(((P->rank & 1u) == 0u) == (turn == 0)) ? 1 : 0]; }
 
 extern "C" {
 
 int isingmc_pt_decide(uint64_t seed, uint64_t step, uint32_t nchains, uint32_t ntemps, const double *betas,
                       const uint32_t *n_of_config, uint32_t *config_at, uint64_t *nswaps) {
     if (!betas || !n_of_config || !config_at || nchains == 0 || ntemps == 0) return ISINGMC_EINVAL;
-    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
     uint64_t swaps = 0;
     for (uint32_t chain = 0; chain < nchains && ntemps > 1; ++chain) {
-        uint32_t ctr[4] = {0u, (uint32_t)step, chain, (SSE_TAG_PT << 24) | (uint32_t)((step >> 32) & 0xFFFFFFu)};
-        uint32_t o[4];
-        host_philox(ctr, key, o);
-        const bool a_first = (o[0] >> 31) != 0u; // gen_bool(0.5) (tempering_container.rs:140)
-        for (int phase = 0; phase < 2; ++phase) {
-            const bool set_a = (phase == 0) ? a_first : !a_first;
-            for (uint32_t t = set_a ? 0u : 1u; t + 1 < ntemps; t += 2) { // make_first/second_subgraphs (:83-99)
-                ctr[0] = 1u + t;
-                host_philox(ctr, key, o);
-                const double u = (double)o[0] * (1.0 / 4294967296.0);
+        const PtChain c = pt_chain(seed, step, chain);
+        const bool a_first = pt_a_first(c, PtHostDraw{});
+        for (int phase = 0; phase < 2; ++phase)
+            pt_walk_phase(c, a_first, phase, 0u, ntemps - 1u, PtHostDraw{}, [&](uint32_t t, double u) {
                 uint32_t &ca = config_at[(size_t)t * nchains + chain], &cb = config_at[(size_t)(t + 1) * nchains + chain];
-                if (pt_accept(betas[t], betas[t + 1], n_of_config[ca], n_of_config[cb], 1.0, u)) { // (equal Hamiltonians)
-                    const uint32_t tmp = ca; ca = cb; cb = tmp;
-                    swaps++;
-                }
-            }
-        }
+                if (pt_accept(betas[t], betas[t + 1], n_of_config[ca], n_of_config[cb], 1.0, u)) { std::swap(ca, cb); swaps++; } // (equal Hamiltonians)
+            });
     }
     if (nswaps) *nswaps += swaps;
+    return ISINGMC_OK;
+}
+
+// One rank's decisions of one phase from plain data (include/isingmc_hip.h): no device, no batch.  Chain k walks the pairs (t, t + 1)
+// that touch this rank's block [t_lo, t_hi): the pair below the block when there is a lower neighbour, the interior pairs, the pair
+// above it when there is an upper one.  A walker that is not local comes from the neighbour's wire.
+int isingmc_pt_plan_phase(isingmc_pt_phase *v) {
+    if (!v || v->struct_size != sizeof(isingmc_pt_phase) || v->world == 0 || v->rank >= v->world || v->tper == 0 || v->nchains == 0 || v->phase > 1 ||
+        !v->betas || !v->n || !v->cutoff || !v->slot_of || !v->at) return ISINGMC_EINVAL;
+    const bool has[2] = {v->rank > 0, v->rank + 1 < v->world};
+    for (int s = 0; s < 2; ++s) if (has[s] && (!v->from[s] || !v->items[s])) return ISINGMC_EINVAL;
+    const uint32_t K = v->nchains, t_lo = v->rank * v->tper, t_hi = t_lo + v->tper;
+    size_t off[2] = {0, 0};
+    v->nitems[0] = v->nitems[1] = 0;
+    v->nswaps = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+        const PtChain c = pt_chain(v->seed, v->step, k);
+        pt_walk_phase(c, pt_a_first(c, PtHostDraw{}), (int)v->phase, t_lo - (has[0] ? 1u : 0u), t_hi - (has[1] ? 0u : 1u), PtHostDraw{}, [&](uint32_t t, double u) {
+            const bool a_here = t >= t_lo, b_here = t + 1 < t_hi; // the walkers at t and at t + 1: local, or the neighbour's
+            const uint32_t la = (t - t_lo) * K + k, lb = la + K, ra = a_here ? v->at[la] : 0u, rb = b_here ? v->at[lb] : 0u;
+            const uint32_t n_a = a_here ? v->n[ra] : v->from[0][k].n, n_b = b_here ? v->n[rb] : v->from[1][k].n;
+            const double rel_a = !a_here ? v->from[0][k].rel : v->rel ? v->rel[ra] : 1.0, rel_b = !b_here ? v->from[1][k].rel : v->rel ? v->rel[rb] : 1.0;
+            if (!pt_accept(v->betas[t], v->betas[t + 1], n_a, n_b, rel_a * rel_b, u)) return;
+            if (a_here && b_here) { // labels change hands
+                std::swap(v->slot_of[ra], v->slot_of[rb]);
+                v->at[la] = rb; v->at[lb] = ra;
+            } else { // the two configurations change ranks
+                const int s = a_here ? 1 : 0;
+                uint32_t *it = v->items[s] + 3 * v->nitems[s]++;
+                it[0] = a_here ? ra : rb; it[1] = (uint32_t)off[s]; it[2] = v->cutoff[k];
+                off[s] += (size_t)v->fixed_words + v->cutoff[k];
+            }
+            if (a_here) v->nswaps++; // counted by the owner of the lower temperature
+        });
+    }
+    v->words[0] = off[0]; v->words[1] = off[1];
     return ISINGMC_OK;
 }
 
@@ -306,6 +334,9 @@ int isingmc_pt_create(isingmc_batch *b, const isingmc_pt_layout *lay) {
     b->dev.rid = P->d_rid;
     HIP_TRY(b, hipMalloc((void **)&P->d_small, 4 * 4 * (size_t)(P->nchains * 2 + 2)));
     HIP_TRY(b, hipMalloc((void **)&P->d_items, 4 * 3 * (size_t)P->nchains));
+    P->side[0].peer = P->rank > 0 ? (int)P->rank - 1 : -1;
+    P->side[1].peer = P->rank + 1 < P->world ? (int)P->rank + 1 : -1;
+    for (PtSide &S : P->side) { S.sent.resize(P->nchains); S.got.resize(P->nchains); S.items.resize(3 * (size_t)P->nchains); }
     P->pack_cap_words = (size_t)P->nchains * (PT_HDR + b->dev.nwords + 2 * SSE_MAX_CHUNKS + b->dev.cap);
     HIP_TRY(b, hipMalloc((void **)&P->d_pack_s, 4 * P->pack_cap_words));
     HIP_TRY(b, hipMalloc((void **)&P->d_pack_r, 4 * P->pack_cap_words));
@@ -318,16 +349,14 @@ int isingmc_pt_create(isingmc_batch *b, const isingmc_pt_layout *lay) {
         HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
         b->dev.ham_row = P->d_ham_row;
         HIP_TRY(b, hipMalloc((void **)&P->d_counts, 4 * (size_t)R * b->dev.Nb));
-        const uint32_t E = b->dev.E, K = P->nchains, HS = E + 2; // a Hamiltonian row: [E] couplings, Gamma, h
-        auto Jrow = [&](uint32_t row, std::vector<double> &out, size_t at) { pt_ham_row(b, row, out.data() + at); };
-        std::vector<double> first((size_t)K * HS), last((size_t)K * HS);
-        for (uint32_t k = 0; k < K; ++k) { Jrow(k, first, (size_t)k * HS); Jrow((tper - 1) * K + k, last, (size_t)k * HS); }
-        P->J_prev_last.assign((size_t)K * HS, 0.0); P->J_next_first.assign((size_t)K * HS, 0.0);
-        if (P->world > 1) {
-            const int prev = (int)P->rank - 1, next = (int)P->rank + 1;
-            if (prev >= 0 && P->tr.sendrecv(P->tr.ctx, prev, first.data(), 8 * first.size(), P->J_prev_last.data(), 8 * first.size())) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
-            if (next < (int)P->world && P->tr.sendrecv(P->tr.ctx, next, last.data(), 8 * last.size(), P->J_next_first.data(), 8 * last.size())) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
-        }
+        const uint32_t K = P->nchains, HS = b->dev.E + 2; // a Hamiltonian row: [E] couplings, Gamma, h
+        const size_t edge = (size_t)K * HS;               // one temperature's rows: what a neighbour needs
+        P->ham.assign((size_t)(R + 2 * K) * HS, 0.0);
+        for (uint32_t ls = 0; ls < R; ++ls) pt_ham_row(b, ls, P->ham.data() + (size_t)(K + ls) * HS);
+        // my first temperature goes to the lower neighbour, my last to the upper one; theirs fill the halo
+        const size_t mine[2] = {edge, (size_t)R * HS}, halo[2] = {0, (size_t)(R + K) * HS};
+        for (int s = 0; s < 2; ++s)
+            if (P->side[s].peer >= 0 && P->tr.sendrecv(P->tr.ctx, P->side[s].peer, P->ham.data() + mine[s], 8 * edge, P->ham.data() + halo[s], 8 * edge)) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
     }
     if (P->world == 1 && !P->hams_differ) { // every pair is interior and weighs one Hamiltonian: the decisions run on the device
         HIP_TRY(b, hipMalloc((void **)&P->d_slot_of, 4 * (size_t)R));
@@ -372,12 +401,18 @@ int isingmc_pt_timesteps(isingmc_batch *b, uint64_t t, uint32_t sampling_freq, u
     return isingmc_timesteps(b, t, br.data(), sampling_freq, flags);
 }
 
-int isingmc_pt_nccl_unique_id(isingmc_nccl_id *out) {
-    if (!out) return ISINGMC_EINVAL;
+// RCCL: the copy the process already uses (e.g. torch's), if any, then the loader's, then ROCm's
+static void *pt_open_rccl() {
     void *lib = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);
     if (!lib) lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
     if (!lib) lib = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
     if (!lib) lib = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_LOCAL);
+    return lib;
+}
+
+int isingmc_pt_nccl_unique_id(isingmc_nccl_id *out) {
+    if (!out) return ISINGMC_EINVAL;
+    void *lib = pt_open_rccl();
     if (!lib) return ISINGMC_ENODEVICE;
     auto f = reinterpret_cast<int (*)(isingmc_nccl_id *)>(dlsym(lib, "ncclGetUniqueId"));
     return (f && f(out) == 0) ? ISINGMC_OK : ISINGMC_ENODEVICE;
@@ -387,10 +422,7 @@ int isingmc_pt_attach_nccl(isingmc_batch *b, const isingmc_nccl_id *id) {
     if (!b || !b->pt || !id) { if (b) b->err = "isingmc_pt_create first"; return ISINGMC_EINVAL; }
     PtState *P = b->pt;
     HIP_TRY(b, hipSetDevice(b->device));
-    void *lib = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD); // the copy the process already uses (e.g. torch's), if any
-    if (!lib) lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
-    if (!lib) lib = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-    if (!lib) lib = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_LOCAL);
+    void *lib = pt_open_rccl();
     if (!lib) { b->err = "librccl.so not found"; return ISINGMC_ENODEVICE; }
     P->nccl_lib = lib;
     P->p_send = reinterpret_cast<decltype(P->p_send)>(dlsym(lib, "ncclSend"));
@@ -448,187 +480,197 @@ int isingmc_pt_set_state(isingmc_batch *b, const uint32_t *slot_of_replica, cons
     return ISINGMC_OK;
 }
 
+// ---- isingmc_pt_step in parts: the device leg, or the host leg's read, equalise, two phases (counts, decisions, moves), finish ----
+
+// The device leg: label swaps only, the op-strings (and any flip bytes still pending on them) are not touched.  Nothing is read back
+// unless the caller wants this step's count.
+static int pt_step_on_device(isingmc_batch *b, uint64_t *nswaps) {
+    PtState *P = b->pt;
+    const uint32_t K = P->nchains;
+    if (P->ntemps <= 1) { P->step++; return ISINGMC_OK; }
+    PtDev D{};
+    D.slot_of = P->d_slot_of; D.at = P->d_at; D.result = P->d_result; D.betas = P->d_betas; D.beta_r = P->d_beta_r; D.total = P->d_total;
+    D.acc_row = b->acc_follow_slots ? b->d_acc_row : nullptr; // per-slot accumulators (isingmc_set_accumulator_rows with the slots) follow the labels
+    D.K = K; D.T = P->ntemps; D.seed = P->seed; D.step = P->step;
+    hipLaunchKernelGGL(pt_decide_kernel, dim3(1), dim3(K < 256 ? ((K + 63) / 64) * 64 : 256), 0, b->stream, b->dev, D);
+    HIP_TRY(b, hipGetLastError());
+    P->step++;
+    P->host_stale = true;
+    if (nswaps) { // one small read-back
+        uint32_t res[2] = {0u, 0u};
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        HIP_TRY(b, hipMemcpy(res, P->d_result, 8, hipMemcpyDeviceToHost));
+        if (res[1]) { b->err = "cutoff exceeds capacity"; return ISINGMC_ECAPACITY; }
+        *nswaps += res[0];
+    }
+    return ISINGMC_OK;
+}
+
+// what the host leg carries from part to part
+struct PtHostStep {
+    std::vector<uint32_t> n, cut; // [R] operator count and cutoff of local replica r
+    std::vector<uint32_t> at;     // [R] replica at local slot ls (the inverse of slot_of)
+    std::vector<uint32_t> maxcut; // [nchains] the chain's cutoff after equalising
+    std::vector<uint32_t> counts; // [R][Nb] bond counts            } only when the Hamiltonians differ between temperatures
+    std::vector<double> rel;      // [R] see pt_relative_weights    }
+    uint64_t swaps = 0;
+};
+
+static int pt_read_counts(isingmc_batch *b, PtHostStep &S) {
+    const PtState *P = b->pt;
+    const uint32_t R = b->dev.R;
+    S.n.resize(R); S.cut.resize(R); S.at.resize(R);
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    HIP_TRY(b, hipMemcpy(S.n.data(), b->dev.n, 4 * (size_t)R, hipMemcpyDeviceToHost));
+    HIP_TRY(b, hipMemcpy(S.cut.data(), b->dev.cutoff, 4 * (size_t)R, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < R; ++r) S.at[P->slot_of[r] - P->rank * R] = r;
+    return ISINGMC_OK;
+}
+
+// every chain gets one cutoff over all its temperatures (:129-137): the maximum, over the ranks too
+static int pt_equalise_cutoffs(isingmc_batch *b, PtHostStep &S) {
+    PtState *P = b->pt;
+    const uint32_t R = b->dev.R, K = P->nchains;
+    S.maxcut.assign(K, 0u);
+    for (uint32_t r = 0; r < R; ++r) { const uint32_t k = P->slot_of[r] % K; if (S.cut[r] > S.maxcut[k]) S.maxcut[k] = S.cut[r]; }
+    if (P->world > 1) if (const int rc = pt_allreduce_max(b, S.maxcut)) return rc;
+    for (uint32_t r = 0; r < R; ++r) {
+        const uint32_t k = P->slot_of[r] % K;
+        if (S.maxcut[k] > b->dev.cap) { b->err = "cutoff exceeds capacity"; return ISINGMC_ECAPACITY; }
+        S.cut[r] = S.maxcut[k];
+    }
+    HIP_TRY(b, hipMemcpy(b->dev.cutoff, S.cut.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+    return ISINGMC_OK;
+}
+
+// bond counts of every local configuration (again in the second phase: a boundary swap of the first one replaced configurations)
+static int pt_bond_counts(isingmc_batch *b, PtHostStep &S) {
+    const uint32_t R = b->dev.R;
+    hipLaunchKernelGGL(pt_bond_count_kernel, dim3(R), dim3(256), 0, b->stream, b->dev, b->pt->d_counts);
+    S.counts.resize((size_t)R * b->dev.Nb);
+    HIP_TRY(b, hipMemcpyAsync(S.counts.data(), b->pt->d_counts, 4 * S.counts.size(), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    return ISINGMC_OK;
+}
+
+// rel[r]: the weight of local replica r under the Hamiltonian of the partner of its pair in this phase, relative to its own slot's
+// (1 at an end of the ladder).  Pairs of a phase are disjoint: one weight per replica.
+static void pt_relative_weights(const isingmc_batch *b, int phase, PtHostStep &S) {
+    const PtState *P = b->pt;
+    const uint32_t R = b->dev.R, K = P->nchains, HS = b->dev.E + 2;
+    S.rel.resize(R);
+    for (uint32_t ls = 0; ls < R; ++ls) {
+        const uint32_t r = S.at[ls], t = P->rank * P->tper + ls / K;
+        const bool up = pt_in_phase(pt_a_first(pt_chain(P->seed, P->step, ls % K), PtHostDraw{}), phase, t); // the partner sits above
+        const double *own = P->ham.data() + (size_t)(K + ls) * HS, *partner = up ? own + (size_t)K * HS : own - (size_t)K * HS;
+        S.rel[r] = (up ? t + 1 < P->ntemps : t > 0) ? pt_relative_weight(own, partner, S.counts.data() + (size_t)r * b->dev.Nb, b->dev.E, b->dev.N, b->dev.has_long != 0u) : 1.0;
+    }
+}
+
+// the boundary walkers' operator counts (and relative weights) go to both neighbours, theirs come back
+static int pt_exchange_counts(isingmc_batch *b, const PtHostStep &S) {
+    PtState *P = b->pt;
+    const uint32_t K = P->nchains;
+    for (int s = 0; s < 2; ++s)
+        for (uint32_t k = 0; k < K && P->side[s].peer >= 0; ++k) {
+            const uint32_t r = S.at[(s ? (P->tper - 1) * K : 0u) + k];
+            P->side[s].sent[k] = {S.n[r], 0u, P->hams_differ ? S.rel[r] : 1.0};
+        }
+    const size_t words = 4 * (size_t)K;
+    uint32_t *ds = P->d_small, *dr = P->d_small + words;
+    for (int turn = 0; turn < 2; ++turn) {
+        PtSide &N = pt_turn_side(P, turn);
+        if (N.peer < 0) continue;
+        if (P->comm) HIP_TRY(b, hipMemcpyAsync(ds, N.sent.data(), 4 * words, hipMemcpyHostToDevice, b->stream));
+        if (const int rc = pt_sendrecv(b, N.peer, ds, dr, N.sent.data(), N.got.data(), words)) return rc;
+        if (P->comm) {
+            HIP_TRY(b, hipMemcpyAsync(N.got.data(), dr, 4 * words, hipMemcpyDeviceToHost, b->stream));
+            HIP_TRY(b, hipStreamSynchronize(b->stream));
+        }
+    }
+    return ISINGMC_OK;
+}
+
+// isingmc_pt_plan_phase on this rank's view; a walker that is about to arrive brings its operator count
+static int pt_decide_phase(isingmc_batch *b, int phase, PtHostStep &S) {
+    PtState *P = b->pt;
+    isingmc_pt_phase v{};
+    v.struct_size = sizeof(v);
+    v.rank = P->rank; v.world = P->world; v.tper = P->tper; v.nchains = P->nchains; v.phase = (uint32_t)phase;
+    v.betas = P->betas.data(); v.seed = P->seed; v.step = P->step;
+    v.n = S.n.data(); v.rel = P->hams_differ ? S.rel.data() : nullptr;
+    v.cutoff = S.maxcut.data(); v.fixed_words = PT_HDR + b->dev.nwords + 2 * SSE_MAX_CHUNKS;
+    v.slot_of = P->slot_of.data(); v.at = S.at.data();
+    for (int s = 0; s < 2; ++s) { v.from[s] = P->side[s].got.data(); v.items[s] = P->side[s].items.data(); }
+    if (isingmc_pt_plan_phase(&v)) { b->err = "bad tempering phase"; return ISINGMC_EINVAL; }
+    S.swaps += v.nswaps;
+    for (int s = 0; s < 2; ++s) {
+        PtSide &N = P->side[s];
+        N.nitems = v.nitems[s]; N.words = v.words[s];
+        for (uint32_t i = 0; i < N.nitems; ++i) { const uint32_t r = N.items[3 * i]; S.n[r] = N.got[P->slot_of[r] % P->nchains].n; }
+    }
+    return ISINGMC_OK;
+}
+
+// accepted boundary swaps: the two configurations change ranks
+static int pt_move_configurations(isingmc_batch *b) {
+    PtState *P = b->pt;
+    for (int turn = 0; turn < 2; ++turn) {
+        const PtSide &N = pt_turn_side(P, turn);
+        if (N.peer < 0 || N.nitems == 0) continue;
+        const size_t words = N.words;
+        uint32_t *d_it = P->d_items; // (at most one item per chain and turn)
+        HIP_TRY(b, hipMemcpyAsync(d_it, N.items.data(), 4 * 3 * (size_t)N.nitems, hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(pt_pack_kernel, dim3(N.nitems), dim3(256), 0, b->stream, b->dev, P->d_rid, d_it, P->d_pack_s);
+        if (!P->comm) {
+            P->h_pack_s.resize(words); P->h_pack_r.resize(words);
+            HIP_TRY(b, hipMemcpyAsync(P->h_pack_s.data(), P->d_pack_s, 4 * words, hipMemcpyDeviceToHost, b->stream));
+            HIP_TRY(b, hipStreamSynchronize(b->stream));
+        }
+        if (const int rc = pt_sendrecv(b, N.peer, P->d_pack_s, P->d_pack_r, P->h_pack_s.data(), P->h_pack_r.data(), words)) return rc;
+        if (!P->comm) HIP_TRY(b, hipMemcpyAsync(P->d_pack_r, P->h_pack_r.data(), 4 * words, hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(pt_unpack_kernel, dim3(N.nitems), dim3(256), 0, b->stream, b->dev, P->d_rid, d_it, P->d_pack_r);
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    if (P->side[0].nitems || P->side[1].nitems) HIP_TRY(b, hipMemcpy(P->rid.data(), P->d_rid, 4 * (size_t)b->dev.R, hipMemcpyDeviceToHost));
+    return ISINGMC_OK;
+}
+
+// the bond-table rows and the accumulator rows follow the slots (as the decision kernel does), then the counters
+static int pt_finish(isingmc_batch *b, uint64_t swaps, uint64_t *nswaps) {
+    PtState *P = b->pt;
+    const uint32_t R = b->dev.R;
+    if (P->hams_differ) {
+        for (uint32_t r = 0; r < R; ++r) b->ham_row_host[r] = P->slot_of[r] - P->rank * R;
+        HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+    }
+    if (b->acc_follow_slots) HIP_TRY(b, hipMemcpy(b->d_acc_row, P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+    P->step++;
+    P->total_swaps += swaps;
+    if (nswaps) *nswaps += swaps;
+    return ISINGMC_OK;
+}
+
 // One tempering step of every chain (tempering_container.rs:121-149).  Adds the number of swaps this rank took part in
 // as the LOWER temperature's owner (so that the sum over ranks counts every swap once) to *nswaps.
 int isingmc_pt_step(isingmc_batch *b, uint64_t *nswaps) {
     if (!b || !b->pt) { if (b) b->err = "isingmc_pt_create first"; return ISINGMC_EINVAL; }
     PtState *P = b->pt;
     HIP_TRY(b, hipSetDevice(b->device));
-    const uint32_t R = b->dev.R, K = P->nchains, T = P->ntemps, tper = P->tper, E = b->dev.E, Nb = b->dev.Nb;
-    if (P->dev_decide) { // label swaps only: the op-strings (and any flip bytes still pending on them) are not touched
-        if (T <= 1) { P->step++; return ISINGMC_OK; }
-        PtDev D{};
-        D.slot_of = P->d_slot_of; D.at = P->d_at; D.result = P->d_result; D.betas = P->d_betas; D.beta_r = P->d_beta_r; D.total = P->d_total;
-        D.acc_row = b->acc_follow_slots ? b->d_acc_row : nullptr; // per-slot accumulators (isingmc_set_accumulator_rows with the slots) follow the labels
-        D.K = K; D.T = T; D.key0 = (uint32_t)P->seed; D.key1 = (uint32_t)(P->seed >> 32); D.step = P->step;
-        hipLaunchKernelGGL(pt_decide_kernel, dim3(1), dim3(K < 256 ? ((K + 63) / 64) * 64 : 256), 0, b->stream, b->dev, D);
-        HIP_TRY(b, hipGetLastError());
-        P->step++;
-        P->host_stale = true;
-        if (nswaps) { // the caller wants this step's count: one small read-back
-            uint32_t res[2] = {0u, 0u};
-            HIP_TRY(b, hipStreamSynchronize(b->stream));
-            HIP_TRY(b, hipMemcpy(res, P->d_result, 8, hipMemcpyDeviceToHost));
-            if (res[1]) { b->err = "cutoff exceeds capacity"; return ISINGMC_ECAPACITY; }
-            *nswaps += res[0];
-        }
-        return ISINGMC_OK;
-    }
-    { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
-    const uint32_t t_lo = P->rank * tper, t_hi = t_lo + tper; // my temperature block [t_lo, t_hi)
-    const int prev = P->rank > 0 ? (int)P->rank - 1 : -1, next = P->rank + 1 < P->world ? (int)P->rank + 1 : -1;
-    uint64_t swaps = 0;
-    if (T <= 1) { P->step++; return ISINGMC_OK; }
-    std::vector<uint32_t> n(R), cut(R);
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    HIP_TRY(b, hipMemcpy(n.data(), b->dev.n, 4 * (size_t)R, hipMemcpyDeviceToHost));
-    HIP_TRY(b, hipMemcpy(cut.data(), b->dev.cutoff, 4 * (size_t)R, hipMemcpyDeviceToHost));
-    // replica at a local slot
-    std::vector<uint32_t> at(R);
-    auto rebuild_at = [&]() { for (uint32_t r = 0; r < R; ++r) at[P->slot_of[r] - t_lo * K] = r; };
-    rebuild_at();
-    // ---- equalise the cutoffs of every chain over all temperatures (:129-137): max over the ranks ----
-    std::vector<uint32_t> maxcut(K, 0u);
-    for (uint32_t r = 0; r < R; ++r) { const uint32_t k = P->slot_of[r] % K; if (cut[r] > maxcut[k]) maxcut[k] = cut[r]; }
-    if (P->world > 1) {
-        if (P->comm) {
-            HIP_TRY(b, hipMemcpyAsync(P->d_small, maxcut.data(), 4 * (size_t)K, hipMemcpyHostToDevice, b->stream));
-            if (P->p_allreduce(P->d_small, P->d_small, K, (int)ncclUint32, (int)ncclMax, P->comm, b->stream)) { b->err = "ncclAllReduce failed"; return ISINGMC_ENODEVICE; }
-            HIP_TRY(b, hipMemcpyAsync(maxcut.data(), P->d_small, 4 * (size_t)K, hipMemcpyDeviceToHost, b->stream));
-            HIP_TRY(b, hipStreamSynchronize(b->stream));
-        } else if (P->tr.allreduce_max_u32(P->tr.ctx, maxcut.data(), K)) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
-    }
-    for (uint32_t r = 0; r < R; ++r) {
-        const uint32_t k = P->slot_of[r] % K;
-        if (maxcut[k] > b->dev.cap) { b->err = "cutoff exceeds capacity"; return ISINGMC_ECAPACITY; }
-        cut[r] = maxcut[k];
-    }
-    HIP_TRY(b, hipMemcpy(b->dev.cutoff, cut.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
-    std::vector<uint32_t> counts; // bond counts of every local configuration (only when the Hamiltonians differ between temperatures)
-    const uint32_t HS = E + 2;
-    std::vector<double> Ja(HS), Jb(HS);
-    // relative weight of local replica r (at local slot ls) towards the Hamiltonian of the slot above (+1) or below (-1)
-    auto relw = [&](uint32_t r, uint32_t ls, int dir) -> double {
-        if (!P->hams_differ) return 1.0;
-        const uint32_t k = ls % K, tl = ls / K;
-        pt_ham_row(b, ls, Ja.data());
-        if (dir > 0) { if (tl + 1 < tper) pt_ham_row(b, ls + K, Jb.data()); else for (uint32_t e = 0; e < HS; ++e) Jb[e] = P->J_next_first[(size_t)k * HS + e]; }
-        else { if (tl > 0) pt_ham_row(b, ls - K, Jb.data()); else for (uint32_t e = 0; e < HS; ++e) Jb[e] = P->J_prev_last[(size_t)k * HS + e]; }
-        return pt_relative_weight(Ja.data(), Jb.data(), counts.data() + (size_t)r * Nb, E, b->dev.N, b->dev.has_long != 0u);
-    };
-    // order coin per chain (gen_bool(0.5), :140)
-    const uint32_t key[2] = {(uint32_t)P->seed, (uint32_t)(P->seed >> 32)};
-    std::vector<uint8_t> a_first(K);
-    for (uint32_t k = 0; k < K; ++k) {
-        const uint32_t ctr[4] = {0u, (uint32_t)P->step, k, (SSE_TAG_PT << 24) | (uint32_t)((P->step >> 32) & 0xFFFFFFu)};
-        uint32_t o[4];
-        host_philox(ctr, key, o);
-        a_first[k] = (o[0] >> 31) != 0u;
-    }
-    auto decide = [&](uint32_t k, uint32_t t, uint32_t na, uint32_t nb2, double ra, double rb) -> bool {
-        const uint32_t ctr[4] = {1u + t, (uint32_t)P->step, k, (SSE_TAG_PT << 24) | (uint32_t)((P->step >> 32) & 0xFFFFFFu)};
-        uint32_t o[4];
-        host_philox(ctr, key, o);
-        const double u = (double)o[0] * (1.0 / 4294967296.0);
-        return pt_accept(P->betas[t], P->betas[t + 1], na, nb2, P->hams_differ ? ra * rb : 1.0, u);
-    };
-    struct Wire { uint32_t n; uint32_t pad; double rel; };
+    if (P->dev_decide) return pt_step_on_device(b, nswaps);
+    int rc = ensure_materialized(b);
+    if (rc) return rc;
+    if (P->ntemps <= 1) { P->step++; return ISINGMC_OK; }
+    PtHostStep S;
+    if ((rc = pt_read_counts(b, S)) || (rc = pt_equalise_cutoffs(b, S))) return rc;
     for (int phase = 0; phase < 2; ++phase) {
-        if (P->hams_differ) { // (again in the second phase: a boundary swap of the first one replaced configurations)
-            hipLaunchKernelGGL(pt_bond_count_kernel, dim3(R), dim3(256), 0, b->stream, b->dev, P->d_counts);
-            counts.resize((size_t)R * Nb);
-            HIP_TRY(b, hipMemcpyAsync(counts.data(), P->d_counts, 4 * counts.size(), hipMemcpyDeviceToHost, b->stream));
-            HIP_TRY(b, hipStreamSynchronize(b->stream));
+        if (P->hams_differ) {
+            if ((rc = pt_bond_counts(b, S))) return rc;
+            pt_relative_weights(b, phase, S);
         }
-        // boundary walkers of this phase: for chain k the pair (t, t+1) is in the phase's set iff (t even) == (set a)
-        auto in_set = [&](uint32_t k, uint32_t t) { const bool set_a = (phase == 0) ? a_first[k] : !a_first[k]; return ((t & 1u) == 0u) == set_a; };
-        // ---- exchange the operator counts (and relative weights) of the boundary walkers with both neighbours ----
-        std::vector<Wire> s_prev(K), r_prev(K), s_next(K), r_next(K);
-        for (uint32_t k = 0; k < K; ++k) {
-            const uint32_t rf = at[k], rl = at[(tper - 1) * K + k];
-            s_prev[k] = {n[rf], 0u, prev >= 0 ? relw(rf, k, -1) : 1.0};
-            s_next[k] = {n[rl], 0u, next >= 0 ? relw(rl, (tper - 1) * K + k, +1) : 1.0};
-        }
-        static_assert(sizeof(Wire) == 16, "wire format");
-        int rc;
-        // (even ranks talk to their upper neighbour first: the host-staged transport is blocking)
-        for (int turn = 0; turn < 2; ++turn) {
-            const bool up = ((P->rank & 1u) == 0u) == (turn == 0);
-            if (up) { if ((rc = pt_exchange_small(b, next, reinterpret_cast<const uint32_t *>(s_next.data()), reinterpret_cast<uint32_t *>(r_next.data()), 4 * (size_t)K))) return rc; }
-            else if ((rc = pt_exchange_small(b, prev, reinterpret_cast<const uint32_t *>(s_prev.data()), reinterpret_cast<uint32_t *>(r_prev.data()), 4 * (size_t)K))) return rc;
-        }
-        // ---- decisions ----
-        std::vector<uint32_t> items_next, items_prev; // accepted boundary swaps: (replica, word offset in the message, cutoff)
-        size_t off_next = 0, off_prev = 0;
-        for (uint32_t k = 0; k < K; ++k) {
-            // interior pairs
-            for (uint32_t t = t_lo; t + 1 < t_hi; ++t) {
-                if (!in_set(k, t)) continue;
-                const uint32_t la = (t - t_lo) * K + k, lb = la + K;
-                const uint32_t ra_ = at[la], rb_ = at[lb];
-                if (decide(k, t, n[ra_], n[rb_], relw(ra_, la, +1), relw(rb_, lb, -1))) {
-                    std::swap(P->slot_of[ra_], P->slot_of[rb_]);
-                    at[la] = rb_; at[lb] = ra_;
-                    swaps++;
-                }
-            }
-            const size_t words = PT_HDR + b->dev.nwords + 2 * SSE_MAX_CHUNKS + maxcut[k];
-            // boundary pair with the next rank: (t_hi - 1, t_hi)
-            if (next >= 0 && in_set(k, t_hi - 1)) {
-                const uint32_t la = (tper - 1) * K + k, ra_ = at[la];
-                if (decide(k, t_hi - 1, n[ra_], r_next[k].n, s_next[k].rel, r_next[k].rel)) {
-                    items_next.insert(items_next.end(), {ra_, (uint32_t)off_next, maxcut[k]});
-                    off_next += words;
-                    n[ra_] = r_next[k].n;
-                    swaps++; // counted by the owner of the lower temperature
-                }
-            }
-            // boundary pair with the previous rank: (t_lo - 1, t_lo)
-            if (prev >= 0 && in_set(k, t_lo - 1)) {
-                const uint32_t rb_ = at[k];
-                if (decide(k, t_lo - 1, r_prev[k].n, n[rb_], r_prev[k].rel, s_prev[k].rel)) {
-                    items_prev.insert(items_prev.end(), {rb_, (uint32_t)off_prev, maxcut[k]});
-                    off_prev += words;
-                    n[rb_] = r_prev[k].n;
-                }
-            }
-        }
-        // ---- accepted boundary swaps: the two configurations change ranks ----
-        for (int turn = 0; turn < 2; ++turn) {
-            const bool up = ((P->rank & 1u) == 0u) == (turn == 0);
-            const std::vector<uint32_t> &items = up ? items_next : items_prev;
-            const size_t words = up ? off_next : off_prev;
-            const int peer = up ? next : prev;
-            if (peer < 0 || items.empty()) continue;
-            const uint32_t nitems = (uint32_t)(items.size() / 3);
-            uint32_t *d_it = P->d_items; // (at most one item per chain and turn)
-            HIP_TRY(b, hipMemcpyAsync(d_it, items.data(), 4 * items.size(), hipMemcpyHostToDevice, b->stream));
-            hipLaunchKernelGGL(pt_pack_kernel, dim3(nitems), dim3(256), 0, b->stream, b->dev, P->d_rid, d_it, P->d_pack_s);
-            if (P->comm) {
-                if (P->p_gstart() || P->p_send(P->d_pack_s, words, (int)ncclUint32, peer, P->comm, b->stream) || P->p_recv(P->d_pack_r, words, (int)ncclUint32, peer, P->comm, b->stream) || P->p_gend()) {
-                    b->err = "RCCL send/recv failed"; return ISINGMC_ENODEVICE;
-                }
-            } else {
-                P->h_pack_s.resize(words); P->h_pack_r.resize(words);
-                HIP_TRY(b, hipMemcpyAsync(P->h_pack_s.data(), P->d_pack_s, 4 * words, hipMemcpyDeviceToHost, b->stream));
-                HIP_TRY(b, hipStreamSynchronize(b->stream));
-                if (P->tr.sendrecv(P->tr.ctx, peer, P->h_pack_s.data(), 4 * words, P->h_pack_r.data(), 4 * words)) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
-                HIP_TRY(b, hipMemcpyAsync(P->d_pack_r, P->h_pack_r.data(), 4 * words, hipMemcpyHostToDevice, b->stream));
-            }
-            hipLaunchKernelGGL(pt_unpack_kernel, dim3(nitems), dim3(256), 0, b->stream, b->dev, P->d_rid, d_it, P->d_pack_r);
-            HIP_TRY(b, hipStreamSynchronize(b->stream));
-        }
-        if (!items_next.empty() || !items_prev.empty()) HIP_TRY(b, hipMemcpy(P->rid.data(), P->d_rid, 4 * (size_t)R, hipMemcpyDeviceToHost));
+        if ((rc = pt_exchange_counts(b, S)) || (rc = pt_decide_phase(b, phase, S)) || (rc = pt_move_configurations(b))) return rc;
     }
-    if (P->hams_differ) { // the bond-table row follows the slot
-        for (uint32_t r = 0; r < R; ++r) b->ham_row_host[r] = P->slot_of[r] - t_lo * K;
-        HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
-    }
-    if (b->acc_follow_slots) HIP_TRY(b, hipMemcpy(b->d_acc_row, P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice)); // as the decision kernel does
-    P->step++;
-    P->total_swaps += swaps;
-    if (nswaps) *nswaps += swaps;
-    return ISINGMC_OK;
+    return pt_finish(b, S.swaps, nswaps);
 }
 
 } // extern "C"

@@ -38,12 +38,12 @@ def pt_decide(seed, step, nchains, ntemps, betas, n_of_config, config_at):
     return int(sw.value)
 
 
-class _Collective:
-    """all-gather of small integer arrays: torch.distributed when initialised (nccl = RCCL on ROCm), else local."""
+class _Ranks:
+    """torch.distributed when it is initialised with more than one rank (nccl = RCCL on ROCm), else a single process: `dist` (the
+    module or None), rank, world, and the device that tensors of a collective live on."""
 
     def __init__(self, device=None):
         self.dist = None
-        self.device = device
         try:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -52,13 +52,23 @@ class _Collective:
             self.dist = None
         self.rank = self.dist.get_rank() if self.dist else 0
         self.world = self.dist.get_world_size() if self.dist else 1
+        self._device = device
+
+    @property
+    def device(self):
+        if self._device is not None:
+            return self._device
+        return "cuda" if self.dist and self.dist.get_backend() == "nccl" else "cpu"
+
+
+class _Collective(_Ranks):
+    """all-gather of small integer arrays over the ranks, else local."""
 
     def all_gather_u32(self, local):
         if not self.dist:
             return local.copy()
         import torch
-        dev = self.device if self.device is not None else ("cuda" if self.dist.get_backend() == "nccl" else "cpu")
-        t = torch.from_numpy(local.astype(np.int64)).to(dev)
+        t = torch.from_numpy(local.astype(np.int64)).to(self.device)
         outs = [torch.empty_like(t) for _ in range(self.world)]
         self.dist.all_gather(outs, t)
         return torch.cat(outs).cpu().numpy().astype(np.uint32)
@@ -67,8 +77,7 @@ class _Collective:
         if not self.dist:
             return local.copy()
         import torch
-        dev = self.device if self.device is not None else ("cuda" if self.dist.get_backend() == "nccl" else "cpu")
-        t = torch.from_numpy(local.astype(np.int64)).to(dev)
+        t = torch.from_numpy(local.astype(np.int64)).to(self.device)
         self.dist.all_reduce(t)
         return t.cpu().numpy().astype(np.uint64)
 
@@ -186,15 +195,8 @@ class NativeTemperingContainer:
         self.g = graph
         self.betas = np.ascontiguousarray(np.asarray(betas, dtype=np.float64))
         self.ntemps, self.nchains, self.flags = len(self.betas), int(nchains), int(flags)
-        self.dist = None
-        try:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                self.dist = dist
-        except Exception:
-            self.dist = None
-        self.rank = self.dist.get_rank() if self.dist else 0
-        self.world = self.dist.get_world_size() if self.dist else 1
+        self._ranks = _Ranks()
+        self.dist, self.rank, self.world = self._ranks.dist, self._ranks.rank, self._ranks.world
         self._cb = (_PT_SENDRECV(self._sendrecv), _PT_ALLMAX(self._allmax))  # keep the callbacks alive
         self._tr = _PtTransport(ctx=None, sendrecv=self._cb[0], allreduce_max_u32=self._cb[1])
         lay = _PtLayout(struct_size=C.sizeof(_PtLayout), ntemps=self.ntemps, nchains=self.nchains, rank=self.rank, world=self.world,
@@ -234,14 +236,11 @@ class NativeTemperingContainer:
         return getattr(self, name)
 
     # ---- host-staged transport over torch.distributed (CPU tensors with gloo, device tensors with nccl) ----
-    def _tensor_dev(self):
-        return "cuda" if self.dist.get_backend() == "nccl" else "cpu"
-
     def _sendrecv(self, ctx, peer, sbuf, sbytes, rbuf, rbytes):
         try:
             import torch
-            ts = torch.from_numpy(np.ctypeslib.as_array(C.cast(sbuf, C.POINTER(C.c_uint8)), shape=(sbytes,)).copy()).to(self._tensor_dev())
-            tr = torch.empty(rbytes, dtype=torch.uint8, device=self._tensor_dev())
+            ts = torch.from_numpy(np.ctypeslib.as_array(C.cast(sbuf, C.POINTER(C.c_uint8)), shape=(sbytes,)).copy()).to(self._ranks.device)
+            tr = torch.empty(rbytes, dtype=torch.uint8, device=self._ranks.device)
             ops = [self.dist.P2POp(self.dist.isend, ts, peer), self.dist.P2POp(self.dist.irecv, tr, peer)]
             if self.rank > peer:
                 ops.reverse()
@@ -257,7 +256,7 @@ class NativeTemperingContainer:
         try:
             import torch
             a = np.ctypeslib.as_array(buf, shape=(count,))
-            t = torch.from_numpy(a.astype(np.int64)).to(self._tensor_dev())
+            t = torch.from_numpy(a.astype(np.int64)).to(self._ranks.device)
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
             a[:] = t.cpu().numpy().astype(np.uint32)
             return 0
@@ -273,7 +272,7 @@ class NativeTemperingContainer:
         nid = _NcclId()
         if self.rank == 0:
             self.g._check(self.g._lib.isingmc_pt_nccl_unique_id(C.byref(nid)))
-        t = torch.frombuffer(bytearray(C.string_at(C.byref(nid), 128)), dtype=torch.uint8).clone().to(self._tensor_dev() if self.dist else "cpu")
+        t = torch.frombuffer(bytearray(C.string_at(C.byref(nid), 128)), dtype=torch.uint8).clone().to(self._ranks.device)
         if self.dist:
             self.dist.broadcast(t, src=0)
         C.memmove(C.byref(nid), t.cpu().numpy().ctypes.data, 128)
@@ -321,7 +320,7 @@ class NativeTemperingContainer:
         if not self.dist:
             return self.total_swaps_local
         import torch
-        t = torch.tensor([self.total_swaps_local], dtype=torch.int64, device=self._tensor_dev())
+        t = torch.tensor([self.total_swaps_local], dtype=torch.int64, device=self._ranks.device)
         self.dist.all_reduce(t)
         return int(t.item())
 

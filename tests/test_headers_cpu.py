@@ -27,6 +27,14 @@ def test_the_shared_data_header_is_plain_cpp():
     assert p.returncode == 0, p.stderr
 
 
+def test_the_tempering_rule_header_is_plain_cpp():
+    """pt_rule.h is shared by the host, the decision kernel and a stand-alone test program: a host compiler without HIP takes it."""
+    p = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I.", "-x", "c++", "-"],
+                       input='#include "pt_rule.h"\nbool f() { return pt_a_first(pt_chain(1, 2, 3), PtHostDraw{}) && pt_accept(1.0, 2.0, 3, 4, 1.0, 0.5); }\n',
+                       cwd=_build.CSRC, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+
+
 KERNEL_HEADERS = {"sse_fast.hip.h", "sse_rvb.hip.h", "sse_rvb_split.hip.h", "sse_cluster.hip.h", "sse_sweep.hip.h",
                   "sse_diag.hip.h", "sse_cluster_pass.hip.h", "sse_unionfind.hip.h", "sse_loop.hip.h"}  # the last four: the passes behind sse_sweep.hip.h
 

@@ -7,7 +7,8 @@ Single GPU:   python tools/bench_tempering.py
 Several GPUs: python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 tools/bench_tempering.py [--rccl]
               (temperatures are sharded over the ranks; --rccl attaches the library's own RCCL communicator: ncclSend / ncclRecv
               on device buffers, one rank per GPU; without it the exchange is staged through torch.distributed)
---window B W : betas geometric in [B / W, B * W] instead of [beta-min, beta-max] (a grid on which 64x64 swaps are accepted)"""
+--window B W : betas geometric in [B / W, B * W] instead of [beta-min, beta-max] (a grid on which 64x64 swaps are accepted)
+--host-decisions : take the swap decisions on the host leg of isingmc_pt_step (set_device_decisions(False)) where the device would"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -23,6 +24,7 @@ ap.add_argument("--nchains", type=int, default=32); ap.add_argument("--beta-min"
 ap.add_argument("--beta-max", type=float, default=16.0); ap.add_argument("--equilibrate", type=int, default=60)
 ap.add_argument("--steps", type=int, default=20); ap.add_argument("--seed", type=int, default=1234)
 ap.add_argument("--rccl", action="store_true"); ap.add_argument("--window", type=float, nargs=2, default=None)
+ap.add_argument("--host-decisions", action="store_true")
 a = ap.parse_args()
 world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
 torch.cuda.set_device(local)
@@ -39,6 +41,8 @@ R = a.ntemps * a.nchains
 cap = 1 << int(np.ceil(np.log2(2.0 * a.beta_max * 5.2 * N + 4 * N)))
 g = im.QmcIsingGraph(lat.two_d_ferro(L), 1.0, 0.0, N, a.seed, nreplicas=R, capacity=cap, replica_offset=rank * R, device=local)
 tc = NativeTemperingContainer(g, betas, a.nchains, a.seed, flags=0)
+if a.host_decisions and tc.device_decisions:
+    tc.set_device_decisions(False)
 if a.rccl and world > 1:
     tc.attach_rccl()  # (never executed on hardware so far: run tools/rccl_selfcheck.py first on a multi-GPU node)
 for _ in range(a.equilibrate):
@@ -58,4 +62,4 @@ if rank == 0:
                       "swaps_per_step": (tc.get_total_swaps() - swaps0) / a.steps,
                       "spin_op_updates_per_s_this_rank": float(acc[:, 4].sum() + acc[:, 5].sum()) / dt,
                       "mean_cutoff": float(g.get_cutoff().mean()), "max_cutoff": int(g.get_cutoff().max()),
-                      "launch": g.launch_info(), "all_verified": bool(g.verify().all())}))
+                      "launch": g.launch_info(), "device_decisions": tc.device_decisions, "all_verified": bool(g.verify().all())}))

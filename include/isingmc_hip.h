@@ -204,6 +204,21 @@ int isingmc_set_epoch(isingmc_batch *b, const uint64_t *epochs);
 int isingmc_itime_magnetization(isingmc_batch *b, int64_t *sum_m, uint64_t *sum_m2, uint64_t *sum_abs_m);
 /* OpContainer::get_count (op_container.rs:129; fast_ops.rs:1281-1294) */
 int isingmc_get_bond_count(isingmc_batch *b, uint32_t r, uint32_t bond, uint32_t *out);
+/* itime_fold (fast_ops.rs:1296-1315; QmcStepper::imaginary_time_fold, qmc_ising.rs:815-821) of two-valued observables, every replica,
+ * one pass on the device.  Groups exactly as in isingmc_record_series (same validation, same flip convention: the observable's bit is
+ * parity(state bits of the group) ^ group_flip[g], 1 standing for +1).  x_g(p) = +1/-1 is the observable on the propagated state BEFORE
+ * slot p's op.
+ *   sum_all[r][g] = sum over p < cutoff[r] of x_g(p)
+ *   sum_occ[r][g] = the same sum over occupied slots only (ops[p] != 0)
+ * Either pointer may be NULL (not both).  Rows are replicas (not tempering slots).  Exact integers: x_g only changes at off-diagonal ops,
+ * and the fold is evaluated from those (csrc/sse_itime.h).  The batch is left as it was (pending cluster flips are brought into the
+ * op-strings first, as by isingmc_verify).  ISINGMC_ENOTIMPL, before anything is launched, when the groups' sums and bit arrays exceed
+ * LDS: 16 bytes per group and N / 2 bytes (about 9800 groups at N = 1024, 8600 at N = 32768); the message names the cap. */
+int isingmc_itime_groups(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars, const uint8_t *group_flip,
+                         int64_t *sum_all, int64_t *sum_occ);
+/* OpContainer::get_count (op_container.rs:129; fast_ops.rs:1281-1294) for every bond of every replica in one pass on the device:
+ * out[R][isingmc_num_bonds] */
+int isingmc_bond_counts(isingmc_batch *b, uint32_t *out);
 /* get_pth for every p (op_container.rs:127): words[cutoff] in the sse_format.h encoding */
 int isingmc_export_ops(isingmc_batch *b, uint32_t r, uint32_t *words, uint32_t nwords);
 /* FastOps::new_from_ops (fast_ops.rs:80-174): install an op-string (words[nwords], slot p = index) */

@@ -157,6 +157,8 @@ SYMBOLS = {
     "isingmc_record_read": (C.c_int, [_vp, _u32, _u32, _u32, _P(C.c_uint8)]),
     "isingmc_record_series": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _P(C.c_uint8), _u32, _u32, _P(_u32)]),
     "isingmc_record_autocorrelation": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _u32, _u32, _P(_f64)]),
+    "isingmc_itime_groups": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _P(C.c_uint8), _P(C.c_int64), _P(C.c_int64)]),
+    "isingmc_bond_counts": (C.c_int, [_vp, _P(_u32)]),
 }
 
 _LIB = None
@@ -408,6 +410,79 @@ class QmcIsingGraph:
         c = np.zeros(self.nreplicas, dtype=np.uint64)
         self._check(self._lib.isingmc_itime_magnetization(self._h, _ptr(a, C.c_int64), _ptr(b, C.c_uint64), _ptr(c, C.c_uint64)))
         return a, b, c
+
+    def itime_groups(self, groups, flips=None):
+        """imaginary_time_fold (qmc_ising.rs:815-821; fast_ops.rs:1296-1315) of two-valued observables for every replica, on the device
+        and in exact integers.  Observable g is parity(state bits of the variables groups[g]) ^ flips[g], bit 1 standing for +1, as in
+        record_series (autocorrelations.variable_groups / product_groups / bond_groups build the reference's three); x_g(p) is its
+        value +-1 on the propagated state before slot p's op.  Returns (sum_all, sum_occ), int64 [R][G]: the sums of x_g(p) over
+        p < cutoff, and over the occupied slots only."""
+        ng, start, vs = self._groups(groups)
+        fl = None if flips is None else np.ascontiguousarray(np.asarray(flips, dtype=np.uint8))
+        if fl is not None and fl.shape != (ng,):
+            raise IsingMcError(-1, "flips must hold one entry per group")
+        sum_all = np.zeros((self.nreplicas, ng), dtype=np.int64)
+        sum_occ = np.zeros((self.nreplicas, ng), dtype=np.int64)
+        self._check(self._lib.isingmc_itime_groups(self._h, ng, _ptr(start, C.c_uint32), _ptr(vs, C.c_uint32),
+                                                   _ptr(fl, C.c_uint8) if fl is not None else None,
+                                                   _ptr(sum_all, C.c_int64), _ptr(sum_occ, C.c_int64)))
+        return sum_all, sum_occ
+
+    def bond_counts(self):
+        """OpContainer::get_count (op_container.rs:129) of every bond of every replica, counted on the device: uint32 [R][num_bonds]."""
+        out = np.zeros((self.nreplicas, self.num_bonds()), dtype=np.uint32)
+        self._check(self._lib.isingmc_bond_counts(self._h, _ptr(out, C.c_uint32)))
+        return out
+
+    def itime_average(self, groups, flips=None):
+        """Imaginary-time averages of the observables `groups` (itime_groups): sum_all / cutoff, float64 [R][G]."""
+        sum_all, _ = self.itime_groups(groups, flips)
+        return sum_all / self.get_cutoff().astype(np.float64)[:, None]
+
+    @staticmethod
+    def _kubo(s, count, beta):
+        """beta (S^2 + L) / (L (L + 1)) for the sum S of an observable with O^2 = 1 over L slots (beta where L = 0): Sandvik's
+        estimator of int_0^beta <O(tau) O(0)> dtau (Sandvik & Kurkijarvi, PRB 43, 5950; Sandvik, J. Phys. A 25, 3667)."""
+        s = np.asarray(s, dtype=np.float64)
+        L = np.asarray(count, dtype=np.float64)[:, None]
+        b = np.asarray(beta, dtype=np.float64)[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            chi = b * (s * s + L) / (L * (L + 1.0))
+        return np.where(L > 0, chi, b)
+
+    def itime_susceptibility(self, groups, beta, flips=None, slots="occupied"):
+        """Kubo susceptibility chi_g = int_0^beta <O_g(tau) O_g(0)> dtau of the observables `groups` from the current op-strings,
+        float64 [R][G] (one sample per replica: average over samples).  slots="occupied" sums over the n occupied slots,
+        beta (S^2 + n) / (n (n + 1)), beta for n = 0; slots="all" over the cutoff's M slots, beta (S^2 + M) / (M (M + 1))."""
+        if slots not in ("occupied", "all"):
+            raise IsingMcError(-1, 'slots must be "occupied" or "all"')
+        sum_all, sum_occ = self.itime_groups(groups, flips)
+        b = self._betas(beta)
+        if slots == "occupied":
+            return self._kubo(sum_occ, self.get_n(), b)
+        return self._kubo(sum_all, self.get_cutoff(), b)
+
+    def timesteps_measure_itime(self, t, beta, groups, sampling_freq=1, flags=None, flips=None):
+        """timesteps_measure (qmc_stepper.rs:43-95) for the imaginary-time observables: t timesteps in chunks of sampling_freq, the fold
+        of `groups` after each chunk.  Returns (average, chi_occupied, chi_all), each float64 [R][G]: the means over the t //
+        sampling_freq samples of itime_average and of itime_susceptibility in both forms, summed on the host.  The accumulators keep
+        summing (as with run())."""
+        freq = int(sampling_freq)
+        nsamp = int(t) // freq
+        b = self._betas(beta)
+        ng = len(groups)
+        avg = np.zeros((self.nreplicas, ng)); chi_occ = np.zeros_like(avg); chi_all = np.zeros_like(avg)
+        for _ in range(nsamp):
+            self.run(freq, b, sampling_freq=freq, flags=flags)
+            sum_all, sum_occ = self.itime_groups(groups, flips)
+            cut = self.get_cutoff()
+            avg += sum_all / cut.astype(np.float64)[:, None]
+            chi_occ += self._kubo(sum_occ, self.get_n(), b)
+            chi_all += self._kubo(sum_all, cut, b)
+        if int(t) % freq:
+            self.run(int(t) % freq, b, sampling_freq=freq, flags=flags)
+        k = max(nsamp, 1)
+        return avg / k, chi_occ / k, chi_all / k
 
     def imaginary_time_fold(self, fold_fn, init, r=0):
         """QmcStepper::imaginary_time_fold (qmc_ising.rs:815-821) with an arbitrary Python closure fold_fn(acc, state)

@@ -73,6 +73,9 @@ struct isingmc_batch : BatchGeometry {
     // scratch of the record's observables, grown on demand: observable groups, bit series [R][ngroups][Tw], autocorrelations [R][T]
     void *obs_groups = nullptr, *obs_series = nullptr, *obs_out = nullptr;
     size_t obs_groups_bytes = 0, obs_series_bytes = 0, obs_out_bytes = 0;
+    // scratch of the imaginary-time folds (isingmc_itime_groups, isingmc_bond_counts), grown on demand: results, groups, variable -> groups lists
+    void *itime_buf = nullptr;
+    size_t itime_buf_bytes = 0;
 };
 
 #define HIP_TRY(b, expr)                                                                              \

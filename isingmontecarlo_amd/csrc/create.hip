@@ -486,7 +486,7 @@ void isingmc_destroy(isingmc_batch *b) {
     for (void *p : b->allocs) (void)hipFree(p);
     if (b->dev.rvb_prod) (void)hipFree(b->dev.rvb_prod);
     if (b->dev.rvb_tbl) (void)hipFree(b->dev.rvb_tbl);
-    for (void *p : {(void *)b->rec, b->obs_groups, b->obs_series, b->obs_out}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)b->rec, b->obs_groups, b->obs_series, b->obs_out, b->itime_buf}) if (p) (void)hipFree(p);
     for (hipEvent_t ev : b->evpool) (void)hipEventDestroy(ev);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);

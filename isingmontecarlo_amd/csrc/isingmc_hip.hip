@@ -1,9 +1,12 @@
-// isingmc_hip.hip — the accessors of the C ABI (include/isingmc_hip.h) and their three kernels.  Creation lives in create.hip, the sweep
-// driver in driver.hip, parallel tempering in pt.hip, the sample record in record.hip.  There is no CPU compute fallback.
+// isingmc_hip.hip — the accessors of the C ABI (include/isingmc_hip.h) and their three kernels; the imaginary-time folds of group observables
+// and the bond counts are checked and staged here and launch itime.hip's kernel.  Creation lives in create.hip, the sweep driver in
+// driver.hip, parallel tempering in pt.hip, the sample record in record.hip.  There is no CPU compute fallback.
 #include "batch.hip.h"
 #include "sse_core.hip.h" // op_weight, the op-word fields
+#include "sse_launch.h"   // launch_itime and its LDS plan
 
 #include <algorithm>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -140,6 +143,73 @@ static int copy_up(isingmc_batch *b, T *dst, const T *in, size_t count, bool dra
     HIP_TRY(b, hipSetDevice(b->device));
     if (drain) HIP_TRY(b, hipStreamSynchronize(b->stream));
     HIP_TRY(b, hipMemcpy(dst, in, sizeof(T) * count, hipMemcpyHostToDevice));
+    return ISINGMC_OK;
+}
+
+// The launch behind isingmc_itime_groups (ngroups checked groups -> sum_all / sum_occ [R][ngroups]) and isingmc_bond_counts (ngroups = 0,
+// counts [R][Nb]): what LDS cannot serve is refused before anything is launched; then the pending flip bytes are brought in, the groups and
+// the variable -> groups lists built from them go up, itime_kernel runs on the batch's stream and the results come down.
+static int itime_run(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars, const uint8_t *group_flip,
+                     int64_t *sum_all, int64_t *sum_occ, uint32_t *counts) {
+    const uint32_t R = b->dev.R, N = b->dev.N, Nb = b->dev.Nb, nv = ngroups ? group_start[ngroups] : 0u;
+    const ItimePlan plan = itime_plan(b->lds_total_words, N, b->dev.nwords, Nb, ngroups, nv, counts != nullptr);
+    if (!plan.W) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "itime_groups: %u groups on %u variables exceed LDS (their sums and bit arrays live there): at most %u groups on this model",
+                 ngroups, N, itime_max_groups(b->lds_total_words, N, b->dev.nwords));
+        b->err = buf;
+        return ISINGMC_ENOTIMPL;
+    }
+    HIP_TRY(b, hipSetDevice(b->device));
+    { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
+    // device scratch: sums [2][R][G] (8-byte aligned, first) | counts [R][Nb] | words: start [G + 1], vars [nv], vstart [N + 1], vgroups [nv], flip bytes [G], flip bits
+    const size_t o_occ = (size_t)R * ngroups * 8, o_counts = 2 * o_occ, o_meta = o_counts + (counts ? (size_t)R * Nb * 4 : 0);
+    const size_t w_vars = (size_t)ngroups + 1, w_vstart = w_vars + nv, w_vgroups = w_vstart + N + 1, w_flip = w_vgroups + nv, w_fbits = w_flip + (ngroups + 3) / 4,
+                 meta_words = ngroups ? w_fbits + 2 * (((size_t)ngroups + 63) / 64) : 0;
+    const size_t bytes = o_meta + 4 * meta_words;
+    if (b->itime_buf_bytes < bytes || !b->itime_buf) {
+        if (b->itime_buf) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->itime_buf); b->itime_buf = nullptr; b->itime_buf_bytes = 0; }
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); b->err = "itime fold: allocation of the device scratch failed"; return ISINGMC_ENODEVICE; }
+        b->itime_buf = q; b->itime_buf_bytes = bytes;
+    }
+    char *buf = (char *)b->itime_buf;
+    ItimeArgs A{};
+    A.W = plan.W; A.hist_lds = plan.hist_lds; A.csr_lds = plan.csr_lds; A.nv = nv;
+    std::vector<uint32_t> meta(meta_words); // (lives until the stream has been drained below)
+    if (ngroups) {
+        std::copy(group_start, group_start + ngroups + 1, meta.begin());
+        std::copy(group_vars, group_vars + nv, meta.begin() + w_vars);
+        // variable -> groups: a counting sort of the (group, variable) pairs by variable, groups ascending within a variable
+        uint32_t *vstart = meta.data() + w_vstart, *vgroups = meta.data() + w_vgroups;
+        for (uint32_t k = 0; k < nv; ++k) vstart[group_vars[k] + 1]++;
+        for (uint32_t v = 0; v < N; ++v) vstart[v + 1] += vstart[v];
+        std::vector<uint32_t> fill(vstart, vstart + N);
+        for (uint32_t g = 0; g < ngroups; ++g)
+            for (uint32_t k = group_start[g]; k < group_start[g + 1]; ++k) vgroups[fill[group_vars[k]]++] = g;
+        if (group_flip)
+            for (uint32_t g = 0; g < ngroups; ++g) {
+                ((uint8_t *)(meta.data() + w_flip))[g] = group_flip[g] & 1u;
+                meta[w_fbits + (g >> 5)] |= (uint32_t)(group_flip[g] & 1u) << (g & 31u);
+            }
+        HIP_TRY(b, hipMemcpyAsync(buf + o_meta, meta.data(), 4 * meta_words, hipMemcpyHostToDevice, b->stream));
+        const uint32_t *dm = (const uint32_t *)(buf + o_meta);
+        A.G = ObsGroups{ngroups, dm, dm + w_vars, group_flip ? (const uint8_t *)(dm + w_flip) : nullptr};
+        A.vstart = dm + w_vstart; A.vgroups = dm + w_vgroups;
+        A.flip_bits = group_flip ? dm + w_fbits : nullptr;
+        A.sum_all = sum_all ? (int64_t *)buf : nullptr;
+        A.sum_occ = sum_occ ? (int64_t *)(buf + o_occ) : nullptr;
+    }
+    if (counts) {
+        A.counts = (uint32_t *)(buf + o_counts);
+        if (!plan.hist_lds) HIP_TRY(b, hipMemsetAsync(A.counts, 0, (size_t)R * Nb * 4, b->stream));
+    }
+    const hipError_t e = launch_itime(b->stream, b->dev, A);
+    if (e != hipSuccess) { b->err = std::string("itime fold launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    if (sum_all) HIP_TRY(b, hipMemcpyAsync(sum_all, buf, o_occ, hipMemcpyDeviceToHost, b->stream));
+    if (sum_occ) HIP_TRY(b, hipMemcpyAsync(sum_occ, buf + o_occ, o_occ, hipMemcpyDeviceToHost, b->stream));
+    if (counts) HIP_TRY(b, hipMemcpyAsync(counts, A.counts, (size_t)R * Nb * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
     return ISINGMC_OK;
 }
 
@@ -300,6 +370,25 @@ int isingmc_get_bond_count(isingmc_batch *b, uint32_t r, uint32_t bond, uint32_t
     for (uint32_t x : w) if (x && sse_op_bond(x) == bond) c++;
     *out = c;
     return ISINGMC_OK;
+}
+
+int isingmc_itime_groups(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars, const uint8_t *group_flip,
+                         int64_t *sum_all, int64_t *sum_occ) {
+    if (!b) return ISINGMC_EINVAL;
+    if (!ngroups || !group_start || !group_vars) { b->err = "itime_groups: no observable groups"; return ISINGMC_EINVAL; }
+    if (!sum_all && !sum_occ) { b->err = "itime_groups: no output buffer"; return ISINGMC_EINVAL; }
+    if (group_start[0] != 0u) { b->err = "itime_groups: group_start[0] must be 0"; return ISINGMC_EINVAL; }
+    for (uint32_t g = 0; g < ngroups; ++g)
+        if (group_start[g + 1] <= group_start[g]) { b->err = "itime_groups: every observable group needs at least one variable"; return ISINGMC_EINVAL; }
+    const uint32_t nv = group_start[ngroups];
+    for (uint32_t k = 0; k < nv; ++k)
+        if (group_vars[k] >= b->dev.N) { b->err = "itime_groups: group variable out of range"; return ISINGMC_EINVAL; }
+    return itime_run(b, ngroups, group_start, group_vars, group_flip, sum_all, sum_occ, nullptr);
+}
+int isingmc_bond_counts(isingmc_batch *b, uint32_t *out) {
+    if (!b) return ISINGMC_EINVAL;
+    if (!out) { b->err = "bond_counts: no output buffer"; return ISINGMC_EINVAL; }
+    return itime_run(b, 0, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int isingmc_debug_counts(isingmc_batch *b, uint32_t *out) {

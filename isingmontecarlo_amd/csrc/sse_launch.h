@@ -64,4 +64,58 @@ struct ObsGroups {
 hipError_t launch_record_series(hipStream_t stream, const uint32_t *rec, uint32_t R, uint32_t nwords, uint32_t T, const ObsGroups &G, uint32_t *out);
 hipError_t launch_bit_autocorr(hipStream_t stream, const uint32_t *series, uint32_t R, uint32_t ngroups, uint32_t T, double *out);
 
+// itime.hip (sse_itime.hip.h): imaginary-time folds of two-valued observables and bond counts, one workgroup per replica
+struct ItimeArgs {
+    ObsGroups G;             // ngroups == 0: bond counts only
+    const uint32_t *vstart;  // [N + 1] variable -> groups, offsets into vgroups (built on the host per call)
+    const uint32_t *vgroups; // [nv] the groups of every variable
+    uint32_t nv;             // group variables in all = G.start[G.ngroups]
+    const uint32_t *flip_bits; // [2 * ceil(ngroups / 64)] G.flip as bits (bit g & 31 of word g >> 5), or nullptr
+    int64_t *sum_all, *sum_occ; // [R][ngroups]
+    uint32_t *counts;        // [R][Nb] or nullptr; zeroed by the caller when hist_lds == 0 (the kernel then adds to it)
+    uint32_t W;              // waves of the workgroup
+    uint32_t hist_lds;       // the bond histogram is kept in LDS
+    uint32_t csr_lds;        // vstart / vgroups are staged in LDS
+};
+// The LDS of itime_kernel in words, in this order: 64-bit event sums [2][G] | per-wave group bits [W][sw] | per-wave variable bits
+// [W][nwords] | per-wave occupied counts [W] | bond histogram [Nb] | p = 0 state [nwords] | vstart [N + 1] | vgroups [nv]
+struct ItimeCarve { uint32_t o_acc, o_sign, sw, o_mask, o_cnt, o_hist, o_st0, o_vstart, o_vgroups; size_t words; };
+__host__ __device__ inline ItimeCarve itime_carve(uint32_t W, uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t G, uint32_t nv, bool hist_lds, bool csr_lds) {
+    ItimeCarve c;
+    size_t o = 0;
+    c.o_acc = (uint32_t)o; o += 4 * (size_t)G; // first: 8-byte aligned
+    c.sw = 2u * ((G + 63u) / 64u);             // a ballot of 64 groups is two words
+    c.o_sign = (uint32_t)o; o += (size_t)W * c.sw;
+    c.o_mask = (uint32_t)o; o += G ? (size_t)W * nwords : 0;
+    c.o_cnt = (uint32_t)o; o += W;
+    c.o_hist = (uint32_t)o; o += hist_lds ? Nb : 0;
+    c.o_st0 = (uint32_t)o; o += G ? nwords : 0;
+    c.o_vstart = (uint32_t)o; o += csr_lds ? (size_t)N + 1 : 0;
+    c.o_vgroups = (uint32_t)o; o += csr_lds ? nv : 0;
+    c.words = o;
+    return c;
+}
+// What a launch keeps in LDS of `total_words`: 16 waves with everything there, then without the histogram (global atomics), then
+// without the variable -> groups lists (read through L2), then the same with 4 waves; W = 0: the sums and bit arrays alone do not fit
+struct ItimePlan { uint32_t W; bool hist_lds, csr_lds; size_t words; };
+inline ItimePlan itime_plan(size_t total_words, uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t G, uint32_t nv, bool counts) {
+    const struct { uint32_t W; bool hist, csr; } tries[4] = {{16, true, true}, {16, false, true}, {16, false, false}, {4, false, false}};
+    for (const auto &t : tries) {
+        const bool hist = t.hist && counts, csr = t.csr && G;
+        const size_t words = itime_carve(t.W, N, nwords, Nb, G, nv, hist, csr).words;
+        if (words <= total_words) return {t.W, hist, csr, words};
+    }
+    return {0, false, false, 0};
+}
+// the most groups a model of N variables can be given (4 waves, nothing optional in LDS)
+inline uint32_t itime_max_groups(size_t total_words, uint32_t N, uint32_t nwords) {
+    uint32_t lo = 0, hi = 1u << 24;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (itime_carve(4, N, nwords, 0, mid, 0, false, false).words <= total_words) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+hipError_t launch_itime(hipStream_t stream, const DevBatch &B, const ItimeArgs &A);
+
 } // namespace sse

@@ -14,9 +14,9 @@
 //     (transverse-field op: the sign bit, so the cut mask is one signed compare), "longitudinal".  Empty slots and one-variable
 //     bonds name the same variable twice / a dummy variable N, so that nothing below is predicated on the kind of the slot;
 //   * per wave ONE packed 32-bit entry per variable: current segment id (16) | in-row cut marker (8) | touched (1).  A leg's
-//     lookup is one ds_or_rtn_b32 (returns id + marker, sets the touched bit): two LDS round trips per row instead of the
-//     four sub-dword reads + two touched-byte stores of the general scan (the scan is bound by LDS bank conflicts of random
-//     full-wave accesses once the instruction count is down);
+//     lookup is one 32-bit read (id + marker + flag): two LDS round trips per row instead of the four sub-dword reads + two
+//     touched-byte stores of the general scan (the scan is bound by LDS bank conflicts of random full-wave accesses once the
+//     instruction count is down).  Without a longitudinal field the flag needs no store of its own (see the build scan);
 //   * the table holds the segment ID itself (placeholder ids are written at initialisation), not a rank to be converted;
 //   * every slot keeps ONE 16-bit id in HBM (B.segs, two rows per dword): a two-site op's legs are in one cluster once its
 //     union is done, a cut's own id is its dense number, recomputed by the apply pass from the row's cut mask.  HBM traffic of the
@@ -63,6 +63,26 @@ __device__ __forceinline__ uint32_t cl_low16(uint32_t x) {
     uint32_t r;
     asm("v_and_b32 %0, 0xffff, %1" : "=v"(r) : "v"(x));
     return r;
+}
+// The two places of the scan that need the clean 16-bit id of a leg word.  Without a longitudinal field (HL = false) a leg word may
+// carry the touched flag above its id (see the build scan); each takes the low half inside the one instruction it costs anyway:
+// two ids of the apply pass in one dword (v_perm_b32 in place of v_lshl_or_b32; sel = SSE_CL_PACK_SEL, which the caller keeps in a
+// vector register: as a scalar it cost the kernel two more scalar spills) ...
+#define SSE_CL_PACK_SEL 0x05040100u // bytes 1:0 of the second operand below bytes 1:0 of the first
+template <bool HL>
+__device__ __forceinline__ uint32_t cl_pack_ids(uint32_t lo, uint32_t hi, uint32_t sel) {
+    if constexpr (HL) return lo | (hi << 16);
+    else return __builtin_amdgcn_perm(hi, lo, sel);
+}
+// ... and the LDS address of the id's parent-table entry (v_mad_u32_u16 in place of v_lshl_add_u32)
+template <bool HL>
+__device__ __forceinline__ uint32_t cl_par_addr(uint32_t par_b, uint32_t leg) {
+    if constexpr (HL) return par_b + 2u * leg;
+    else {
+        uint32_t r;
+        asm("v_mad_u32_u16 %0, %1, 2, %2" : "=v"(r) : "v"(leg), "s"(par_b));
+        return r;
+    }
 }
 // word of o_misc that the lanes of a predicated LDS store with nothing to store are pointed at (sse_fast.hip.h, "Predicated LDS
 // stores and atomics are written branch-free"): this kernel uses words 0-2 of the 16, nothing ever reads this one
@@ -217,8 +237,23 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     // value the lane saw, so that a later cut's fresh id is never overwritten).  A two-site op whose legs already carry the same
     // representative — most of them, clusters being long-lived — then costs no union-find access at all, and the others start
     // their finds one hop from a root.  Any member of the cluster serves the apply pass and the range joins equally well.
+    //
+    // The touched flag without a longitudinal field (HAS_LONG = false) costs no store of its own.  An entry of a wave's table holds
+    // its initial id (the placeholder id0 + v, or v itself in wave 0: unique to the variable, flag clear), a cut's id (written by
+    // the cut lane as a whole word, flag set) or a root (written by the union block's compare-and-store, flag set).  At h == 0 every
+    // op is a cut or a two-site op.  A cut flags its variable.  A two-site op whose legs differ runs the union block, which
+    // rewrites BOTH legs' entries with the flag, the leg whose own id survives as the root included; where its compare-and-store
+    // fails, a cut or a union of another lane wrote the entry first, with the flag.  A two-site op whose legs carry the same id on
+    // different variables can only have met values that a cut or a union wrote: an untouched initial id is referenced by its own
+    // entry alone.  Hence: variable v is touched in this wave's range <=> its entry carries SSE_CL_TOUCHED behind the scan (the test
+    // of the join phase).  The leg words ua / uc keep the flag bit of the entry they were read from (LEGF), so that they are the
+    // compare-and-store's expected word as they stand, and the id of a cut carries it through cutnext; where a clean id is needed
+    // (the id stored for the apply pass, the parent-table address) the instruction that takes it reads the low half only.  With a
+    // longitudinal field an op can act on a variable without cutting or linking: both legs store the flag byte, as before.
+    constexpr uint32_t LEGF = HAS_LONG ? 0u : SSE_CL_TOUCHED, LEGM = 0xFFFFu | LEGF; // flag bit kept in a leg word; what a leg word keeps of its entry
     {
-        uint32_t cutnext = N + cutbase; // id of the next cut of this range
+        uint32_t cutnext = (N + cutbase) | LEGF; // id of the next cut of this range (ids stay below 2^16: the flag rides along in the additions)
+        const uint32_t packsel = vgpr_copy_u32(SSE_CL_PACK_SEL);
         uint32_t wnext[K], idpend[K / 2];
         // deferred flips: the cut mask and the two-site mask of every row are wave-uniform; dword c of row j's uint4 is collected in
         // lane 4 j + c of one register (v_writelane) and lanes 0 .. 4 K - 1 store the tile's masks with one dword store each
@@ -262,15 +297,15 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                 LDS8B(acut + 2u) = (uint8_t)(kown + 1u);
                 SSE_WAVE_FENCE();
                 const uint32_t ea = LDS32B(aa), ec = LDS32B(ac);
-                LDS8B(aa + 3u) = (uint8_t)1; LDS8B(ac + 3u) = (uint8_t)1; // touched flag (byte 3): plain stores with an immediate offset, nothing waits for them
+                if constexpr (HAS_LONG) { LDS8B(aa + 3u) = (uint8_t)1; LDS8B(ac + 3u) = (uint8_t)1; } // touched flag (byte 3): plain stores with an immediate offset, nothing waits for them
                 const uint32_t qa = (ea >> 16) & 0xFFu, qc = (ec >> 16) & 0xFFu;
-                uint32_t seg_a = ea & 0xFFFFu, seg_c = ec & 0xFFFFu;
+                uint32_t seg_a = ea & LEGM, seg_c = ec & LEGM;
                 const uint64_t dup = cutm & sse_ballot(qa != kown + 1u);
                 if (!dup) {
                     seg_a = ((qa - 1u) < kown) ? cutnext + (qa - 1u) : seg_a; // qa == 0: no cut on the variable in this row
                     seg_c = ((qc - 1u) < kown) ? cutnext + (qc - 1u) : seg_c;
                     SSE_WAVE_FENCE();
-                    LDS32B(acut) = (cutnext + kown) | SSE_CL_TOUCHED; // the segment the cut opens; clears the marker
+                    LDS32B(acut) = (cutnext + kown) | (SSE_CL_TOUCHED & ~LEGF); // the segment the cut opens, touched; clears the marker
                 } else { // two cuts of this row on one variable (rare): lane order decides
                     const uint32_t va = e[j] & 0x1FFFu, vc = (e[j] >> 13) & 0x1FFFu;
                     bool lastcut = iscut;
@@ -288,25 +323,29 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                     }
                     SSE_WAVE_FENCE();
                     LDS8B(acut + 2u) = (uint8_t)0;
-                    if (iscut & lastcut) LDS16B(aa) = (uint16_t)(cutnext + kown); // the last cut wins
+                    if (iscut & lastcut) { // the last cut wins
+                        LDS16B(aa) = (uint16_t)(cutnext + kown);
+                        if constexpr (!HAS_LONG) LDS8B(aa + 3u) = (uint8_t)1; // (the 16-bit store leaves the flag byte as it was)
+                    }
                     SSE_WAVE_FENCE();
                 }
                 if constexpr (HAS_LONG)
                     if (e[j] & SSE_CLE_LONG) uf.frozen_or(seg_a >> 5, 1u << (seg_a & 31)); // qmc_ising.rs:759-775
                 cutnext += (uint32_t)popc64(cutm);
-                if (DEFER) { // (without a longitudinal field every op that is not a cut is a two-site op: the cut mask alone will do)
-                    mpend = cl_writelane(mpend, (uint32_t)cutm, 4 * j); mpend = cl_writelane(mpend, (uint32_t)(cutm >> 32), 4 * j + 1);
-                    if constexpr (HAS_LONG) { // (without one, dwords 2 and 3 of a row stay 0)
-                        const uint64_t twom = sse_ballot((e[j] & SSE_CLE_TWO) != 0u);
-                        mpend = cl_writelane(mpend, (uint32_t)twom, 4 * j + 2); mpend = cl_writelane(mpend, (uint32_t)(twom >> 32), 4 * j + 3);
-                    }
+                // the row's masks for a deferred apply pass, collected whether or not one follows: two v_writelane cost what the test
+                // of the flag in front of them did (without a longitudinal field every op that is not a cut is a two-site op: the
+                // cut mask alone will do)
+                mpend = cl_writelane(mpend, (uint32_t)cutm, 4 * j); mpend = cl_writelane(mpend, (uint32_t)(cutm >> 32), 4 * j + 1);
+                if constexpr (HAS_LONG) { // (without one, dwords 2 and 3 of a row stay 0)
+                    const uint64_t twom = sse_ballot((e[j] & SSE_CLE_TWO) != 0u);
+                    mpend = cl_writelane(mpend, (uint32_t)twom, 4 * j + 2); mpend = cl_writelane(mpend, (uint32_t)(twom >> 32), 4 * j + 3);
                 }
                 ua[j] = seg_a; uc[j] = seg_c; // (one-variable ops and empty slots: seg_c == seg_a, no union below)
             }
             // one 16-bit id per slot for the apply pass: the input leg's representative (a two-site op's other leg is in the same
             // cluster once its union below is done; a cut's own id is recomputed from the cut masks)
 #pragma unroll
-            for (int j = 0; j < K; j += 2) idpend[j / 2] = ua[j] | (ua[j + 1] << 16);
+            for (int j = 0; j < K; j += 2) idpend[j / 2] = cl_pack_ids<HAS_LONG>(ua[j], ua[j + 1], packsel);
             // Unions: only the lanes whose two legs carry different representatives take part — a handful per tile once the
             // representatives have settled —, row by row, under their own exec mask (the union-find reads of a full wave at random
             // addresses would cost the LDS more than the whole scan).  Parents, grandparents (root test), link + read-back (two lanes
@@ -314,13 +353,12 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
             // stores, no atomics.  Anything deeper goes through the serial routine.
 #pragma unroll
             for (int j = 0; j < K; ++j) {
-                const bool need = ua[j] != uc[j];
-                if (!sse_any(need) || SSE_DBG(B, 2u)) continue; // wave-uniform
-                if (need) {
+                const bool need = ua[j] != uc[j]; // (h == 0: equal ids carry equal flags, see LEGF)
+                if (need && !SSE_DBG(B, 2u)) { // entered on the exec mask alone: a row without such a lane branches over the block
                     // SSE_CL_FIND_LEVELS hops up from each representative, straight-line (a representative is a root or close to one: it was
                     // a root when it was written); nodes found below a root are re-pointed at it on the way (they are not roots, so
                     // no link of this batch can be undone by that)
-                    const uint32_t xa = par_b + 2u * ua[j], xc = par_b + 2u * uc[j]; // (each parent address: one shift-and-add)
+                    const uint32_t xa = cl_par_addr<HAS_LONG>(par_b, ua[j]), xc = cl_par_addr<HAS_LONG>(par_b, uc[j]); // (each parent address: one instruction)
                     const uint32_t pa = lds_ld16(xa), pc = lds_ld16(xc);
                     uint32_t ga = lds_ld16(par_b + 2u * pa), gc = lds_ld16(par_b + 2u * pc);
                     uint32_t ta = lds_ld16(par_b + 2u * ga), tc = lds_ld16(par_b + 2u * gc);
@@ -352,9 +390,12 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                     }
 #endif
                     if ((!found | (link & (chk != lo))) && !SSE_DBG(B, 16u)) lo = cl_union_wave(uf, pa, pc);
-                    // both legs' entries now name the surviving root (or the common parent found one hop up)
-                    lds_cas32(adra[j], ua[j] | SSE_CL_TOUCHED, lo | SSE_CL_TOUCHED);
-                    lds_cas32(adrc[j], uc[j] | SSE_CL_TOUCHED, lo | SSE_CL_TOUCHED);
+                    // both legs' entries now name the surviving root (or the common parent found one hop up), touched.  Expected is
+                    // the word the entry held when the lane looked it up (h == 0: the leg word itself, an untouched initial id
+                    // included; h != 0: the id, which the byte store of the scan has flagged): the store fails only where a cut or a
+                    // union of another lane rewrote the entry first, and those write the flag too
+                    lds_cas32(adra[j], ua[j] | (SSE_CL_TOUCHED & ~LEGF), lo | SSE_CL_TOUCHED);
+                    lds_cas32(adrc[j], uc[j] | (SSE_CL_TOUCHED & ~LEGF), lo | SSE_CL_TOUCHED);
                 }
             }
         }

@@ -7,9 +7,10 @@
 Parts are found by shape, not by label (labels move with every change):
   * build loop: the longest backward-branch span without a barrier that holds both a compare-and-store (ds_cmpst_b32: the
     rewrite of the two legs' entries behind a union) and global loads (the prefetch of the next tile);
-  * a row's union block, fast path: inside the build loop, from the "any lane needs a union" test in front of the last row's
-    compare-and-stores to the second of them, without the serial routine (the span between the exec-masked branch that skips
-    it and that branch's target);
+  * a row's union block, fast path: inside the build loop, from the "needs a union" compare in front of the last row's
+    compare-and-stores (followed by a wave-uniform any-lane test up to r12, by the exec-masked branch over the block since r15)
+    to the second of them, without the serial routine (the span between the exec-masked branch that skips it and that
+    branch's target);
   * initialisation loops: every innermost loop in front of the kernel's first barrier, in program order (state and touch words,
     bond entries, chunk counts, per-wave tables, parent table);
   * loops between the scan and the apply pass (range joins, flatten, coins): every outermost barrier-free loop behind the build
@@ -89,8 +90,11 @@ def main():
     # the last row's union block: back from its two compare-and-stores to the wave-uniform test in front of it
     cas = [i for i in range(build[0], build[1]) if ops[i].startswith("ds_cmpst")]
     b = cas[-1] + 1
-    a = max(i for i in range(build[0], cas[-2]) if ops[i] == "s_cmp_lg_u64" and insts[i][1].startswith("vcc") and ops[i - 1].startswith("v_cmp_ne_u32"))
-    a -= 1
+    old = [i for i in range(build[0], cas[-2]) if ops[i] == "s_cmp_lg_u64" and insts[i][1].startswith("vcc") and ops[i - 1].startswith("v_cmp_ne_u32")]
+    if old:  # up to r12: a wave-uniform "any lane" test (v_cmp, s_cmp_lg_u64 vcc) in front of the exec-masked block
+        a = max(old) - 1
+    else:  # since r15 the block is entered on its exec mask alone: v_cmp, s_and_saveexec, s_cbranch_execz to just behind the block
+        a = max(i for i in range(build[0], cas[-2]) if ops[i] == "s_cbranch_execz" and label_at.get(insts[i][1]) == b and ops[i - 1].startswith("s_and_saveexec")) - 2
     inner = [s for s in spans if a <= s[0] and s[1] <= b]
     skip = (b, b)
     if inner:

@@ -419,6 +419,76 @@ typedef struct isingmc_pt_phase {
 } isingmc_pt_phase;
 int isingmc_pt_plan_phase(isingmc_pt_phase *view);
 
+/* ---- classical Monte Carlo: qmc::classical::GraphState (src/classical/graph.rs) for a batch of replicas --------------------------
+ * One handle = R replicas of one graph (edges, couplings, biases common to the batch; beta per replica), resident on one device.
+ * The moves are stated once in csrc/classical_rule.h; their random numbers are the Philox streams of sse_format.h (tags CLASSICAL
+ * and CLASSICAL_WORM; epoch = the replica's time-step counter), so a run is a function of (seed, replica, epoch) alone: any split of
+ * a run into calls, batches or devices gives the same states.  On the device one wave64 owns a replica and evaluates 64 consecutive
+ * moves of a spin or edge step side by side (csrc/sse_classical.hip.h); the result equals the sequential rule move for move. */
+#define ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE 1u /* enable_edge_importance_sampling(true) (graph.rs:320-336); needs every J > 0 */
+#define ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES 2u   /* keep the graph tables in global memory even when they fit in LDS (testing) */
+#define ISINGMC_CLASSICAL_CFG_SERIAL_MOVES 4u    /* the wave takes one move at a time (testing / A-B timing); same results */
+/* `kinds` of isingmc_classical_timesteps */
+#define ISINGMC_CLASSICAL_KINDS_ALL 0u   /* spin, edge or worm step, drawn per step as do_time_step does (graph.rs:364-365) */
+#define ISINGMC_CLASSICAL_KINDS_BASIC 1u /* only_basic_moves = Some(true): spin or edge step */
+#define ISINGMC_CLASSICAL_KINDS_SPIN 2u  /* every step: nspin x do_spin_flip */
+#define ISINGMC_CLASSICAL_KINDS_EDGE 3u  /* every step: nedge x do_edge_flip */
+#define ISINGMC_CLASSICAL_KINDS_WORM 4u  /* every step: nworm x do_worm_flip with allow_doubles = true (as do_time_step calls it) */
+#define ISINGMC_CLASSICAL_KINDS_WORM_NO_DOUBLES 5u /* ... with allow_doubles = false (the reference's own tests, graph.rs:481-562) */
+
+typedef struct isingmc_classical isingmc_classical;
+typedef struct isingmc_classical_config {
+    uint32_t struct_size;      /* = sizeof(isingmc_classical_config) */
+    uint32_t nreplicas;        /* R */
+    uint32_t nvars;            /* N = biases.len() (graph.rs:69); at most 2^24 */
+    uint32_t nedges;           /* E >= 1 (the reference's edge move would panic on an empty edge list) */
+    const uint32_t *edges;     /* [2E]: a0,b0,a1,b1,...; a self-loop is ISINGMC_EINVAL as in isingmc_create */
+    const double *J;           /* [E] */
+    const double *biases;      /* [N] longitudinal fields, or NULL: all zero */
+    uint64_t seed;             /* Philox key */
+    uint32_t replica_offset;   /* global index of local replica 0 */
+    int32_t device;            /* HIP device ordinal, -1 = current device */
+    const uint8_t *init_state; /* [R][N] 0/1, or NULL: random under SSE_TAG_INIT exactly as isingmc_create draws it */
+    uint32_t flags;            /* ISINGMC_CLASSICAL_CFG_* */
+} isingmc_classical_config;
+
+/* GraphState::new / new_with_state_and_rng (graph.rs:56-88).  No CPU fallback: ISINGMC_ENODEVICE without a HIP device.
+ * ISINGMC_ENOTIMPL, before anything is allocated, when the per-replica state bits and move stamps (N / 8 + N bytes) exceed LDS. */
+int isingmc_classical_create(const isingmc_classical_config *cfg, isingmc_classical **out);
+void isingmc_classical_destroy(isingmc_classical *g);
+/* error text of the last failing call on this handle (g may be NULL: the last failing create / plan / host_steps call) */
+const char *isingmc_classical_last_error(const isingmc_classical *g);
+/* t x do_time_step (graph.rs:350-406) for every replica in one launch; beta[R].  nspin / nedge / nworm: moves per spin / edge /
+ * worm step, UINT32_MAX = the reference's None: max(1, N / 2), max(1, E / 2), 1.  kinds: ISINGMC_CLASSICAL_KINDS_*. */
+int isingmc_classical_timesteps(isingmc_classical *g, uint64_t t, const double *beta, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds);
+/* state_ref / clone_state / set_state (graph.rs:414-427): [N] bytes 0/1 of replica r; r == UINT32_MAX: all replicas, [R][N] */
+int isingmc_classical_get_state(isingmc_classical *g, uint32_t r, uint8_t *out);
+int isingmc_classical_set_state(isingmc_classical *g, uint32_t r, const uint8_t *in);
+/* the per-replica time-step counters (the Philox epoch), [R]: with get / set_state a run resumes bit-exactly */
+int isingmc_classical_get_epoch(isingmc_classical *g, uint64_t *out);
+int isingmc_classical_set_epoch(isingmc_classical *g, const uint64_t *epochs);
+/* get_energy (graph.rs:430-447) of every replica, one pass on the device: out[R] */
+int isingmc_classical_energies(isingmc_classical *g, double *out);
+/* out[R][8]: spin moves attempted, accepted, edge moves attempted, accepted, worms attempted, kept (neither failed nor rejected by the
+ * field energy), worm failures (path longer than N, graph.rs:281-285), worm path entries */
+int isingmc_classical_counters(isingmc_classical *g, uint64_t *out);
+int isingmc_classical_set_stream(isingmc_classical *g, void *hip_stream);
+int isingmc_classical_synchronize(isingmc_classical *g);
+/* HIP-event time of the most recent isingmc_classical_timesteps launch */
+int isingmc_classical_last_kernel_ms(isingmc_classical *g, float *ms);
+/* Host-only, a device-free test entry: the launch isingmc_classical_create plans for cfg on a device whose workgroups have lds_bytes
+ * of LDS, by the function create itself calls, or the code and message it would refuse cfg with.  out[0] waves (= replicas) per
+ * workgroup; out[1] which tables live in LDS, bit 0 row starts, 1 row entries, 2 couplings, 3 biases, 4 edge list, 5 cumulative edge
+ * weights (a table the model does not have has its bit clear); out[2] dynamic LDS words of the launch; out[3] LDS words per wave
+ * (state bits and stamp bytes); out[4] bits of out[1] that the model has at all; out[5] 1 = couplings kept as a dictionary of at most
+ * 256 values; out[6] 1 = edges packed into one word; out[7] 0 */
+int isingmc_classical_plan(const isingmc_classical_config *cfg, uint32_t lds_bytes, uint32_t out[8]);
+/* Host-only, a device-free test entry: t time steps of the sequential rule (csrc/classical_rule.h) on the CPU, for the graph, seed
+ * and replica_offset of cfg (init_state is not read): states[R][N] and epochs[R] in / out, counters[R][8] added to (may be NULL).
+ * exp is the host's libm. */
+int isingmc_classical_host_steps(const isingmc_classical_config *cfg, uint64_t t, const double *beta, uint32_t nspin, uint32_t nedge,
+                                 uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint64_t *counters);
+
 #ifdef __cplusplus
 }
 #endif

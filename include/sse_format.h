@@ -84,6 +84,16 @@ SSE_HD static inline int sse_op_is_diagonal(uint32_t w) { return sse_op_in(w) ==
 #define SSE_TAG_RVB 5u
 #define SSE_TAG_PT 6u
 #define SSE_TAG_HEATBATH 7u
+/* Classical Monte Carlo (GraphState, src/classical/graph.rs): epoch = the replica's time-step counter, one per do_time_step.
+ *   tag CLASSICAL       index 0      word 0: the kind of the step, __umulhi(word, only_basic_moves ? 2 : 3) (graph.rs:364-365)
+ *                       index 1 + i  move i of a spin or edge step: word 0 the site or edge choice, word 1 the acceptance uniform
+ *   tag CLASSICAL_WORM  index n      the n-th draw of the step's worm moves, word 0 of its own call, in program order: per worm the
+ *                                    start variable, one draw per path step that has candidates, the final acceptance (when the
+ *                                    field energy is positive: should_flip draws nothing otherwise, graph.rs:339-347)
+ * Ranges are __umulhi(word, n), uniforms word / 2^32; with edge importance sampling the edge is the number of cumulative weights
+ * strictly below (word / 2^32) * total weight (graph.rs:131-138). */
+#define SSE_TAG_CLASSICAL 8u
+#define SSE_TAG_CLASSICAL_WORM 9u
 
 #ifdef __cplusplus
 }

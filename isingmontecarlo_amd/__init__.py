@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _build
 
-__all__ = ["QmcIsingGraph", "Qmc", "TemperingContainer", "NativeTemperingContainer", "IsingMcError", "load_library", "op_make", "op_fields",
+__all__ = ["QmcIsingGraph", "Qmc", "GraphState", "new_qmc_from_graph", "TemperingContainer", "NativeTemperingContainer", "IsingMcError", "load_library", "op_make", "op_fields",
            "interaction_at", "interaction_sym_under_ising",
            "FLAG_LOOP", "FLAG_NO_CLUSTER", "FLAG_HEATBATH", "FLAG_RVB", "FLAG_PREP", "CFG_NO_LDS_TABLES", "CFG_FUSED_LAUNCH", "CFG_PER_REPLICA_J", "CFG_GLOBAL_TABLES", "CFG_NO_FAST_DIAG", "CFG_RVB_SERIAL_GROWTH", "CFG_NO_LEAN_CLUSTER", "CFG_NO_DEFERRED_FLIPS", "CFG_NO_PM_DECODE", "CFG_RVB_FUSED", "CFG_RVB_GLOBAL_TABLES"]
 
@@ -87,6 +87,13 @@ class _PtPhase(C.Structure):
                 ("words", C.c_uint64 * 2), ("nswaps", C.c_uint64)]
 
 
+class _ClassicalConfig(C.Structure):
+    """include/isingmc_hip.h: isingmc_classical_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("nreplicas", C.c_uint32), ("nvars", C.c_uint32), ("nedges", C.c_uint32),
+                ("edges", C.POINTER(C.c_uint32)), ("J", C.POINTER(C.c_double)), ("biases", C.POINTER(C.c_double)), ("seed", C.c_uint64),
+                ("replica_offset", C.c_uint32), ("device", C.c_int32), ("init_state", C.POINTER(C.c_uint8)), ("flags", C.c_uint32)]
+
+
 class _NcclId(C.Structure):
     _fields_ = [("internal", C.c_char * 128)]
 
@@ -159,6 +166,21 @@ SYMBOLS = {
     "isingmc_record_autocorrelation": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _u32, _u32, _P(_f64)]),
     "isingmc_itime_groups": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _P(C.c_uint8), _P(C.c_int64), _P(C.c_int64)]),
     "isingmc_bond_counts": (C.c_int, [_vp, _P(_u32)]),
+    "isingmc_classical_create": (C.c_int, [_P(_ClassicalConfig), _P(_vp)]),
+    "isingmc_classical_destroy": (None, [_vp]),
+    "isingmc_classical_last_error": (C.c_char_p, [_vp]),
+    "isingmc_classical_timesteps": (C.c_int, [_vp, _u64, _P(_f64), _u32, _u32, _u32, _u32]),
+    "isingmc_classical_get_state": (C.c_int, [_vp, _u32, _P(C.c_uint8)]),
+    "isingmc_classical_set_state": (C.c_int, [_vp, _u32, _P(C.c_uint8)]),
+    "isingmc_classical_get_epoch": (C.c_int, [_vp, _P(_u64)]),
+    "isingmc_classical_set_epoch": (C.c_int, [_vp, _P(_u64)]),
+    "isingmc_classical_energies": (C.c_int, [_vp, _P(_f64)]),
+    "isingmc_classical_counters": (C.c_int, [_vp, _P(_u64)]),
+    "isingmc_classical_set_stream": (C.c_int, [_vp, _vp]),
+    "isingmc_classical_synchronize": (C.c_int, [_vp]),
+    "isingmc_classical_last_kernel_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "isingmc_classical_plan": (C.c_int, [_P(_ClassicalConfig), _u32, _P(_u32)]),
+    "isingmc_classical_host_steps": (C.c_int, [_P(_ClassicalConfig), _u64, _P(_f64), _u32, _u32, _u32, _u32, _P(C.c_uint8), _P(_u64), _P(_u64)]),
 }
 
 _LIB = None
@@ -304,6 +326,16 @@ class QmcIsingGraph:
         self.capacity = int(capacity)
         self._flags = 0
         self._acc_rows = self.nreplicas
+
+    @classmethod
+    def new_from_graph(cls, graph, transverse, longitudinal, cutoff, seed, **kw):
+        """QmcIsingGraph::new_from_graph (qmc_ising.rs:151-166): the quantum batch on the edges of a classical GraphState
+        (isingmontecarlo_amd.classical), started from its states, one quantum replica per classical one.  Like the reference it
+        insists that every bias is zero (:157).  `seed` replaces the rng that the reference moves over."""
+        assert not np.any(np.asarray(graph.biases) != 0.0), "new_from_graph: every bias of the classical graph must be zero (qmc_ising.rs:157)"
+        kw.setdefault("nreplicas", graph.nreplicas)
+        kw.setdefault("nvars", graph.nvars)
+        return cls(graph.edge_list(), transverse, longitudinal, cutoff, seed, state=graph.state_ref(), **kw)
 
     # ---- lifetime ----
     def close(self):
@@ -882,3 +914,4 @@ class Qmc(QmcIsingGraph):
 
 
 from .tempering import TemperingContainer, NativeTemperingContainer, pt_decide  # noqa: E402
+from .classical import GraphState, new_qmc_from_graph  # noqa: E402

@@ -1,0 +1,409 @@
+// classical.hip — the C ABI of classical Monte Carlo (include/isingmc_hip.h, isingmc_classical_*): the config checks, the graph tables,
+// the launch plan (isingmc_classical_plan reports it), allocation, the accessors, and the sequential rule on the CPU
+// (isingmc_classical_host_steps).  The kernels are seen through classical_launch.h alone.
+#include "../../include/isingmc_hip.h"
+#include "classical_launch.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+using namespace sse;
+
+static_assert(ISINGMC_CLASSICAL_KINDS_ALL == CMC_KINDS_ALL && ISINGMC_CLASSICAL_KINDS_BASIC == CMC_KINDS_BASIC && ISINGMC_CLASSICAL_KINDS_SPIN == CMC_KINDS_SPIN &&
+              ISINGMC_CLASSICAL_KINDS_EDGE == CMC_KINDS_EDGE && ISINGMC_CLASSICAL_KINDS_WORM == CMC_KINDS_WORM &&
+              ISINGMC_CLASSICAL_KINDS_WORM_NO_DOUBLES == CMC_KINDS_WORM_NO_DOUBLES, "the header's kinds are the rule's");
+
+static thread_local std::string g_classical_error;
+static int refuse(int rc, const std::string &why) { g_classical_error = why; return rc; }
+
+// the graph tables of classical_rule.h on the host
+struct CmcHostTables {
+    std::vector<uint32_t> row, ent, edges;
+    std::vector<double> jv, bias, cum;
+    uint32_t N = 0, E = 0, flags = 0;
+    double totalw = 0.0;
+    CmcTables view() const {
+        return CmcTables{N, E, flags, (uint32_t)jv.size(), row.data(), ent.data(), jv.data(), bias.empty() ? nullptr : bias.data(), edges.data(),
+                         cum.empty() ? nullptr : cum.data(), totalw};
+    }
+};
+
+static int check_config(const isingmc_classical_config *cfg) {
+    if (!cfg || cfg->struct_size != sizeof(isingmc_classical_config)) return refuse(ISINGMC_EINVAL, "bad config pointer or struct_size");
+    if (cfg->nreplicas == 0 || cfg->nvars == 0) return refuse(ISINGMC_EINVAL, "nreplicas and nvars must be > 0");
+    if (cfg->nedges == 0) return refuse(ISINGMC_EINVAL, "a classical graph needs at least one edge (the reference's edge move would panic)");
+    if (!cfg->edges || !cfg->J) return refuse(ISINGMC_EINVAL, "edges and J must be non-null");
+    if (cfg->nvars > CMC_MAX_VARS) return refuse(ISINGMC_EINVAL, "too many variables (at most 2^24)");
+    if (cfg->nedges > 0x3FFFFFFFu) return refuse(ISINGMC_EINVAL, "too many edges");
+    if (cfg->flags & ~(ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE | ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES | ISINGMC_CLASSICAL_CFG_SERIAL_MOVES))
+        return refuse(ISINGMC_EINVAL, "unknown flag");
+    for (uint32_t e = 0; e < cfg->nedges; ++e) {
+        const uint32_t a = cfg->edges[2 * e], b = cfg->edges[2 * e + 1];
+        if (a >= cfg->nvars || b >= cfg->nvars) return refuse(ISINGMC_EINVAL, "edge endpoint out of range");
+        if (a == b) return refuse(ISINGMC_EINVAL, "edge joins a variable to itself (self-loop)");
+        if (!std::isfinite(cfg->J[e])) return refuse(ISINGMC_EINVAL, "couplings must be finite");
+        if ((cfg->flags & ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE) && !(cfg->J[e] > 0.0))
+            return refuse(ISINGMC_EINVAL, "edge importance sampling needs every J > 0 (the reference searches their running sums)");
+    }
+    for (uint32_t v = 0; cfg->biases && v < cfg->nvars; ++v)
+        if (!std::isfinite(cfg->biases[v])) return refuse(ISINGMC_EINVAL, "biases must be finite");
+    return ISINGMC_OK;
+}
+
+// binding_mat (graph.rs:69-78) and what goes with it, in the packed form of classical_rule.h
+static void build_tables(const isingmc_classical_config *cfg, CmcHostTables &H) {
+    const uint32_t N = cfg->nvars, E = cfg->nedges;
+    H.N = N; H.E = E; H.flags = 0;
+    // distinct couplings by bit pattern, in order of first appearance
+    std::map<uint64_t, uint32_t> code_of;
+    std::vector<uint32_t> code(E);
+    std::vector<double> dict;
+    for (uint32_t e = 0; e < E; ++e) {
+        uint64_t bits;
+        std::memcpy(&bits, &cfg->J[e], 8);
+        auto it = code_of.find(bits);
+        if (it == code_of.end()) { it = code_of.emplace(bits, (uint32_t)dict.size()).first; dict.push_back(cfg->J[e]); }
+        code[e] = it->second;
+    }
+    const bool compact = dict.size() <= 256;
+    if (compact) H.flags |= CMC_T_COMPACT;
+    H.row.assign((size_t)N + 1, 0);
+    for (uint32_t e = 0; e < E; ++e) { H.row[cfg->edges[2 * e] + 1]++; H.row[cfg->edges[2 * e + 1] + 1]++; }
+    for (uint32_t v = 0; v < N; ++v) H.row[v + 1] += H.row[v];
+    struct Ent { uint32_t nbr, edge; };
+    std::vector<Ent> ents(2 * (size_t)E);
+    std::vector<uint32_t> fill(H.row.begin(), H.row.end() - 1);
+    for (uint32_t e = 0; e < E; ++e) { // pushes in edge order ...
+        const uint32_t a = cfg->edges[2 * e], b = cfg->edges[2 * e + 1];
+        ents[fill[a]++] = Ent{b, e};
+        ents[fill[b]++] = Ent{a, e};
+    }
+    for (uint32_t v = 0; v < N; ++v) // ... then the stable sort by neighbour
+        std::stable_sort(ents.begin() + H.row[v], ents.begin() + H.row[v + 1], [](const Ent &x, const Ent &y) { return x.nbr < y.nbr; });
+    H.ent.resize(ents.size());
+    H.jv = compact ? dict : std::vector<double>(ents.size());
+    for (size_t k = 0; k < ents.size(); ++k) {
+        H.ent[k] = ents[k].nbr | (compact ? code[ents[k].edge] << 24 : 0u);
+        if (!compact) H.jv[k] = cfg->J[ents[k].edge];
+    }
+    if (N <= 65536u) {
+        H.flags |= CMC_T_EDGE16;
+        H.edges.resize(E);
+        for (uint32_t e = 0; e < E; ++e) H.edges[e] = cfg->edges[2 * e] | (cfg->edges[2 * e + 1] << 16);
+    } else H.edges.assign(cfg->edges, cfg->edges + 2 * (size_t)E);
+    H.bias.clear();
+    if (cfg->biases && std::any_of(cfg->biases, cfg->biases + N, [](double h) { return h != 0.0; })) {
+        H.flags |= CMC_T_BIAS;
+        H.bias.assign(cfg->biases, cfg->biases + N);
+    }
+    H.cum.clear(); H.totalw = 0.0;
+    if (cfg->flags & ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE) { // the fold of graph.rs:324-331
+        H.flags |= CMC_T_CUM;
+        H.cum.resize(E);
+        double accw = 0.0;
+        for (uint32_t e = 0; e < E; ++e) { accw = accw + cfg->J[e]; H.cum[e] = accw; }
+        H.totalw = accw;
+    }
+}
+
+// checks, tables and the launch plan: everything isingmc_classical_create decides before it touches a device
+static int plan_config(const isingmc_classical_config *cfg, uint32_t lds_bytes, CmcHostTables &H, CmcCarve &C) {
+    if (const int rc = check_config(cfg)) return rc;
+    build_tables(cfg, H);
+    const size_t total_words = lds_bytes / 4;
+    C = cmc_plan(H.view(), total_words, (cfg->flags & ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES) != 0u);
+    if (C.W == 0u) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "model too large: the state bits and move stamps of one replica exceed LDS (at most %u variables in %u bytes)",
+                      cmc_max_vars(total_words), lds_bytes);
+        return refuse(ISINGMC_ENOTIMPL, msg);
+    }
+    return ISINGMC_OK;
+}
+
+struct isingmc_classical {
+    CmcDev dev{};
+    CmcCarve carve{};
+    CmcHostTables host;
+    uint32_t flags = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+    double *d_beta = nullptr, *d_energy = nullptr;
+    std::vector<void *> allocs;
+    mutable std::string err;
+};
+
+#define CMC_TRY(g, expr)                                                                              \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) {                                                                       \
+            (g)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                             \
+            return ISINGMC_ENODEVICE;                                                                 \
+        }                                                                                             \
+    } while (0)
+
+template <typename T>
+static int cmc_upload(isingmc_classical *g, const T **p, const std::vector<T> &v) {
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
+    CMC_TRY(g, hipMalloc(&q, bytes));
+    g->allocs.push_back(q);
+    if (!v.empty()) CMC_TRY(g, hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *p = reinterpret_cast<const T *>(q);
+    return ISINGMC_OK;
+}
+template <typename T>
+static int cmc_alloc(isingmc_classical *g, T **p, size_t count) {
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    CMC_TRY(g, hipMalloc(&q, bytes));
+    g->allocs.push_back(q);
+    CMC_TRY(g, hipMemset(q, 0, bytes));
+    *p = reinterpret_cast<T *>(q);
+    return ISINGMC_OK;
+}
+
+static void pack_states(const uint8_t *in, uint32_t rows, uint32_t N, uint32_t nwords, std::vector<uint32_t> &out) {
+    out.assign((size_t)rows * nwords, 0u);
+    for (uint32_t r = 0; r < rows; ++r)
+        for (uint32_t v = 0; v < N; ++v)
+            if (in[(size_t)r * N + v]) out[(size_t)r * nwords + (v >> 5)] |= 1u << (v & 31u);
+}
+
+static int allocate_and_upload(isingmc_classical *g, const isingmc_classical_config *cfg) {
+    const CmcHostTables &H = g->host;
+    CmcDev &D = g->dev;
+    D.R = cfg->nreplicas; D.nwords = (H.N + 31u) / 32u;
+    D.seed_lo = (uint32_t)cfg->seed; D.seed_hi = (uint32_t)(cfg->seed >> 32); D.replica_offset = cfg->replica_offset;
+    D.T = H.view();
+    if (const int rc = cmc_upload(g, &D.T.row, H.row)) return rc;
+    if (const int rc = cmc_upload(g, &D.T.ent, H.ent)) return rc;
+    if (const int rc = cmc_upload(g, &D.T.jv, H.jv)) return rc;
+    if (const int rc = cmc_upload(g, &D.T.edges, H.edges)) return rc;
+    D.T.bias = nullptr; D.T.cum = nullptr;
+    if (!H.bias.empty()) if (const int rc = cmc_upload(g, &D.T.bias, H.bias)) return rc;
+    if (!H.cum.empty()) if (const int rc = cmc_upload(g, &D.T.cum, H.cum)) return rc;
+    if (const int rc = cmc_alloc(g, &D.state, (size_t)D.R * D.nwords)) return rc;
+    if (const int rc = cmc_alloc(g, &D.epoch, D.R)) return rc;
+    if (const int rc = cmc_alloc(g, &D.counters, (size_t)D.R * 8)) return rc;
+    if (const int rc = cmc_alloc(g, &D.err, D.R)) return rc;
+    if (const int rc = cmc_alloc(g, &g->d_beta, D.R)) return rc;
+    if (const int rc = cmc_alloc(g, &g->d_energy, D.R)) return rc;
+    CMC_TRY(g, hipEventCreate(&g->ev0));
+    CMC_TRY(g, hipEventCreate(&g->ev1));
+    if (cfg->init_state) {
+        std::vector<uint32_t> words;
+        pack_states(cfg->init_state, D.R, H.N, D.nwords, words);
+        CMC_TRY(g, hipMemcpy(D.state, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+    } else {
+        CMC_TRY(g, launch_classical_init_state(nullptr, D, H.N));
+        CMC_TRY(g, hipDeviceSynchronize());
+    }
+    return ISINGMC_OK;
+}
+
+// the sequential rule on the CPU: a replica's state as bytes, with the marks of the worm next to them
+struct CmcHostState {
+    uint8_t *s, *mark;
+    bool get(uint32_t v) const { return s[v] != 0; }
+    void flip(uint32_t v) { s[v] ^= 1u; mark[v] ^= 1u; }
+    bool marked(uint32_t v) const { return mark[v] != 0; }
+    void unmark(uint32_t v) { mark[v] = 0; }
+};
+
+extern "C" {
+
+int isingmc_classical_plan(const isingmc_classical_config *cfg, uint32_t lds_bytes, uint32_t out[8]) {
+    if (!out) return refuse(ISINGMC_EINVAL, "null output");
+    CmcHostTables H; CmcCarve C;
+    if (const int rc = plan_config(cfg, lds_bytes, H, C)) return rc;
+    const uint32_t slots[8] = {C.W, C.in_lds, C.words, C.wave_words, C.has, (H.flags & CMC_T_COMPACT) ? 1u : 0u, (H.flags & CMC_T_EDGE16) ? 1u : 0u, 0u};
+    std::copy(slots, slots + 8, out);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_create(const isingmc_classical_config *cfg, isingmc_classical **out) {
+    if (!out) return refuse(ISINGMC_EINVAL, "null output");
+    *out = nullptr;
+    if (const int rc = check_config(cfg)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return refuse(ISINGMC_ENODEVICE, "no HIP device available (this library has no CPU fallback)");
+    int dev = cfg->device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (hipSetDevice(dev) != hipSuccess) return refuse(ISINGMC_ENODEVICE, "hipSetDevice failed");
+    int max_lds = 0;
+    if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || max_lds <= 0) max_lds = 65536;
+    isingmc_classical *g = new isingmc_classical();
+    g->device = dev; g->flags = cfg->flags;
+    if (const int rc = plan_config(cfg, (uint32_t)max_lds, g->host, g->carve)) { delete g; return rc; }
+    if (const int rc = allocate_and_upload(g, cfg)) { g_classical_error = g->err; isingmc_classical_destroy(g); return rc; }
+    *out = g;
+    return ISINGMC_OK;
+}
+
+void isingmc_classical_destroy(isingmc_classical *g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    for (void *p : g->allocs) (void)hipFree(p);
+    if (g->ev0) (void)hipEventDestroy(g->ev0);
+    if (g->ev1) (void)hipEventDestroy(g->ev1);
+    delete g;
+}
+
+const char *isingmc_classical_last_error(const isingmc_classical *g) { return g ? g->err.c_str() : g_classical_error.c_str(); }
+
+int isingmc_classical_timesteps(isingmc_classical *g, uint64_t t, const double *beta, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!beta) { g->err = "beta must be non-null"; return ISINGMC_EINVAL; }
+    if (kinds >= CMC_KINDS_COUNT) { g->err = "kinds must be one of ISINGMC_CLASSICAL_KINDS_*"; return ISINGMC_EINVAL; }
+    for (uint32_t r = 0; r < g->dev.R; ++r)
+        if (std::isnan(beta[r])) { g->err = "beta must not be NaN"; return ISINGMC_EINVAL; }
+    if (t == 0) return ISINGMC_OK;
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipMemcpyAsync(g->d_beta, beta, (size_t)g->dev.R * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    const CmcStepArgs A{t, g->d_beta, nspin, nedge, nworm, kinds, (g->flags & ISINGMC_CLASSICAL_CFG_SERIAL_MOVES) ? 1u : 0u};
+    CMC_TRY(g, hipEventRecord(g->ev0, g->stream));
+    const hipError_t e = launch_classical_steps(g->stream, g->dev, g->carve, A);
+    if (e != hipSuccess) { g->err = std::string("classical steps launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    CMC_TRY(g, hipEventRecord(g->ev1, g->stream));
+    g->timed = true;
+    // beta is borrowed for the call only, and its copy was asynchronous from pageable memory: wait for the stream
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_get_state(isingmc_classical *g, uint32_t r, uint8_t *out) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!out || (r != UINT32_MAX && r >= g->dev.R)) { g->err = "bad replica index or null buffer"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    const uint32_t r0 = r == UINT32_MAX ? 0u : r, rows = r == UINT32_MAX ? g->dev.R : 1u, nw = g->dev.nwords, N = g->host.N;
+    std::vector<uint32_t> words((size_t)rows * nw);
+    CMC_TRY(g, hipMemcpy(words.data(), g->dev.state + (size_t)r0 * nw, words.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < rows; ++i)
+        for (uint32_t v = 0; v < N; ++v) out[(size_t)i * N + v] = (uint8_t)((words[(size_t)i * nw + (v >> 5)] >> (v & 31u)) & 1u);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_set_state(isingmc_classical *g, uint32_t r, const uint8_t *in) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!in || (r != UINT32_MAX && r >= g->dev.R)) { g->err = "bad replica index or null buffer"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    const uint32_t r0 = r == UINT32_MAX ? 0u : r, rows = r == UINT32_MAX ? g->dev.R : 1u, nw = g->dev.nwords;
+    std::vector<uint32_t> words;
+    pack_states(in, rows, g->host.N, nw, words);
+    CMC_TRY(g, hipMemcpy(g->dev.state + (size_t)r0 * nw, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_get_epoch(isingmc_classical *g, uint64_t *out) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    CMC_TRY(g, hipMemcpy(out, g->dev.epoch, (size_t)g->dev.R * 8, hipMemcpyDeviceToHost));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_set_epoch(isingmc_classical *g, const uint64_t *epochs) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!epochs) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    CMC_TRY(g, hipMemcpy(g->dev.epoch, epochs, (size_t)g->dev.R * 8, hipMemcpyHostToDevice));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_energies(isingmc_classical *g, double *out) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    const hipError_t e = launch_classical_energies(g->stream, g->dev, g->d_energy);
+    if (e != hipSuccess) { g->err = std::string("classical energies launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    CMC_TRY(g, hipMemcpy(out, g->d_energy, (size_t)g->dev.R * 8, hipMemcpyDeviceToHost));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_counters(isingmc_classical *g, uint64_t *out) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    CMC_TRY(g, hipMemcpy(out, g->dev.counters, (size_t)g->dev.R * 64, hipMemcpyDeviceToHost));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_set_stream(isingmc_classical *g, void *hip_stream) {
+    if (!g) return ISINGMC_EINVAL;
+    g->stream = reinterpret_cast<hipStream_t>(hip_stream);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_synchronize(isingmc_classical *g) {
+    if (!g) return ISINGMC_EINVAL;
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_last_kernel_ms(isingmc_classical *g, float *ms) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!ms) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    *ms = 0.f;
+    if (!g->timed) return ISINGMC_OK;
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipEventSynchronize(g->ev1));
+    CMC_TRY(g, hipEventElapsedTime(ms, g->ev0, g->ev1));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_host_steps(const isingmc_classical_config *cfg, uint64_t t, const double *beta, uint32_t nspin, uint32_t nedge,
+                                 uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint64_t *counters) {
+    if (const int rc = check_config(cfg)) return rc;
+    if (!beta || !states || !epochs) return refuse(ISINGMC_EINVAL, "beta, states and epochs must be non-null");
+    if (kinds >= CMC_KINDS_COUNT) return refuse(ISINGMC_EINVAL, "kinds must be one of ISINGMC_CLASSICAL_KINDS_*");
+    CmcHostTables H;
+    build_tables(cfg, H);
+    const CmcGraphMem g{H.view()};
+    const uint32_t N = H.N;
+    const uint32_t ns = cmc_default_moves(nspin, N / 2u), ne = cmc_default_moves(nedge, H.E / 2u), nw = cmc_default_moves(nworm, 1u);
+    std::vector<uint8_t> mark(N, 0);
+    for (uint32_t r = 0; r < cfg->nreplicas; ++r) {
+        CmcHostState s{states + (size_t)r * N, mark.data()};
+        uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        CmcHostDraw draw{(uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32), cfg->replica_offset + r, 0u, 0u};
+        for (uint64_t step = 0; step < t; ++step, ++epochs[r]) {
+            draw.epoch_lo = (uint32_t)epochs[r]; draw.epoch_hi24 = (uint32_t)(epochs[r] >> 32) & 0xFFFFFFu;
+            const uint32_t kind = cmc_step_kind(kinds, draw);
+            if (kind == 2u) {
+                uint32_t ndraw = 0;
+                for (uint32_t i = 0; i < nw; ++i) cmc_worm(g, s, beta[r], kinds != CMC_KINDS_WORM_NO_DOUBLES, draw, &ndraw, ctr);
+                continue;
+            }
+            const uint32_t n = kind == 0u ? ns : ne;
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint32_t choice = draw(SSE_TAG_CLASSICAL, cmc_index_move(i), 0), uword = draw(SSE_TAG_CLASSICAL, cmc_index_move(i), 1);
+                uint32_t a, b = CMC_NONE;
+                if (kind == 0u) a = cmc_range(choice, N); else g.edge(cmc_pick_edge(g, choice), a, b);
+                const double de = kind == 0u ? cmc_spin_de(g, s, a) : cmc_edge_de(g, s, a, b);
+                const bool acc = cmc_should_flip(beta[r], de, uword);
+                if (acc) { s.s[a] ^= 1u; if (kind == 1u) s.s[b] ^= 1u; }
+                ctr[kind == 0u ? CMC_C_SPIN : CMC_C_EDGE] += 1;
+                ctr[kind == 0u ? CMC_C_SPIN_ACC : CMC_C_EDGE_ACC] += acc ? 1u : 0u;
+            }
+        }
+        for (int i = 0; counters && i < 8; ++i) counters[(size_t)r * 8 + i] += ctr[i];
+    }
+    return ISINGMC_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,90 @@
+// classical_launch.h — the host-facing interface of the classical Monte Carlo kernels (sse_classical.hip.h, unit sweep_classical.hip):
+// what a launch is given, the LDS carve that the kernel lays its LDS out with and the host sizes the launch by, and the launchers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include "classical_rule.h"
+
+namespace sse {
+
+struct CmcDev {
+    CmcTables T;        // the graph tables in global memory (shared by the batch)
+    uint32_t R, nwords; // replicas; state words per replica
+    uint32_t *state;    // [R][nwords] bit v of word v >> 5
+    uint64_t *epoch;    // [R] time steps taken
+    uint64_t *counters; // [R][8] (classical_rule.h: CMC_C_*)
+    uint32_t *err;      // [R] sticky error flags: a flagged replica is skipped
+    uint32_t seed_lo, seed_hi, replica_offset;
+};
+struct CmcStepArgs {
+    uint64_t t;
+    const double *beta; // [R]
+    uint32_t nspin, nedge, nworm, kinds, serial;
+};
+
+// The LDS of classical_steps_kernel in words.  Per wave (= per replica of the workgroup), from word 0: the state bits [nwords], then
+// one stamp byte per variable [ceil(N / 4)].  Behind the waves' areas the graph tables that fit, in the order row starts, row entries,
+// couplings, biases, edge list, cumulative weights (the order in which they pay: a move reads its rows more often than anything
+// else); a table that does not fit, or any table with force_global, is read from global memory (offset CMC_NONE).  Tables of doubles
+// start on even words.
+enum { CMC_L_ROW = 1, CMC_L_ENT = 2, CMC_L_JV = 4, CMC_L_BIAS = 8, CMC_L_EDGES = 16, CMC_L_CUM = 32 };
+struct CmcCarve {
+    uint32_t W, wave_words, o_stamp; // a wave's area: wave_words words at wave * wave_words, its stamps o_stamp words in
+    uint32_t o_row, o_ent, o_jv, o_bias, o_edges, o_cum;
+    uint32_t in_lds, has;            // CMC_L_* of the tables in LDS / of the tables the model has
+    uint32_t words;                  // the dynamic LDS of the launch
+};
+__host__ __device__ inline uint32_t cmc_wave_words(uint32_t N) { return (N + 31u) / 32u + (N + 3u) / 4u; }
+__host__ __device__ inline uint32_t cmc_edge_words(const CmcTables &T) { return (T.flags & CMC_T_EDGE16) ? T.E : 2u * T.E; }
+inline CmcCarve cmc_carve(const CmcTables &T, uint32_t W, size_t total_words, bool force_global) {
+    CmcCarve c{};
+    c.W = W; c.wave_words = cmc_wave_words(T.N); c.o_stamp = (T.N + 31u) / 32u;
+    size_t o = (size_t)W * c.wave_words;
+    auto place = [&](uint32_t bit, size_t words, bool dbl, bool present) {
+        if (!present) return (uint32_t)CMC_NONE;
+        c.has |= bit;
+        const size_t at = dbl ? (o + 1) & ~(size_t)1 : o;
+        if (force_global || at + words > total_words) return (uint32_t)CMC_NONE;
+        c.in_lds |= bit; o = at + words;
+        return (uint32_t)at;
+    };
+    c.o_row = place(CMC_L_ROW, (size_t)T.N + 1, false, true);
+    c.o_ent = place(CMC_L_ENT, 2 * (size_t)T.E, false, true);
+    c.o_jv = place(CMC_L_JV, 2 * (size_t)T.njv, true, true);
+    c.o_bias = place(CMC_L_BIAS, 2 * (size_t)T.N, true, (T.flags & CMC_T_BIAS) != 0u);
+    c.o_edges = place(CMC_L_EDGES, cmc_edge_words(T), false, true);
+    c.o_cum = place(CMC_L_CUM, 2 * (size_t)T.E, true, (T.flags & CMC_T_CUM) != 0u);
+    c.words = (uint32_t)o;
+    return c;
+}
+// The launch of a model: the most waves per workgroup of 4, 2, 1 with every table in LDS; when no count does that, the most waves
+// whose own areas fit, with the tables that still fit.  W = 0: the areas of a single wave exceed LDS.
+inline CmcCarve cmc_plan(const CmcTables &T, size_t total_words, bool force_global) {
+    const uint32_t counts[3] = {4, 2, 1};
+    if (!force_global)
+        for (uint32_t W : counts) {
+            const CmcCarve c = cmc_carve(T, W, total_words, false);
+            if (c.in_lds == c.has && c.words <= total_words) return c;
+        }
+    for (uint32_t W : counts)
+        if ((size_t)W * cmc_wave_words(T.N) <= total_words) return cmc_carve(T, W, total_words, force_global);
+    CmcCarve none{};
+    return none;
+}
+// the most variables whose per-wave areas fit (what ISINGMC_ENOTIMPL names)
+inline uint32_t cmc_max_vars(size_t total_words) {
+    uint32_t lo = 0, hi = CMC_MAX_VARS;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (cmc_wave_words(mid) <= total_words) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// sweep_classical.hip
+hipError_t launch_classical_steps(hipStream_t stream, const CmcDev &D, const CmcCarve &C, const CmcStepArgs &A);
+hipError_t launch_classical_energies(hipStream_t stream, const CmcDev &D, double *out);
+hipError_t launch_classical_init_state(hipStream_t stream, const CmcDev &D, uint32_t N);
+
+} // namespace sse

@@ -347,7 +347,9 @@ int isingmc_last_kernel_ms(isingmc_batch *b, float *ms, uint32_t *launches);
 int isingmc_last_pass_ms(isingmc_batch *b, float ms[2], uint32_t launches[2]);
 /* ... and, of ms[1], the part spent in the RVB-sweep launches of split timesteps (0 when none ran) */
 int isingmc_last_rvb_ms(isingmc_batch *b, float *ms, uint32_t *launches);
-/* diagnostic builds (-DSSE_PHASE_TIMING) only: per-replica phase durations in 10-ns ticks, out[R][16]; zero otherwise */
+/* out[R][16] per-replica debug words.  Diagnostic builds (-DSSE_PHASE_TIMING): phase durations in 10-ns ticks.  Every build: the
+ * dedicated cluster kernel adds the unions its build scan parked to word 11 and the queue drains in front of a range's last one to
+ * word 15 (whole queues: 64 unions each); the other words are zero outside diagnostic builds.  reset != 0 clears the array. */
 int isingmc_debug_phase_ticks(isingmc_batch *b, uint64_t *out, int reset);
 /* number of sweeps fused into one kernel launch by isingmc_timesteps (0 = all t steps in one launch) */
 int isingmc_set_steps_per_launch(isingmc_batch *b, uint64_t steps);
@@ -371,6 +373,9 @@ int isingmc_plan_geometry(uint32_t capacity, uint32_t W, uint32_t K, uint32_t Wm
  * the u16 root list), o_frozen, o_froot, o_parent; dynamic LDS words of the launch; 1 if the replica is the kernel's case (else
  * it is left to the general kernel); entries of the root list}.  Exposed so that the layout can be asserted on a CPU box. */
 int isingmc_plan_cluster_lds(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t has_long, uint32_t ufcap, uint32_t S, uint32_t out[13]);
+/* Host-only: in that layout, the per-wave queues of unions the build scan parks (16 x (entries + 1 count word), in front of o_ent):
+ * out = {word offset, words, entries per wave}. */
+int isingmc_plan_cluster_queue(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t has_long, uint32_t ufcap, uint32_t out[3]);
 /* Host-only: every launch geometry and mode isingmc_create chooses for cfg on a device whose workgroups have lds_bytes of LDS, by the
  * function create itself calls; or the code and message (isingmc_last_error(NULL)) create would refuse cfg with once it has found a
  * device.  No device is looked for and nothing is allocated.  LDS sizes are in 32-bit words.

@@ -156,6 +156,7 @@ SYMBOLS = {
     "isingmc_last_rvb_ms": (C.c_int, [_vp, _P(C.c_float), _P(_u32)]),
     "isingmc_plan_geometry": (C.c_int, [_u32, _u32, _u32, _u32, _P(_u32)]),
     "isingmc_plan_cluster_lds": (C.c_int, [_u32, _u32, _u32, _u32, _u32, _u32, _P(_u32)]),
+    "isingmc_plan_cluster_queue": (C.c_int, [_u32, _u32, _u32, _u32, _u32, _P(_u32)]),
     "isingmc_plan_batch": (C.c_int, [_P(_Config), _u32, _P(_u32)]),
     "isingmc_pt_plan_phase": (C.c_int, [_P(_PtPhase)]),
     "isingmc_record_attach": (C.c_int, [_vp, _u32]),

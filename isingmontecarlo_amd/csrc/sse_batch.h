@@ -77,7 +77,7 @@ struct DevBatch {
     uint32_t rvb_prod_cap; // attempts per replica that rvb_prod holds
     uint32_t rvb_prod_stride; // words per attempt in rvb_prod
     uint32_t dbg_flags;   // diagnostic builds only
-    unsigned long long *dbg; // [R][16] phase durations in 10-ns ticks (diagnostic builds only, -DSSE_PHASE_TIMING)
+    unsigned long long *dbg; // [R][16] phase durations in 10-ns ticks (diagnostic builds only, -DSSE_PHASE_TIMING); every build: words 11 and 15, the cluster kernel's parked unions and full-queue drains
 };
 
 // which primitives a launch runs per step

@@ -87,6 +87,11 @@ __device__ __forceinline__ uint32_t cl_par_addr(uint32_t par_b, uint32_t leg) {
 // word of o_misc that the lanes of a predicated LDS store with nothing to store are pointed at (sse_fast.hip.h, "Predicated LDS
 // stores and atomics are written branch-free"): this kernel uses words 0-2 of the 16, nothing ever reads this one
 #define SSE_CL_MISC_DUMMY 12u
+// Parked unions of the build scan (see there): every wave owns SSE_CL_QCAP queue words and, behind them, the word that counts
+// them and the count of the full queues it has served
+#define SSE_CL_QCAP 64u
+#define SSE_CL_QWAVE (SSE_CL_QCAP + 2u)
+#define SSE_CL_QUEUE_WORDS ((uint32_t)SSE_CLW * SSE_CL_QWAVE)
 
 struct ClLds { // word offsets into lds_raw
     uint32_t o_tab;    // [Nb + 1]   packed bond entries, at word 0 (the index is the op word >> 4)
@@ -95,6 +100,7 @@ struct ClLds { // word offsets into lds_raw
     uint32_t o_misc;   // [16]
     uint32_t o_chn;    // [SSE_MAX_CHUNKS]
     uint32_t o_chtr;   // [SSE_MAX_CHUNKS]
+    uint32_t o_queue;  // [16][SSE_CL_QWAVE] per wave: parked unions of the build scan (two u16 ids per word), their count, full queues served
     uint32_t o_ent;    // [16][N + 1] per (wave, variable): id | marker << 16 | touched << 24; after the joins: root list + flip bits
     uint32_t o_frozen, o_froot; // [ufwords] (h != 0)
     uint32_t o_parent; // [ufcap] u16
@@ -107,6 +113,7 @@ struct ClLds { // word offsets into lds_raw
         o_misc = base; base += 16u;
         o_chn = base; base += SSE_MAX_CHUNKS;
         o_chtr = base; base += SSE_MAX_CHUNKS;
+        o_queue = base; base += SSE_CL_QUEUE_WORDS;
         o_ent = base; base += (uint32_t)SSE_CLW * (N + 1u);
         o_frozen = base; base += has_long ? (ufcap + 31u) / 32u : 0u;
         o_froot = base; base += has_long ? (ufcap + 31u) / 32u : 0u;
@@ -209,6 +216,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
         const uint32_t tb = L.o_ent + (uint32_t)wave * (N + 1u), id0 = wave == 0 ? 0u : N + C + (uint32_t)(wave - 1) * N;
         for (uint32_t v = (uint32_t)lane; v < N; v += 64u) LDSW(tb, v) = id0 + v;
         if (lane == 0) LDSW(tb, N) = S; // (the dummy variable of empty slots carries the null id S)
+        if (lane < 2) LDSW(L.o_queue, (uint32_t)wave * SSE_CL_QWAVE + SSE_CL_QCAP + (uint32_t)lane) = 0u; // no union parked, no queue served
     }
     for (uint32_t i = tid; i < S / 2u + 1u; i += NT) LDSW(L.o_parent, i) = (2u * i) | ((2u * i + 1u) << 16); // parent[i] = i for i <= S
     if constexpr (HAS_LONG) for (uint32_t i = tid; i < (S + 31u) / 32u; i += NT) uf.bits_clear(i);
@@ -229,6 +237,7 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     // Predicated LDS stores of the scan and of the union block are written branch-free (see SSE_CL_MISC_DUMMY): an address select
     // on the mask the code has anyway, instead of an exec save / restore around every store
     const uint32_t dummy_b = vgpr_copy_u32(lds0 + 4u * (L.o_misc + SSE_CL_MISC_DUMMY));
+    const uint32_t que_b = lds0 + 4u * (L.o_queue + (uint32_t)wave * SSE_CL_QWAVE), qcnt_b = que_b + 4u * SSE_CL_QCAP; // this wave's queue, its count (the count of full queues served: the word behind)
 
     SSE_STAMP(0);
     // ---- build: label every leg, union through the two-site ops (cluster.rs:193-271) ----
@@ -264,8 +273,23 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
 #pragma unroll
         for (int j = 0; j < K / 2; ++j) idpend[j] = 0u;
         uint32_t pprev = pbeg;
+        // Parked unions.  A lane of the union blocks below whose find does not end inside the straight-line hops, or whose link
+        // lost against another lane's, does not walk on there (a latency chain of LDS reads at whole-wave issue cost for one or
+        // two lanes, in a fifth of the rows): it appends the pair of ancestors it reached to this wave's queue, and the pairs are
+        // served together, one lane each, when the queue is full (looked at once per tile) and behind the scan.  Sound because
+        // the partition a set of unions leaves does not depend on their order, and nothing in front of the barrier behind the
+        // scan asks for more than a representative: the ids stored per slot and the table entries name members of the right
+        // clusters once every parked union is done, which is when the apply pass and the joins read them.
+        auto drain = [&](uint32_t cnt) {
+            if ((uint32_t)lane < cnt) {
+                const uint32_t pr = LDS32B(que_b + 4u * (uint32_t)lane);
+                (void)cl_union_wave(uf, pr & 0xFFFFu, pr >> 16);
+            }
+            LDS32B(qcnt_b) = 0u;
+        };
         for (uint32_t p0 = pbeg; p0 < pend; p0 += TS) {
             uint32_t e[K];
+            const uint32_t qfill = LDS32B(qcnt_b); // (read here, used in front of the union blocks)
             {
                 uint32_t word[K];
 #pragma unroll
@@ -350,7 +374,8 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
             // representatives have settled —, row by row, under their own exec mask (the union-find reads of a full wave at random
             // addresses would cost the LDS more than the whole scan).  Parents, grandparents (root test), link + read-back (two lanes
             // hooking one root); the trees a wave touches during the scan are private to it (own cuts, own placeholders): plain
-            // stores, no atomics.  Anything deeper goes through the serial routine.
+            // stores, no atomics.  Anything deeper is parked (see above).
+            if ((uint32_t)__builtin_amdgcn_readfirstlane((int)qfill) == SSE_CL_QCAP) { drain(SSE_CL_QCAP); LDS32B(qcnt_b + 4u) += 1u; }
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 const bool need = ua[j] != uc[j]; // (h == 0: equal ids carry equal flags, see LEGF)
@@ -389,8 +414,20 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                         }
                     }
 #endif
-                    if ((!found | (link & (chk != lo))) && !SSE_DBG(B, 16u)) lo = cl_union_wave(uf, pa, pc);
-                    // both legs' entries now name the surviving root (or the common parent found one hop up), touched.  Expected is
+                    if ((!found | (link & (chk != lo))) && !SSE_DBG(B, 16u)) {
+                        // park the union of the highest ancestors the hops reached (found: the two roots) behind the pairs the
+                        // queue holds: the count and, of the lanes in here, those below this one.  (Re-pointing the legs' start
+                        // nodes at these ancestors as well, and a returning LDS add for the position, were timed and are slower.)
+                        const uint64_t bm = sse_ballot(true); // the lanes in here
+                        const uint32_t fill = LDS32B(qcnt_b);
+                        const uint32_t pos = fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+                        LDS32B(qcnt_b) = min(fill + (uint32_t)popc64(bm), SSE_CL_QCAP);
+                        lo = min(ta, tc); // (found: min(ga, gc) as before)
+                        if (pos < SSE_CL_QCAP) LDS32B(que_b + 4u * pos) = ta | (tc << 16);
+                        else lo = cl_union_wave(uf, ta, tc); // the queue is full until the next tile looks at it: served here, as every such lane used to be
+                    }
+                    // both legs' entries now name the surviving root (or the common parent found one hop up; parked: the smaller of
+                    // the two ancestors, a member of the cluster both legs are in once the queue is served), touched.  Expected is
                     // the word the entry held when the lane looked it up (h == 0: the leg word itself, an untouched initial id
                     // included; h != 0: the id, which the byte store of the scan has flagged): the store fails only where a cut or a
                     // union of another lane rewrote the entry first, and those write the flag too
@@ -403,6 +440,15 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
 #pragma unroll
             for (int j = 0; j < K; j += 2) row_st(ids, (pprev >> 1) + (uint32_t)(j * 32 + lane), idpend[j / 2]);
             if (DEFER) { if (lane < 4 * K) row_st(mskw, (pprev >> 6) * 4u + (uint32_t)lane, mpend); }
+        }
+        // what is still parked, in front of the barrier: behind it every id and table entry is read as what it stands for
+        const uint32_t qlast = (uint32_t)__builtin_amdgcn_readfirstlane((int)LDS32B(qcnt_b));
+        const uint32_t qdrains = (uint32_t)__builtin_amdgcn_readfirstlane((int)LDS32B(qcnt_b + 4u));
+        drain(qlast);
+        // for the tests (isingmc_debug_phase_ticks, every build): unions this replica's waves parked, drains in front of the last
+        if (lane == 0 && (qlast | qdrains)) {
+            atomicAdd(&B.dbg[(size_t)r * 16 + 11], (unsigned long long)(qdrains * SSE_CL_QCAP + qlast));
+            if (qdrains) atomicAdd(&B.dbg[(size_t)r * 16 + 15], (unsigned long long)qdrains);
         }
     }
     __syncthreads();

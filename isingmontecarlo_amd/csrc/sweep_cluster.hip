@@ -37,3 +37,11 @@ extern "C" int isingmc_plan_cluster_lds(uint32_t N, uint32_t nwords, uint32_t Nb
     out[12] = sse::cl_list_cap(N, S);
     return ISINGMC_OK;
 }
+// ... and, of the same carve, the queues of parked unions: word offset, words, entries per wave
+extern "C" int isingmc_plan_cluster_queue(uint32_t N, uint32_t nwords, uint32_t Nb, uint32_t has_long, uint32_t ufcap, uint32_t out[3]) {
+    if (!out || N == 0 || N > SSE_CL_MAX_VARS || nwords < (N + 31) / 32) return ISINGMC_EINVAL;
+    sse::ClLds L;
+    L.carve(N, nwords, Nb, ufcap, has_long != 0u);
+    out[0] = L.o_queue; out[1] = SSE_CL_QUEUE_WORDS; out[2] = SSE_CL_QCAP;
+    return ISINGMC_OK;
+}

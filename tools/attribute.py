@@ -34,5 +34,6 @@ for spec in a.flags:
     else:
         print(f"flags {f:#04x}: {ms:7.3f} ms   init %.0f build %.0f join %.0f flatten %.0f coins %.0f apply %.0f us" % tuple(tk[:6]))
         c = out.astype(float).mean(axis=0)
-        if c[11] > 0: print("   wave 3 of a replica: %.0f tiles, %.0f rows with a union, %.0f shader cycles in the union blocks (%.0f of them in the serial routine); need lanes %.0f, successful write-backs %.0f, last (old<<32|expected) %x" % (c[11], c[8], c[9], c[10], c[12], c[13], int(out[0, 14])))
+        print("   per wave and range: %.1f unions parked, %.3f full queues served in front of the last drain (replica maxima %d, %d)" % (c[11] / 16, c[15] / 16, int(out[:, 11].max()), int(out[:, 15].max())))
+        if c[8] > 0: print("   wave 3 of a replica (-DSSE_CL_UNION_COUNTERS): %.0f rows with a union, %.0f with a find beyond the hops, %.0f with a lost link only; union lanes %.0f, beyond the hops %.0f, lost links %.0f" % (c[8], c[9], c[10], c[12], c[13], c[14]))
     del g

@@ -96,14 +96,29 @@ def main():
     else:  # since r15 the block is entered on its exec mask alone: v_cmp, s_and_saveexec, s_cbranch_execz to just behind the block
         a = max(i for i in range(build[0], cas[-2]) if ops[i] == "s_cbranch_execz" and label_at.get(insts[i][1]) == b and ops[i - 1].startswith("s_and_saveexec")) - 2
     inner = [s for s in spans if a <= s[0] and s[1] <= b]
-    skip = (b, b)
+    skip, serial = (b, b), (b, b)
     if inner:
         lo, hi = min(s[0] for s in inner), max(s[1] for s in inner)
         cand = [i for i in range(a, lo) if ops[i] == "s_cbranch_execz" and label_at.get(insts[i][1], -1) >= hi]
         if cand:
-            skip = (cand[-1] + 1, label_at[insts[cand[-1]][1]])
+            serial = (cand[-1] + 1, label_at[insts[cand[-1]][1]])
+            # since r16 the lanes beyond the fast path are parked: around the serial routine (now the branch of the lanes that find
+            # the queue full) lies the exec-masked park branch, itself inside the block's own branch
+            skip = (cand[1] + 1, label_at[insts[cand[1]][1]]) if len(cand) > 2 else serial
     fast = ops[a:skip[0]] + ops[skip[1]:b]
-    row("union block of a row, fast path", fast, f"   (serial routine left out: {skip[1] - skip[0]} instructions)")
+    if skip == serial:
+        row("union block of a row, fast path", fast, f"   (serial routine left out: {skip[1] - skip[0]} instructions)")
+    else:
+        row("union block of a row, fast path", fast, f"   (park branch left out: {skip[1] - skip[0]} instructions)")
+        row("  its park branch", ops[skip[0]:serial[0]] + ops[serial[1]:skip[1]], f"   (serial routine for a full queue left out: {serial[1] - serial[0]} instructions)")
+        # the drain of a full queue: in front of the first row's union block, the shortest loop of the tile that walks the parent
+        # table AND links (16-bit reads and writes: the serial routine's retry loop around its walk; the scan's own loops, two
+        # cuts on one variable, read lanes instead), without a compare-and-store or a global access
+        drains = [s for s in spans if build[0] <= s[0] and s[1] <= cas[0] and has(s, "ds_read_u16") and has(s, "ds_write_b16")
+                  and not has(s, "ds_cmpst") and not has(s, "global_")]
+        if drains:
+            s = min(drains, key=lambda s: s[1] - s[0])
+            row("drain of a full queue, its loop", ops[s[0]:s[1]])
     first_barrier = ops.index("s_barrier")
     init = [s for s in spans if s[1] <= first_barrier and innermost(s)]
     for k, s in enumerate(init):

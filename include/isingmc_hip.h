@@ -488,6 +488,9 @@ int isingmc_classical_last_kernel_ms(isingmc_classical *g, float *ms);
  * (state bits and stamp bytes); out[4] bits of out[1] that the model has at all; out[5] 1 = couplings kept as a dictionary of at most
  * 256 values; out[6] 1 = edges packed into one word; out[7] 0 */
 int isingmc_classical_plan(const isingmc_classical_config *cfg, uint32_t lds_bytes, uint32_t out[8]);
+/* The launch this handle runs with: the eight slots of isingmc_classical_plan, as isingmc_classical_create chose them from the LDS
+ * size of the handle's own device.  Read-only; no device call. */
+int isingmc_classical_launch_plan(isingmc_classical *g, uint32_t out[8]);
 /* Host-only, a device-free test entry: t time steps of the sequential rule (csrc/classical_rule.h) on the CPU, for the graph, seed
  * and replica_offset of cfg (init_state is not read): states[R][N] and epochs[R] in / out, counters[R][8] added to (may be NULL).
  * exp is the host's libm. */

@@ -181,6 +181,7 @@ SYMBOLS = {
     "isingmc_classical_synchronize": (C.c_int, [_vp]),
     "isingmc_classical_last_kernel_ms": (C.c_int, [_vp, _P(C.c_float)]),
     "isingmc_classical_plan": (C.c_int, [_P(_ClassicalConfig), _u32, _P(_u32)]),
+    "isingmc_classical_launch_plan": (C.c_int, [_vp, _P(_u32)]),
     "isingmc_classical_host_steps": (C.c_int, [_P(_ClassicalConfig), _u64, _P(_f64), _u32, _u32, _u32, _u32, _P(C.c_uint8), _P(_u64), _P(_u64)]),
 }
 

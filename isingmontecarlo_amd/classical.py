@@ -38,6 +38,10 @@ def _kinds(only_basic_moves, kinds):
     return (KINDS_BASIC if only_basic_moves else KINDS_ALL) if kinds is None else int(kinds)
 
 
+def _plan_dict(out):
+    return dict(waves=out[0], in_lds=out[1], lds_words=out[2], wave_words=out[3], tables=out[4], compact_couplings=bool(out[5]), packed_edges=bool(out[6]))
+
+
 def plan(edges, biases, lds_bytes=160 * 1024, flags=0):
     """isingmc_classical_plan: the launch isingmc_classical_create would choose, without a device."""
     lib = load_library()
@@ -46,7 +50,7 @@ def plan(edges, biases, lds_bytes=160 * 1024, flags=0):
     rc = lib.isingmc_classical_plan(C.byref(_config(ed, js, hs, 0, 1, flags=flags)), int(lds_bytes), out)
     if rc:
         raise IsingMcError(rc, lib.isingmc_classical_last_error(None).decode())
-    return dict(waves=out[0], in_lds=out[1], lds_words=out[2], wave_words=out[3], tables=out[4], compact_couplings=bool(out[5]), packed_edges=bool(out[6]))
+    return _plan_dict(out)
 
 
 def host_steps(edges, biases, seed, states, epochs, t, beta, nspinupdates=None, nedgeupdates=None, nwormupdates=None, only_basic_moves=None,
@@ -178,6 +182,12 @@ class GraphState:
 
     def synchronize(self):
         self._check(self._lib.isingmc_classical_synchronize(self._h))
+
+    def launch_plan(self):
+        """isingmc_classical_launch_plan: the launch this batch runs with, chosen from its device's own LDS size; the dict of plan()."""
+        out = (C.c_uint32 * 8)()
+        self._check(self._lib.isingmc_classical_launch_plan(self._h, out))
+        return _plan_dict(out)
 
     def last_kernel_ms(self):
         ms = C.c_float(0)

@@ -126,6 +126,12 @@ static int plan_config(const isingmc_classical_config *cfg, uint32_t lds_bytes, 
     return ISINGMC_OK;
 }
 
+// the eight slots of isingmc_classical_plan / isingmc_classical_launch_plan
+static void plan_slots(const CmcCarve &C, uint32_t table_flags, uint32_t out[8]) {
+    const uint32_t slots[8] = {C.W, C.in_lds, C.words, C.wave_words, C.has, (table_flags & CMC_T_COMPACT) ? 1u : 0u, (table_flags & CMC_T_EDGE16) ? 1u : 0u, 0u};
+    std::copy(slots, slots + 8, out);
+}
+
 struct isingmc_classical {
     CmcDev dev{};
     CmcCarve carve{};
@@ -224,8 +230,14 @@ int isingmc_classical_plan(const isingmc_classical_config *cfg, uint32_t lds_byt
     if (!out) return refuse(ISINGMC_EINVAL, "null output");
     CmcHostTables H; CmcCarve C;
     if (const int rc = plan_config(cfg, lds_bytes, H, C)) return rc;
-    const uint32_t slots[8] = {C.W, C.in_lds, C.words, C.wave_words, C.has, (H.flags & CMC_T_COMPACT) ? 1u : 0u, (H.flags & CMC_T_EDGE16) ? 1u : 0u, 0u};
-    std::copy(slots, slots + 8, out);
+    plan_slots(C, H.flags, out);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_launch_plan(isingmc_classical *g, uint32_t out[8]) {
+    if (!g) return ISINGMC_EINVAL;
+    if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    plan_slots(g->carve, g->host.flags, out);
     return ISINGMC_OK;
 }
 

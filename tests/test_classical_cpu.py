@@ -150,6 +150,88 @@ def test_plan_places_the_tables():
     assert (145632 + 31) // 32 + (145632 + 3) // 4 <= 40960 < (145633 + 31) // 32 + (145633 + 3) // 4
 
 
+def _flags(c):
+    return _cl().CFG_EDGE_IMPORTANCE if c["importance"] else 0
+
+
+@pytest.mark.parametrize("name", list(cc.LAYOUT_CASES))
+def test_layout_cases_plan_as_their_table_says(name):
+    """The launch of every layout case at 160 KB of LDS is the one tests/test_gpu_classical_layouts.py means to run: waves, tables in
+    LDS, table formats.  A change of the carve that moves a case to another launch fails here, without a device."""
+    c = cc.LAYOUT_CASES[name]
+    p = _cl().plan(c["edges"], c["biases"], flags=_flags(c))
+    assert {k: p[k] for k in c["plan"]} == c["plan"], (name, p)
+    assert p["lds_words"] <= 40960 and p["wave_words"] * p["waves"] <= p["lds_words"]
+
+
+def test_one_variable_more_than_the_largest_is_refused():
+    cl = _cl()
+    assert len(cc.LAYOUT_CASES["hightail145632"]["biases"]) == cc.LAYOUT_MAX_VARS
+    with pytest.raises(cl.IsingMcError) as ei:
+        cl.plan(*cc.hightail(cc.LAYOUT_MAX_VARS + 1))
+    assert ei.value.code == -5 and "at most 145632 variables" in str(ei.value)
+
+
+def _host_layout_chain(name):
+    cl = _cl()
+    c = cc.layout_case(name)
+    st, ep = cc.layout_states(len(c["biases"])), np.zeros(cc.LAYOUT_R, dtype=np.uint64)
+    total = np.zeros((cc.LAYOUT_R, 8), dtype=np.uint64)
+    out = []
+    for kinds, t, nspin, nedge, nworm in cc.LAYOUT_RUNS:
+        st, ep, ctr = cl.host_steps(c["edges"], c["biases"], cc.SEED, st, ep, t, c["betas"], nspin, nedge, nworm, kinds=kinds, replica_offset=cc.OFFSET,
+                                    flags=_flags(c))
+        total = total + ctr
+        out.append((st.copy(), total.copy(), ep.copy()))
+    return out
+
+
+@pytest.mark.parametrize("name", list(cc.LAYOUT_CASES) + list(cc.RANDOM_CASES))
+def test_host_steps_match_the_restatement_on_the_layout_cases(oracle, name):
+    """The sequential rule over both coupling formats and both edge-list formats of build_tables, and over random multigraphs around
+    the word boundaries of the state: states, counters and epochs bit for bit after every run of cc.LAYOUT_RUNS, beta up to +inf."""
+    want, got = cc.layout_reference_chain(name), _host_layout_chain(name)
+    for i, ((ws, wc, we), (gs, gc, ge)) in enumerate(zip(want, got)):
+        assert np.array_equal(ws, gs), (name, cc.LAYOUT_RUNS[i], "states")
+        assert np.array_equal(wc, gc), (name, cc.LAYOUT_RUNS[i], wc.tolist(), gc.tolist())
+        assert np.array_equal(we, ge), (name, cc.LAYOUT_RUNS[i], "epochs")
+
+
+def _final_states_of(name, edges):
+    c = cc.LAYOUT_CASES[name]
+    return cc.run_reference(edges, c["biases"], cc.layout_states(len(c["biases"])), c["betas"], cc.LAYOUT_RUNS, c["importance"])[0][-1][0]
+
+
+@pytest.mark.parametrize("name", cc.LAYOUT_NONCOMPACT)
+def test_noncompact_inputs_tell_a_wrong_coupling_index(oracle, name):
+    """A condition on the restatement alone: with every coupling moved on by one edge the final states are different ones, so a kernel
+    that reads jv one entry off cannot pass the parity test of this case."""
+    c = cc.LAYOUT_CASES[name]
+    assert not np.array_equal(cc.layout_reference_chain(name)[-1][0], _final_states_of(name, cc.rotate_couplings(c["edges"])))
+
+
+@pytest.mark.parametrize("name", cc.LAYOUT_HIGHTAIL)
+def test_hightail_inputs_tell_truncated_endpoints(oracle, name):
+    """Conditions on the restatement alone: the final states differ from those of the graph with its endpoints cut to 16 bits, and a
+    variable with index >= 65536 has changed, so the two-word edge list and the state words beyond 2048 matter to the parity test."""
+    c = cc.LAYOUT_CASES[name]
+    final = cc.layout_reference_chain(name)[-1][0]
+    assert not np.array_equal(final, _final_states_of(name, cc.truncate_endpoints(c["edges"])))
+    assert (final[:, 65536:] != cc.layout_states(len(c["biases"]))[:, 65536:]).any()
+
+
+@pytest.mark.parametrize("start", cc.EPOCH_STARTS)
+def test_host_steps_at_epochs_beyond_32_bits(oracle, start):
+    """epoch_hi24 of the Philox counter: four steps across 2^32 and across 2^56."""
+    cl = _cl()
+    edges, biases = cc.CASES["ring33"]
+    st = np.stack([CR.random_state(cc.SEED, cc.OFFSET + r, 33) for r in range(5)])
+    st, ep, ctr = cl.host_steps(edges, biases, cc.SEED, st, start, 4, cc.betas(5), kinds=CR.KINDS_ALL, replica_offset=cc.OFFSET)
+    ws, wc, we = cc.epoch_reference(start)
+    assert np.array_equal(st, ws) and np.array_equal(ctr, wc) and np.array_equal(ep, we) and (ep == np.uint64(start + 4)).all()
+    assert not np.array_equal(ws, cc.reference_chain("ring33", 5, runs=((CR.KINDS_ALL, 4, None, None, None),))[0][0])  # epoch 0 gives other states
+
+
 def test_config_struct_and_null_handles(tmp_path):
     import isingmontecarlo_amd as im
     lib = im.load_library()
@@ -163,7 +245,7 @@ def test_config_struct_and_null_handles(tmp_path):
         assert fn(None, None) == -1
     assert lib.isingmc_classical_get_state(None, 0, None) == -1 and lib.isingmc_classical_set_state(None, 0, None) == -1
     assert lib.isingmc_classical_set_stream(None, None) == -1 and lib.isingmc_classical_synchronize(None) == -1
-    assert lib.isingmc_classical_last_kernel_ms(None, None) == -1
+    assert lib.isingmc_classical_last_kernel_ms(None, None) == -1 and lib.isingmc_classical_launch_plan(None, None) == -1
     assert lib.isingmc_classical_plan(None, 1024, None) == -1 and lib.isingmc_classical_host_steps(None, 1, None, 1, 1, 1, 0, None, None, None) == -1
     lib.isingmc_classical_destroy(None)
     assert lib.isingmc_classical_create(None, None) == -1

@@ -24,6 +24,12 @@ int main(void) {
     {
         ora_replica *r = ora_replica_create(m2, 2048, 9, 7, 0, NULL);
         if (ora_timesteps(r, 300, 1.5, 1, ORA_FLAG_RVB) != 0 || !ora_verify(r)) bad = 1;
+        uint32_t *stats = (uint32_t *)malloc(sizeof(uint32_t) * 40 * ORA_RVB_NSTATS); /* the same sweep with its per-attempt statistics */
+        uint32_t acc = 0;
+        const uint32_t succ = ora_rvb_update_stats(r, 40, stats);
+        for (int a = 0; a < 40; ++a) acc += stats[a * ORA_RVB_NSTATS + ORA_RVB_ACCEPT];
+        if (acc != succ || !ora_verify(r)) bad = 1;
+        free(stats);
         ora_replica_destroy(r);
     }
     { /* parallel tempering step over four replicas */

@@ -57,6 +57,15 @@ void ora_flip_free_spins(ora_replica *r);
 uint32_t ora_loop_update(ora_replica *r); /* returns number of vertices visited */
 /* RvbUpdater::rvb_update_with_ising_weight (qmc_traits/rvb.rs:88-290): `updates` attempts; returns #accepted */
 uint32_t ora_rvb_update(ora_replica *r, uint32_t updates);
+/* The same sweep; stats (NULL, or [updates][ORA_RVB_NSTATS]) receives one row per attempt: the sizes that the device kernels hold
+ * in fixed arrays.  CSIZE cluster size drawn; NCL members the cluster got; BF, BN peak entries of the two weighted boundary sets
+ * (constant-op segments / variables without constant ops) while the cluster grew; NCAND = NCL + the two sets' entries when growth
+ * ended (sub-variable candidates, before repeats are dropped); NSUB sub-variables; NTOG toggles after remove_doubles; NWIN time
+ * windows with a non-empty cluster (counted for every attempt); BONDS_PROB peak entries of the before / after boundary-bond sets
+ * of calculate_flip_prob; BONDS_MUT the same for mutate_graph (0 when rejected); NADJ sum of the sub-variables' degrees; ACCEPT. */
+enum { ORA_RVB_CSIZE = 0, ORA_RVB_NCL, ORA_RVB_BF, ORA_RVB_BN, ORA_RVB_NCAND, ORA_RVB_NSUB, ORA_RVB_NTOG, ORA_RVB_NWIN,
+       ORA_RVB_BONDS_PROB, ORA_RVB_BONDS_MUT, ORA_RVB_NADJ, ORA_RVB_ACCEPT, ORA_RVB_NSTATS };
+uint32_t ora_rvb_update_stats(ora_replica *r, uint32_t updates, uint32_t *stats);
 uint32_t ora_find_overlapping_starts(uint32_t p_start, uint32_t p_end, uint32_t cutoff, const uint32_t *fp, uint32_t L,
                                      uint32_t *out);
 uint32_t ora_remove_doubles(uint32_t *v, uint32_t n);

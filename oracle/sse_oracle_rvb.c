@@ -20,10 +20,10 @@
 #include <string.h>
 
 typedef struct { uint32_t key, v, p; double w; } wentry; /* p = flip index or SSE_NO_VAR */
-typedef struct { wentry *e; uint32_t n, cap; int32_t *map; uint32_t mapn; double total; } wset;
+typedef struct { wentry *e; uint32_t n, cap, peak; int32_t *map; uint32_t mapn; double total; } wset; /* peak: largest n so far (statistics) */
 
 static void wset_init(wset *s, uint32_t nkeys) {
-    s->cap = 64; s->n = 0; s->total = 0.0;
+    s->cap = 64; s->n = 0; s->peak = 0; s->total = 0.0;
     s->e = (wentry *)malloc(sizeof(wentry) * s->cap);
     s->mapn = nkeys;
     s->map = (int32_t *)malloc(sizeof(int32_t) * (nkeys ? nkeys : 1));
@@ -43,6 +43,7 @@ static void wset_insert(wset *s, uint32_t key, uint32_t v, uint32_t p, double w)
     if (s->n == s->cap) { s->cap *= 2; s->e = (wentry *)realloc(s->e, sizeof(wentry) * s->cap); }
     s->e[s->n] = (wentry){key, v, p, w};
     s->map[key] = (int32_t)s->n++;
+    if (s->n > s->peak) s->peak = s->n;
     s->total += w;
 }
 /* bondcontainer.rs remove_index: swap with the last entry, pop, clamp the running total at 0 */
@@ -210,8 +211,10 @@ static int op_touches(const ora_model *m, uint32_t w, const int32_t *var2sub) {
     return m->bond_b[b] != SSE_NO_VAR && var2sub[m->bond_b[b]] >= 0;
 }
 
-/* One RVB sweep of `updates` attempts.  Returns the number of accepted attempts. */
-uint32_t ora_rvb_update(ora_replica *r, uint32_t updates) {
+/* One RVB sweep of `updates` attempts.  Returns the number of accepted attempts.  stats: NULL, or [updates][ORA_RVB_NSTATS]: the
+ * working set of every attempt (sse_oracle.h) — what the device kernels keep in fixed arrays.  The sets grow only between two pops
+ * (a pop removes one entry, the pushes behind it add), so their peaks are the peaks "after every pop and at the end". */
+uint32_t ora_rvb_update_stats(ora_replica *r, uint32_t updates, uint32_t *stats) {
     const ora_model *m = r->m;
     const uint32_t N = m->nvars, M = r->cutoff, E = m->nedges;
     /* bonds_for_var: make_classical_bonds (qmc_ising.rs:421-432), edge order */
@@ -352,6 +355,25 @@ uint32_t ora_rvb_update(ora_replica *r, uint32_t updates) {
         }
         qsort(toggles, ntog, sizeof(uint32_t), cmp_u32);
         ntog = ora_remove_doubles(toggles, ntog);
+        uint32_t *st = stats ? stats + (size_t)attempt * ORA_RVB_NSTATS : NULL;
+        if (st) {
+            st[ORA_RVB_CSIZE] = csize; st[ORA_RVB_NCL] = ncl; st[ORA_RVB_BF] = bf.peak; st[ORA_RVB_BN] = bn.peak;
+            st[ORA_RVB_NCAND] = nsv_cap; st[ORA_RVB_NSUB] = nsub; st[ORA_RVB_NTOG] = ntog;
+            /* the windows of mutate_graph (:310-360), counted for every attempt: the kernels find them while they grow the cluster */
+            uint8_t *cs2 = (uint8_t *)malloc(nsub + 1);
+            memcpy(cs2, cstart, nsub);
+            uint32_t cnt = 0, nw = 0, nadj = 0;
+            for (uint32_t s = 0; s < nsub; ++s) { cnt += cs2[s]; nadj += adj_start[subvars[s] + 1] - adj_start[subvars[s]]; }
+            if (cnt) nw++;
+            for (uint32_t i = 0; i < ntog; ++i) {
+                if (cnt == 0) nw++;
+                int32_t sv = var2sub[m->bond_a[sse_op_bond(r->ops[toggles[i]])]];
+                cs2[sv] ^= 1u;
+                if (cs2[sv]) cnt++; else cnt--;
+            }
+            free(cs2);
+            st[ORA_RVB_NWIN] = nw; st[ORA_RVB_NADJ] = nadj; st[ORA_RVB_BONDS_MUT] = 0; st[ORA_RVB_ACCEPT] = 0;
+        }
         subctx ctx = {m, nsub, subvars, var2sub, adj_start, adj};
 
         /* ---- calculate_flip_prob (:649-946) ---- */
@@ -410,6 +432,7 @@ uint32_t ora_rvb_update(ora_replica *r, uint32_t updates) {
                 }
             }
             mult *= calc_mult(&before, &after, nb);
+            if (st) st[ORA_RVB_BONDS_PROB] = before.peak > after.peak ? before.peak : after.peak;
             wset_free(&before);
             wset_free(&after);
         }
@@ -507,6 +530,7 @@ uint32_t ora_rvb_update(ora_replica *r, uint32_t updates) {
                     if (vc != SSE_NO_VAR) update_bonds(&ctx, vc, cstate, substate, &bonds, NULL);
                 }
             }
+            if (st) { st[ORA_RVB_BONDS_MUT] = bonds.peak; st[ORA_RVB_ACCEPT] = 1; }
             wset_free(&bonds);
             free(wfrom); free(wuntil);
             if (has_start)
@@ -524,3 +548,5 @@ uint32_t ora_rvb_update(ora_replica *r, uint32_t updates) {
     r->epoch += 1;
     return nsucc;
 }
+
+uint32_t ora_rvb_update(ora_replica *r, uint32_t updates) { return ora_rvb_update_stats(r, updates, NULL); }

@@ -10,6 +10,8 @@ _ORACLE_DIR = os.path.join(os.path.dirname(_HERE), "oracle")
 _LIB = os.path.join(_ORACLE_DIR, "libsse_oracle.so")
 
 FLAG_LOOP, FLAG_NO_CLUSTER, FLAG_HEATBATH, FLAG_RVB = 1, 2, 4, 8
+# columns of Replica.rvb_update(..., stats=True): the enum ORA_RVB_* of oracle/sse_oracle.h, in its order
+RVB_STATS = ("csize", "ncl", "bf", "bn", "ncand", "nsub", "ntog", "nwin", "bonds_prob", "bonds_mut", "nadj", "accept")
 
 
 def build():
@@ -62,6 +64,7 @@ def load():
         "ora_philox4x32_10": (None, [p(u32), p(u32), p(u32)]),
         "ora_pt_step": (u64, [p(vp), p(f64), u32, u64, u32, u64]),
         "ora_rvb_update": (u32, [vp, u32]),
+        "ora_rvb_update_stats": (u32, [vp, u32, p(u32)]),
         "ora_find_overlapping_starts": (u32, [u32, u32, u32, p(u32), u32, p(u32)]),
         "ora_remove_doubles": (u32, [p(u32), u32]),
         "ora_interaction_at": (f64, [u32, u32, p(f64), p(C.c_uint8), p(C.c_uint8)]),
@@ -176,8 +179,13 @@ class Replica:
     def loop_update(self):
         return lib().ora_loop_update(self.ptr)
 
-    def rvb_update(self, updates):
-        return lib().ora_rvb_update(self.ptr, updates)
+    def rvb_update(self, updates, stats=False):
+        """Successes of one sweep; with stats also its working set, [updates][len(RVB_STATS)] (sse_oracle.h: ORA_RVB_*)."""
+        if not stats:
+            return lib().ora_rvb_update(self.ptr, updates)
+        out = np.zeros((int(updates), len(RVB_STATS)), dtype=np.uint32)
+        succ = lib().ora_rvb_update_stats(self.ptr, updates, _ptr(out, C.c_uint32))
+        return succ, out
 
     def timestep(self, beta, flags=0):
         return lib().ora_timestep(self.ptr, beta, flags)

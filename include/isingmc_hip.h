@@ -497,6 +497,39 @@ int isingmc_classical_launch_plan(isingmc_classical *g, uint32_t out[8]);
 int isingmc_classical_host_steps(const isingmc_classical_config *cfg, uint64_t t, const double *beta, uint32_t nspin, uint32_t nedge,
                                  uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint64_t *counters);
 
+/* ---- classical parallel tempering (replica exchange) on the device; the rule is stated once in csrc/classical_pt_rule.h ----
+ * The batch is C chains of T = ntemps temperatures, R = C T, slot r = c T + i; betas[T] is one ladder shared by the chains (finite,
+ * any order, equal neighbours allowed).  temp_of[r] is the temperature index slot r holds (initially r % T).  A swap exchanges
+ * temperature labels: states, epochs, move counters and Philox streams stay with their slots.  The swap decisions of chain
+ * replica_offset / T + c come from the SSE_TAG_PT stream at the handle's step number pt_step, so a run is a function of (seed,
+ * replica_offset, pt_step, the states) alone.  One round = `steps` time steps of every slot at betas[temp_of[r]], then one launch that
+ * computes every slot's energy and magnetisation, records them by temperature (the values before the round's swaps) and takes one
+ * tempering step of every chain; pt_step increments per round.
+ * Errors (ISINGMC_EINVAL with a message): ntemps < 2, R % ntemps != 0, replica_offset % ntemps != 0, a non-finite beta, a null
+ * ladder; pt_run / pt_get / pt_set / pt_swap_counts before pt_attach.  isingmc_classical_timesteps on an attached handle behaves as
+ * without tempering: it takes its own beta array and leaves the maps alone. */
+/* Allocate (first call) and reset the maps, the swap counters and pt_step. */
+int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const double *betas);
+/* rounds x (steps launch, tempering launch) enqueued on the handle's stream, one synchronisation at the end.  energy_out
+ * double [rounds][C][T] and mag_out int32 [rounds][C][T] (M = sum_v (2 s_v - 1)) by temperature, either may be NULL.  rounds == 0 is a
+ * no-op; steps == 0 gives swaps only.  nspin / nedge / nworm / kinds as in isingmc_classical_timesteps. */
+int isingmc_classical_pt_run(isingmc_classical *g, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
+                             double *energy_out, int32_t *mag_out);
+/* temp_of[R] and pt_step, for checkpoints (either output may be NULL); set refuses what is not a permutation within each chain */
+int isingmc_classical_pt_get(isingmc_classical *g, uint32_t *temp_of, uint64_t *pt_step);
+int isingmc_classical_pt_set(isingmc_classical *g, const uint32_t *temp_of, uint64_t pt_step);
+/* swap attempts and acceptances of the pairs (t, t + 1), uint64 [C][T - 1] each, cumulative since attach (either may be NULL);
+ * set_swap_counts restores them from a checkpoint */
+int isingmc_classical_pt_swap_counts(isingmc_classical *g, uint64_t *attempts, uint64_t *accepts);
+int isingmc_classical_pt_set_swap_counts(isingmc_classical *g, const uint64_t *attempts, const uint64_t *accepts);
+/* Host-only, a device-free test entry: the same rounds by the sequential rule on the CPU (the step loop of
+ * isingmc_classical_host_steps, the energy in the kernel's order of additions), with attach's argument checks.  states[R][N],
+ * epochs[R], temp_of[R] and *pt_step in / out; counters[R][8], attempts and accepts [C][T - 1] added to (may be NULL); energy_out and
+ * mag_out as in isingmc_classical_pt_run.  exp is the host's libm. */
+int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint64_t rounds, uint64_t steps,
+                                  uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
+                                  uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out);
+
 #ifdef __cplusplus
 }
 #endif

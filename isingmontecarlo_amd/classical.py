@@ -1,13 +1,14 @@
 """Classical Ising Monte Carlo on the device: `GraphState` (qmc::classical::GraphState, src/classical/graph.rs) for a batch of R
 replicas of one graph, over the isingmc_classical_* entry points of include/isingmc_hip.h.  All moves run in gfx950 kernels
-(csrc/sse_classical.hip.h); there is no CPU fallback.  `host_steps` and `plan` are the device-free test entries of the C ABI."""
+(csrc/sse_classical.hip.h), and so does replica exchange between the temperatures of a chain (csrc/sse_classical_pt.hip.h); there is
+no CPU fallback.  `host_steps`, `host_tempering_run` and `plan` are the device-free test entries of the C ABI."""
 import ctypes as C
 
 import numpy as np
 
 from . import ALL, IsingMcError, QmcIsingGraph, _ClassicalConfig, _ptr, load_library  # (imported at the end of the package's __init__)
 
-__all__ = ["GraphState", "new_qmc_from_graph", "host_steps", "plan", "CFG_EDGE_IMPORTANCE", "CFG_GLOBAL_TABLES", "CFG_SERIAL_MOVES",
+__all__ = ["GraphState", "new_qmc_from_graph", "host_steps", "host_tempering_run", "plan", "CFG_EDGE_IMPORTANCE", "CFG_GLOBAL_TABLES", "CFG_SERIAL_MOVES",
            "KINDS_ALL", "KINDS_BASIC", "KINDS_SPIN", "KINDS_EDGE", "KINDS_WORM", "KINDS_WORM_NO_DOUBLES", "COUNTERS"]
 
 CFG_EDGE_IMPORTANCE, CFG_GLOBAL_TABLES, CFG_SERIAL_MOVES = 1, 2, 4
@@ -70,6 +71,40 @@ def host_steps(edges, biases, seed, states, epochs, t, beta, nspinupdates=None, 
     return st, ep, ctr
 
 
+def host_tempering_run(edges, biases, seed, states, epochs, betas, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None,
+                       only_basic_moves=None, kinds=None, temp_of=None, pt_step=0, replica_offset=0, flags=0, record=True):
+    """isingmc_classical_host_pt_run: `rounds` rounds of (`steps` time steps, one tempering step) by the sequential rule on the CPU, for
+    R = len(states) slots as chains of T = len(betas) temperatures.  Returns a dict: states [R][N], epochs [R], temp_of [R], pt_step,
+    counters [R][8], attempts and accepts [C][T - 1], and with `record` energy and magnetization [rounds][C][T]."""
+    lib = load_library()
+    ed, js, hs = _model(edges, biases)
+    st = np.ascontiguousarray(np.array(states, dtype=np.uint8).reshape(-1, len(hs)))
+    nrep = len(st)
+    ep = np.ascontiguousarray(np.broadcast_to(np.asarray(epochs, dtype=np.uint64), (nrep,)).copy())
+    ladder = None if betas is None else np.ascontiguousarray(np.asarray(betas, dtype=np.float64).reshape(-1))
+    ntemps = 0 if ladder is None else len(ladder)
+    chains = nrep // ntemps if ntemps and nrep % ntemps == 0 else 0
+    tof = np.ascontiguousarray((np.arange(nrep, dtype=np.uint32) % max(ntemps, 1)) if temp_of is None else np.array(temp_of, dtype=np.uint32).reshape(-1))
+    if len(tof) != nrep:
+        raise IsingMcError(-1, "temp_of has the wrong length")
+    step = C.c_uint64(int(pt_step))
+    ctr = np.zeros((nrep, 8), dtype=np.uint64)
+    att, acc = (np.zeros((chains, max(ntemps, 1) - 1), dtype=np.uint64) for _ in range(2))
+    energy = np.zeros((int(rounds), chains, ntemps), dtype=np.float64) if record else None
+    mag = np.zeros((int(rounds), chains, ntemps), dtype=np.int32) if record else None
+    rc = lib.isingmc_classical_host_pt_run(C.byref(_config(ed, js, hs, seed, nrep, replica_offset, flags=flags)), ntemps,
+                                           None if ladder is None else _ptr(ladder, C.c_double), int(rounds), int(steps), _count(nspinupdates),
+                                           _count(nedgeupdates), _count(nwormupdates), _kinds(only_basic_moves, kinds), _ptr(st, C.c_uint8),
+                                           _ptr(ep, C.c_uint64), _ptr(tof, C.c_uint32), C.byref(step), _ptr(ctr, C.c_uint64), _ptr(att, C.c_uint64),
+                                           _ptr(acc, C.c_uint64), _ptr(energy, C.c_double) if record else None, _ptr(mag, C.c_int32) if record else None)
+    if rc:
+        raise IsingMcError(rc, lib.isingmc_classical_last_error(None).decode())
+    out = dict(states=st, epochs=ep, temp_of=tof, pt_step=int(step.value), counters=ctr, attempts=att, accepts=acc)
+    if record:
+        out.update(energy=energy, magnetization=mag)
+    return out
+
+
 class GraphState:
     """R replicas of GraphState::new / new_with_state_and_rng (graph.rs:56-88): `edges` = [((a, b), J), ...], `biases` the
     longitudinal fields (their length is the number of variables), `seed` in place of the rng; `state` [N] or [R][N] (None: random)."""
@@ -83,6 +118,7 @@ class GraphState:
         self.seed, self.replica_offset, self.device = int(seed), int(replica_offset), int(device)
         self._cfg_flags = int(cfg_flags)
         self._counter_base = np.zeros((self.nreplicas, 8), dtype=np.uint64)
+        self._ladder = None  # the ladder of attach_tempering
         init = None
         if state is not None:
             st = np.asarray(state, dtype=np.uint8)
@@ -131,6 +167,7 @@ class GraphState:
         if flags == self._cfg_flags:
             return
         state, epoch, counters = self.state_ref(), self.get_epoch(), self.counters()
+        tempering = self._tempering_state() if self._ladder is not None else None
         old, self._cfg_flags = self._cfg_flags, flags
         handle, self._h = self._h, None
         try:
@@ -141,6 +178,86 @@ class GraphState:
         self._lib.isingmc_classical_destroy(handle)
         self.set_epoch(epoch)
         self._counter_base = counters
+        if tempering is not None:
+            self._restore_tempering(*tempering)
+
+    # ---- parallel tempering (csrc/classical_pt_rule.h) ----
+    def attach_tempering(self, betas):
+        """The batch as C chains of T = len(betas) temperatures, slot r = c T + i starting at betas[i]; one ladder for all chains.
+        Attaching again resets the maps, the swap counters and the step number."""
+        ladder = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).reshape(-1))
+        self._check(self._lib.isingmc_classical_pt_attach(self._h, len(ladder), _ptr(ladder, C.c_double)))
+        self._ladder = ladder
+
+    def _chains(self):
+        if self._ladder is None:
+            raise IsingMcError(-1, "tempering is not attached (attach_tempering)")
+        return self.nreplicas // len(self._ladder), len(self._ladder)
+
+    def tempering_run(self, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None, only_basic_moves=None, kinds=None, record=True):
+        """`rounds` rounds of (`steps` time steps of every slot at its temperature, one tempering step of every chain), enqueued on the
+        device with one synchronisation at the end.  With `record`: {"energy": float64 [rounds][C][T], "magnetization": int32
+        [rounds][C][T]}, by temperature, the values before each round's swaps; otherwise None."""
+        c, t = self._chains()
+        energy = np.zeros((int(rounds), c, t), dtype=np.float64) if record else None
+        mag = np.zeros((int(rounds), c, t), dtype=np.int32) if record else None
+        self._check(self._lib.isingmc_classical_pt_run(self._h, int(rounds), int(steps), _count(nspinupdates), _count(nedgeupdates), _count(nwormupdates),
+                                                       _kinds(only_basic_moves, kinds), _ptr(energy, C.c_double) if record else None,
+                                                       _ptr(mag, C.c_int32) if record else None))
+        return {"energy": energy, "magnetization": mag} if record else None
+
+    def temperature_of(self):
+        """uint32 [R]: the index into the ladder of the temperature each slot holds."""
+        self._chains()
+        out = np.zeros(self.nreplicas, dtype=np.uint32)
+        self._check(self._lib.isingmc_classical_pt_get(self._h, _ptr(out, C.c_uint32), None))
+        return out
+
+    def tempering_step_number(self):
+        self._chains()
+        step = C.c_uint64(0)
+        self._check(self._lib.isingmc_classical_pt_get(self._h, None, C.byref(step)))
+        return int(step.value)
+
+    def slot_at(self):
+        """uint32 [C][T]: the slot (within its chain) that holds each temperature: the inverse of temperature_of()."""
+        c, t = self._chains()
+        tof = self.temperature_of().reshape(c, t)
+        out = np.zeros((c, t), dtype=np.uint32)
+        np.put_along_axis(out, tof.astype(np.int64), np.broadcast_to(np.arange(t, dtype=np.uint32), (c, t)), axis=1)
+        return out
+
+    def states_by_temperature(self):
+        """uint8 [C][T][N]: the state at each temperature of each chain."""
+        c, t = self._chains()
+        return np.take_along_axis(self.state_ref().reshape(c, t, self.nvars), self.slot_at().astype(np.int64)[:, :, None], axis=1)
+
+    def swap_counts(self):
+        """(attempts, accepts), uint64 [C][T - 1] each: swaps of the pairs (t, t + 1), cumulative since attach_tempering."""
+        c, t = self._chains()
+        att, acc = np.zeros((c, t - 1), dtype=np.uint64), np.zeros((c, t - 1), dtype=np.uint64)
+        self._check(self._lib.isingmc_classical_pt_swap_counts(self._h, _ptr(att, C.c_uint64), _ptr(acc, C.c_uint64)))
+        return att, acc
+
+    def _tempering_state(self):
+        return (self._ladder.copy(), self.temperature_of(), self.tempering_step_number()) + self.swap_counts()
+
+    def _restore_tempering(self, ladder, temp_of, pt_step, attempts, accepts):
+        self.attach_tempering(ladder)
+        tof = np.ascontiguousarray(np.asarray(temp_of, dtype=np.uint32).reshape(-1))
+        att, acc = (np.ascontiguousarray(np.asarray(x, dtype=np.uint64)) for x in (attempts, accepts))
+        if len(tof) != self.nreplicas or att.shape != (self.nreplicas // len(ladder), len(ladder) - 1) or acc.shape != att.shape:
+            raise IsingMcError(-1, "tempering state has the wrong shape")
+        self._check(self._lib.isingmc_classical_pt_set(self._h, _ptr(tof, C.c_uint32), int(pt_step)))
+        self._check(self._lib.isingmc_classical_pt_set_swap_counts(self._h, _ptr(att, C.c_uint64), _ptr(acc, C.c_uint64)))
+
+    def set_temperature_of(self, temp_of, pt_step=None):
+        """isingmc_classical_pt_set: the map [R] (a permutation within each chain) and, unless None, the step number."""
+        self._chains()
+        tof = np.ascontiguousarray(np.asarray(temp_of, dtype=np.uint32).reshape(-1))
+        if len(tof) != self.nreplicas:
+            raise IsingMcError(-1, "temp_of has the wrong length")
+        self._check(self._lib.isingmc_classical_pt_set(self._h, _ptr(tof, C.c_uint32), self.tempering_step_number() if pt_step is None else int(pt_step)))
 
     # ---- accessors ----
     def state_ref(self):
@@ -197,14 +314,21 @@ class GraphState:
     # ---- checkpoint / resume ----
     def save_checkpoint(self, path):
         """States, time-step counters, move counters and options of every replica (.npz).  A batch built on the same model and seed and
-        restored with load_checkpoint continues bit-exactly."""
-        np.savez_compressed(path, format=np.array([1], dtype=np.uint32), edges=self.edges, J=self.J, biases=self.biases,
+        restored with load_checkpoint continues bit-exactly.  With tempering attached the file is format 2: it also holds the ladder, the
+        map of slots to temperatures, the tempering step number and both swap counters; without, it is the format-1 file."""
+        extra = {}
+        if self._ladder is not None:
+            ladder, temp_of, pt_step, attempts, accepts = self._tempering_state()
+            extra = dict(ladder=ladder, temp_of=temp_of, pt_step=np.array([pt_step], dtype=np.uint64), swap_attempts=attempts, swap_accepts=accepts)
+        np.savez_compressed(path, format=np.array([2 if extra else 1], dtype=np.uint32), edges=self.edges, J=self.J, biases=self.biases,
                             seed=np.array([self.seed], dtype=np.uint64), replica_offset=np.array([self.replica_offset], dtype=np.uint32),
                             importance=np.array([bool(self._cfg_flags & CFG_EDGE_IMPORTANCE)]), state=self.state_ref(), epoch=self.get_epoch(),
-                            counters=self.counters())
+                            counters=self.counters(), **extra)
 
     def load_checkpoint(self, path):
         z = np.load(path, allow_pickle=False)
+        if int(z["format"][0]) not in (1, 2):
+            raise IsingMcError(-1, "unknown checkpoint format")
         if not np.array_equal(z["edges"], self.edges) or not np.array_equal(z["J"], self.J) or not np.array_equal(z["biases"], self.biases):
             raise IsingMcError(-1, "checkpoint belongs to a different model")
         if z["state"].shape != (self.nreplicas, self.nvars) or int(z["seed"][0]) != self.seed or int(z["replica_offset"][0]) != self.replica_offset:
@@ -213,6 +337,8 @@ class GraphState:
         self.set_state(z["state"])
         self.set_epoch(z["epoch"])
         self._counter_base = z["counters"].astype(np.uint64) - (self.counters() - self._counter_base)
+        if int(z["format"][0]) == 2:
+            self._restore_tempering(z["ladder"], z["temp_of"], int(z["pt_step"][0]), z["swap_attempts"], z["swap_accepts"])
 
     def edge_list(self):
         """The edges as they were given: [((a, b), J), ...]."""

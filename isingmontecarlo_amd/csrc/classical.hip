@@ -1,16 +1,13 @@
 // classical.hip — the C ABI of classical Monte Carlo (include/isingmc_hip.h, isingmc_classical_*): the config checks, the graph tables,
 // the launch plan (isingmc_classical_plan reports it), allocation, the accessors, and the sequential rule on the CPU
-// (isingmc_classical_host_steps).  The kernels are seen through classical_launch.h alone.
-#include "../../include/isingmc_hip.h"
-#include "classical_launch.h"
+// (isingmc_classical_host_steps).  The kernels are seen through classical_launch.h alone; the handle and what tempering
+// (classical_pt.hip) shares with this file are in classical_handle.h.
+#include "classical_handle.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <string>
-#include <vector>
 
 using namespace sse;
 
@@ -19,44 +16,32 @@ static_assert(ISINGMC_CLASSICAL_KINDS_ALL == CMC_KINDS_ALL && ISINGMC_CLASSICAL_
               ISINGMC_CLASSICAL_KINDS_WORM_NO_DOUBLES == CMC_KINDS_WORM_NO_DOUBLES, "the header's kinds are the rule's");
 
 static thread_local std::string g_classical_error;
-static int refuse(int rc, const std::string &why) { g_classical_error = why; return rc; }
+int cmc_refuse(int rc, const std::string &why) { g_classical_error = why; return rc; }
 
-// the graph tables of classical_rule.h on the host
-struct CmcHostTables {
-    std::vector<uint32_t> row, ent, edges;
-    std::vector<double> jv, bias, cum;
-    uint32_t N = 0, E = 0, flags = 0;
-    double totalw = 0.0;
-    CmcTables view() const {
-        return CmcTables{N, E, flags, (uint32_t)jv.size(), row.data(), ent.data(), jv.data(), bias.empty() ? nullptr : bias.data(), edges.data(),
-                         cum.empty() ? nullptr : cum.data(), totalw};
-    }
-};
-
-static int check_config(const isingmc_classical_config *cfg) {
-    if (!cfg || cfg->struct_size != sizeof(isingmc_classical_config)) return refuse(ISINGMC_EINVAL, "bad config pointer or struct_size");
-    if (cfg->nreplicas == 0 || cfg->nvars == 0) return refuse(ISINGMC_EINVAL, "nreplicas and nvars must be > 0");
-    if (cfg->nedges == 0) return refuse(ISINGMC_EINVAL, "a classical graph needs at least one edge (the reference's edge move would panic)");
-    if (!cfg->edges || !cfg->J) return refuse(ISINGMC_EINVAL, "edges and J must be non-null");
-    if (cfg->nvars > CMC_MAX_VARS) return refuse(ISINGMC_EINVAL, "too many variables (at most 2^24)");
-    if (cfg->nedges > 0x3FFFFFFFu) return refuse(ISINGMC_EINVAL, "too many edges");
+int cmc_check_config(const isingmc_classical_config *cfg) {
+    if (!cfg || cfg->struct_size != sizeof(isingmc_classical_config)) return cmc_refuse(ISINGMC_EINVAL, "bad config pointer or struct_size");
+    if (cfg->nreplicas == 0 || cfg->nvars == 0) return cmc_refuse(ISINGMC_EINVAL, "nreplicas and nvars must be > 0");
+    if (cfg->nedges == 0) return cmc_refuse(ISINGMC_EINVAL, "a classical graph needs at least one edge (the reference's edge move would panic)");
+    if (!cfg->edges || !cfg->J) return cmc_refuse(ISINGMC_EINVAL, "edges and J must be non-null");
+    if (cfg->nvars > CMC_MAX_VARS) return cmc_refuse(ISINGMC_EINVAL, "too many variables (at most 2^24)");
+    if (cfg->nedges > 0x3FFFFFFFu) return cmc_refuse(ISINGMC_EINVAL, "too many edges");
     if (cfg->flags & ~(ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE | ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES | ISINGMC_CLASSICAL_CFG_SERIAL_MOVES))
-        return refuse(ISINGMC_EINVAL, "unknown flag");
+        return cmc_refuse(ISINGMC_EINVAL, "unknown flag");
     for (uint32_t e = 0; e < cfg->nedges; ++e) {
         const uint32_t a = cfg->edges[2 * e], b = cfg->edges[2 * e + 1];
-        if (a >= cfg->nvars || b >= cfg->nvars) return refuse(ISINGMC_EINVAL, "edge endpoint out of range");
-        if (a == b) return refuse(ISINGMC_EINVAL, "edge joins a variable to itself (self-loop)");
-        if (!std::isfinite(cfg->J[e])) return refuse(ISINGMC_EINVAL, "couplings must be finite");
+        if (a >= cfg->nvars || b >= cfg->nvars) return cmc_refuse(ISINGMC_EINVAL, "edge endpoint out of range");
+        if (a == b) return cmc_refuse(ISINGMC_EINVAL, "edge joins a variable to itself (self-loop)");
+        if (!std::isfinite(cfg->J[e])) return cmc_refuse(ISINGMC_EINVAL, "couplings must be finite");
         if ((cfg->flags & ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE) && !(cfg->J[e] > 0.0))
-            return refuse(ISINGMC_EINVAL, "edge importance sampling needs every J > 0 (the reference searches their running sums)");
+            return cmc_refuse(ISINGMC_EINVAL, "edge importance sampling needs every J > 0 (the reference searches their running sums)");
     }
     for (uint32_t v = 0; cfg->biases && v < cfg->nvars; ++v)
-        if (!std::isfinite(cfg->biases[v])) return refuse(ISINGMC_EINVAL, "biases must be finite");
+        if (!std::isfinite(cfg->biases[v])) return cmc_refuse(ISINGMC_EINVAL, "biases must be finite");
     return ISINGMC_OK;
 }
 
 // binding_mat (graph.rs:69-78) and what goes with it, in the packed form of classical_rule.h
-static void build_tables(const isingmc_classical_config *cfg, CmcHostTables &H) {
+void cmc_build_tables(const isingmc_classical_config *cfg, CmcHostTables &H) {
     const uint32_t N = cfg->nvars, E = cfg->nedges;
     H.N = N; H.E = E; H.flags = 0;
     // distinct couplings by bit pattern, in order of first appearance
@@ -113,15 +98,15 @@ static void build_tables(const isingmc_classical_config *cfg, CmcHostTables &H) 
 
 // checks, tables and the launch plan: everything isingmc_classical_create decides before it touches a device
 static int plan_config(const isingmc_classical_config *cfg, uint32_t lds_bytes, CmcHostTables &H, CmcCarve &C) {
-    if (const int rc = check_config(cfg)) return rc;
-    build_tables(cfg, H);
+    if (const int rc = cmc_check_config(cfg)) return rc;
+    cmc_build_tables(cfg, H);
     const size_t total_words = lds_bytes / 4;
     C = cmc_plan(H.view(), total_words, (cfg->flags & ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES) != 0u);
     if (C.W == 0u) {
         char msg[200];
         std::snprintf(msg, sizeof msg, "model too large: the state bits and move stamps of one replica exceed LDS (at most %u variables in %u bytes)",
                       cmc_max_vars(total_words), lds_bytes);
-        return refuse(ISINGMC_ENOTIMPL, msg);
+        return cmc_refuse(ISINGMC_ENOTIMPL, msg);
     }
     return ISINGMC_OK;
 }
@@ -130,50 +115,6 @@ static int plan_config(const isingmc_classical_config *cfg, uint32_t lds_bytes, 
 static void plan_slots(const CmcCarve &C, uint32_t table_flags, uint32_t out[8]) {
     const uint32_t slots[8] = {C.W, C.in_lds, C.words, C.wave_words, C.has, (table_flags & CMC_T_COMPACT) ? 1u : 0u, (table_flags & CMC_T_EDGE16) ? 1u : 0u, 0u};
     std::copy(slots, slots + 8, out);
-}
-
-struct isingmc_classical {
-    CmcDev dev{};
-    CmcCarve carve{};
-    CmcHostTables host;
-    uint32_t flags = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    double *d_beta = nullptr, *d_energy = nullptr;
-    std::vector<void *> allocs;
-    mutable std::string err;
-};
-
-#define CMC_TRY(g, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            (g)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                             \
-            return ISINGMC_ENODEVICE;                                                                 \
-        }                                                                                             \
-    } while (0)
-
-template <typename T>
-static int cmc_upload(isingmc_classical *g, const T **p, const std::vector<T> &v) {
-    void *q = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    CMC_TRY(g, hipMalloc(&q, bytes));
-    g->allocs.push_back(q);
-    if (!v.empty()) CMC_TRY(g, hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *p = reinterpret_cast<const T *>(q);
-    return ISINGMC_OK;
-}
-template <typename T>
-static int cmc_alloc(isingmc_classical *g, T **p, size_t count) {
-    void *q = nullptr;
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    CMC_TRY(g, hipMalloc(&q, bytes));
-    g->allocs.push_back(q);
-    CMC_TRY(g, hipMemset(q, 0, bytes));
-    *p = reinterpret_cast<T *>(q);
-    return ISINGMC_OK;
 }
 
 static void pack_states(const uint8_t *in, uint32_t rows, uint32_t N, uint32_t nwords, std::vector<uint32_t> &out) {
@@ -215,19 +156,38 @@ static int allocate_and_upload(isingmc_classical *g, const isingmc_classical_con
     return ISINGMC_OK;
 }
 
-// the sequential rule on the CPU: a replica's state as bytes, with the marks of the worm next to them
-struct CmcHostState {
-    uint8_t *s, *mark;
-    bool get(uint32_t v) const { return s[v] != 0; }
-    void flip(uint32_t v) { s[v] ^= 1u; mark[v] ^= 1u; }
-    bool marked(uint32_t v) const { return mark[v] != 0; }
-    void unmark(uint32_t v) { mark[v] = 0; }
-};
+// the sequential rule on the CPU: t time steps of one replica (isingmc_classical_host_steps, isingmc_classical_host_pt_run)
+void cmc_host_replica_steps(const CmcGraphMem &g, uint64_t seed, uint32_t replica, uint64_t t, double beta, const CmcHostMoves &m, uint8_t *state,
+                            uint8_t *mark, uint64_t *epoch, uint64_t *ctr) {
+    const uint32_t N = g.N();
+    CmcHostState s{state, mark};
+    CmcHostDraw draw{(uint32_t)seed, (uint32_t)(seed >> 32), replica, 0u, 0u};
+    for (uint64_t step = 0; step < t; ++step, ++*epoch) {
+        draw.epoch_lo = (uint32_t)*epoch; draw.epoch_hi24 = (uint32_t)(*epoch >> 32) & 0xFFFFFFu;
+        const uint32_t kind = cmc_step_kind(m.kinds, draw);
+        if (kind == 2u) {
+            uint32_t ndraw = 0;
+            for (uint32_t i = 0; i < m.nworm; ++i) cmc_worm(g, s, beta, m.kinds != CMC_KINDS_WORM_NO_DOUBLES, draw, &ndraw, ctr);
+            continue;
+        }
+        const uint32_t n = kind == 0u ? m.nspin : m.nedge;
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t choice = draw(SSE_TAG_CLASSICAL, cmc_index_move(i), 0), uword = draw(SSE_TAG_CLASSICAL, cmc_index_move(i), 1);
+            uint32_t a, b = CMC_NONE;
+            if (kind == 0u) a = cmc_range(choice, N); else g.edge(cmc_pick_edge(g, choice), a, b);
+            const double de = kind == 0u ? cmc_spin_de(g, s, a) : cmc_edge_de(g, s, a, b);
+            const bool acc = cmc_should_flip(beta, de, uword);
+            if (acc) { s.s[a] ^= 1u; if (kind == 1u) s.s[b] ^= 1u; }
+            ctr[kind == 0u ? CMC_C_SPIN : CMC_C_EDGE] += 1;
+            ctr[kind == 0u ? CMC_C_SPIN_ACC : CMC_C_EDGE_ACC] += acc ? 1u : 0u;
+        }
+    }
+}
 
 extern "C" {
 
 int isingmc_classical_plan(const isingmc_classical_config *cfg, uint32_t lds_bytes, uint32_t out[8]) {
-    if (!out) return refuse(ISINGMC_EINVAL, "null output");
+    if (!out) return cmc_refuse(ISINGMC_EINVAL, "null output");
     CmcHostTables H; CmcCarve C;
     if (const int rc = plan_config(cfg, lds_bytes, H, C)) return rc;
     plan_slots(C, H.flags, out);
@@ -242,14 +202,14 @@ int isingmc_classical_launch_plan(isingmc_classical *g, uint32_t out[8]) {
 }
 
 int isingmc_classical_create(const isingmc_classical_config *cfg, isingmc_classical **out) {
-    if (!out) return refuse(ISINGMC_EINVAL, "null output");
+    if (!out) return cmc_refuse(ISINGMC_EINVAL, "null output");
     *out = nullptr;
-    if (const int rc = check_config(cfg)) return rc;
+    if (const int rc = cmc_check_config(cfg)) return rc;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return refuse(ISINGMC_ENODEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return cmc_refuse(ISINGMC_ENODEVICE, "no HIP device available (this library has no CPU fallback)");
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipSetDevice(dev) != hipSuccess) return refuse(ISINGMC_ENODEVICE, "hipSetDevice failed");
+    if (hipSetDevice(dev) != hipSuccess) return cmc_refuse(ISINGMC_ENODEVICE, "hipSetDevice failed");
     int max_lds = 0;
     if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || max_lds <= 0) max_lds = 65536;
     isingmc_classical *g = new isingmc_classical();
@@ -380,39 +340,18 @@ int isingmc_classical_last_kernel_ms(isingmc_classical *g, float *ms) {
 
 int isingmc_classical_host_steps(const isingmc_classical_config *cfg, uint64_t t, const double *beta, uint32_t nspin, uint32_t nedge,
                                  uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint64_t *counters) {
-    if (const int rc = check_config(cfg)) return rc;
-    if (!beta || !states || !epochs) return refuse(ISINGMC_EINVAL, "beta, states and epochs must be non-null");
-    if (kinds >= CMC_KINDS_COUNT) return refuse(ISINGMC_EINVAL, "kinds must be one of ISINGMC_CLASSICAL_KINDS_*");
+    if (const int rc = cmc_check_config(cfg)) return rc;
+    if (!beta || !states || !epochs) return cmc_refuse(ISINGMC_EINVAL, "beta, states and epochs must be non-null");
+    if (kinds >= CMC_KINDS_COUNT) return cmc_refuse(ISINGMC_EINVAL, "kinds must be one of ISINGMC_CLASSICAL_KINDS_*");
     CmcHostTables H;
-    build_tables(cfg, H);
+    cmc_build_tables(cfg, H);
     const CmcGraphMem g{H.view()};
     const uint32_t N = H.N;
-    const uint32_t ns = cmc_default_moves(nspin, N / 2u), ne = cmc_default_moves(nedge, H.E / 2u), nw = cmc_default_moves(nworm, 1u);
+    const CmcHostMoves m{cmc_default_moves(nspin, N / 2u), cmc_default_moves(nedge, H.E / 2u), cmc_default_moves(nworm, 1u), kinds};
     std::vector<uint8_t> mark(N, 0);
     for (uint32_t r = 0; r < cfg->nreplicas; ++r) {
-        CmcHostState s{states + (size_t)r * N, mark.data()};
         uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        CmcHostDraw draw{(uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32), cfg->replica_offset + r, 0u, 0u};
-        for (uint64_t step = 0; step < t; ++step, ++epochs[r]) {
-            draw.epoch_lo = (uint32_t)epochs[r]; draw.epoch_hi24 = (uint32_t)(epochs[r] >> 32) & 0xFFFFFFu;
-            const uint32_t kind = cmc_step_kind(kinds, draw);
-            if (kind == 2u) {
-                uint32_t ndraw = 0;
-                for (uint32_t i = 0; i < nw; ++i) cmc_worm(g, s, beta[r], kinds != CMC_KINDS_WORM_NO_DOUBLES, draw, &ndraw, ctr);
-                continue;
-            }
-            const uint32_t n = kind == 0u ? ns : ne;
-            for (uint32_t i = 0; i < n; ++i) {
-                const uint32_t choice = draw(SSE_TAG_CLASSICAL, cmc_index_move(i), 0), uword = draw(SSE_TAG_CLASSICAL, cmc_index_move(i), 1);
-                uint32_t a, b = CMC_NONE;
-                if (kind == 0u) a = cmc_range(choice, N); else g.edge(cmc_pick_edge(g, choice), a, b);
-                const double de = kind == 0u ? cmc_spin_de(g, s, a) : cmc_edge_de(g, s, a, b);
-                const bool acc = cmc_should_flip(beta[r], de, uword);
-                if (acc) { s.s[a] ^= 1u; if (kind == 1u) s.s[b] ^= 1u; }
-                ctr[kind == 0u ? CMC_C_SPIN : CMC_C_EDGE] += 1;
-                ctr[kind == 0u ? CMC_C_SPIN_ACC : CMC_C_EDGE_ACC] += acc ? 1u : 0u;
-            }
-        }
+        cmc_host_replica_steps(g, cfg->seed, cfg->replica_offset + r, t, beta[r], m, states + (size_t)r * N, mark.data(), &epochs[r], ctr);
         for (int i = 0; counters && i < 8; ++i) counters[(size_t)r * 8 + i] += ctr[i];
     }
     return ISINGMC_OK;

@@ -1,0 +1,96 @@
+// classical_handle.h — what the two host files of classical Monte Carlo share (classical.hip: creation, time steps, accessors;
+// classical_pt.hip: tempering): the handle, the host form of the graph tables, the config check and the step loop of the sequential
+// rule.  Internal: the C ABI is include/isingmc_hip.h.
+#pragma once
+#include "../../include/isingmc_hip.h"
+#include "classical_launch.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+// the graph tables of classical_rule.h on the host
+struct CmcHostTables {
+    std::vector<uint32_t> row, ent, edges;
+    std::vector<double> jv, bias, cum;
+    uint32_t N = 0, E = 0, flags = 0;
+    double totalw = 0.0;
+    CmcTables view() const {
+        return CmcTables{N, E, flags, (uint32_t)jv.size(), row.data(), ent.data(), jv.data(), bias.empty() ? nullptr : bias.data(), edges.data(),
+                         cum.empty() ? nullptr : cum.data(), totalw};
+    }
+};
+
+// tempering (isingmc_classical_pt_attach): every array is allocated once at its largest size, R entries
+struct CmcPtHandle {
+    bool attached = false;
+    sse::CmcPtDev dev{};
+    double *d_betas = nullptr;
+    uint64_t step = 0;
+    std::vector<double> betas;
+};
+
+struct isingmc_classical {
+    sse::CmcDev dev{};
+    sse::CmcCarve carve{};
+    CmcHostTables host;
+    uint32_t flags = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+    double *d_beta = nullptr, *d_energy = nullptr;
+    CmcPtHandle pt;
+    std::vector<void *> allocs;
+    mutable std::string err;
+};
+
+#define CMC_TRY(g, expr)                                                                              \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) {                                                                       \
+            (g)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                             \
+            return ISINGMC_ENODEVICE;                                                                 \
+        }                                                                                             \
+    } while (0)
+
+template <typename T>
+static int cmc_upload(isingmc_classical *g, const T **p, const std::vector<T> &v) {
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
+    CMC_TRY(g, hipMalloc(&q, bytes));
+    g->allocs.push_back(q);
+    if (!v.empty()) CMC_TRY(g, hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *p = reinterpret_cast<const T *>(q);
+    return ISINGMC_OK;
+}
+template <typename T>
+static int cmc_alloc(isingmc_classical *g, T **p, size_t count) {
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    CMC_TRY(g, hipMalloc(&q, bytes));
+    g->allocs.push_back(q);
+    CMC_TRY(g, hipMemset(q, 0, bytes));
+    *p = reinterpret_cast<T *>(q);
+    return ISINGMC_OK;
+}
+
+// a replica's state as bytes on the host, with the marks of the worm next to them
+struct CmcHostState {
+    uint8_t *s, *mark;
+    bool get(uint32_t v) const { return s[v] != 0; }
+    void flip(uint32_t v) { s[v] ^= 1u; mark[v] ^= 1u; }
+    bool marked(uint32_t v) const { return mark[v] != 0; }
+    void unmark(uint32_t v) { mark[v] = 0; }
+};
+// the move counts of a step as the launches resolve them
+struct CmcHostMoves { uint32_t nspin, nedge, nworm, kinds; };
+
+// classical.hip
+int cmc_refuse(int rc, const std::string &why); // the error text of a call without a handle
+int cmc_check_config(const isingmc_classical_config *cfg);
+void cmc_build_tables(const isingmc_classical_config *cfg, CmcHostTables &H);
+// t time steps of replica `replica` (its global index) by the sequential rule: state [N] bytes, mark [N] zeroed scratch, *epoch
+// advanced, ctr [8] added to
+void cmc_host_replica_steps(const CmcGraphMem &g, uint64_t seed, uint32_t replica, uint64_t t, double beta, const CmcHostMoves &m, uint8_t *state,
+                            uint8_t *mark, uint64_t *epoch, uint64_t *ctr);

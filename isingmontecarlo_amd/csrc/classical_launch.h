@@ -87,4 +87,18 @@ hipError_t launch_classical_steps(hipStream_t stream, const CmcDev &D, const Cmc
 hipError_t launch_classical_energies(hipStream_t stream, const CmcDev &D, double *out);
 hipError_t launch_classical_init_state(hipStream_t stream, const CmcDev &D, uint32_t N);
 
+// The tempering launch (classical_pt_rule.h; sse_classical_pt.hip.h, unit sweep_classical_pt.hip): R = C T slots, all in global memory
+#define CMC_PT_MAX_WAVES 16u // a workgroup has min(T, 16) waves: the energy of a slot is a chain of dependent loads, which only more waves hide
+struct CmcPtDev {
+    uint32_t T, C;                // temperatures per chain, chains
+    const double *betas;          // [T] the ladder
+    uint32_t *temp_of, *slot_at;  // [R] temperature of a slot; slot (within its chain) at a temperature
+    double *beta_slot;            // [R] betas[temp_of[r]]: what the next steps launch reads
+    double *energy;               // [R] by slot, of the latest round
+    int32_t *mag;                 // [R]
+    uint64_t *attempts, *accepts; // [C][T - 1]
+};
+// one tempering step of every chain at step number pt_step; energy_row / mag_row: [C][T] by temperature, or null
+hipError_t launch_classical_tempering(hipStream_t stream, const CmcDev &D, const CmcPtDev &P, uint64_t pt_step, double *energy_row, int32_t *mag_row);
+
 } // namespace sse

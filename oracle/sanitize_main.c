@@ -18,6 +18,11 @@ int main(void) {
         if (ora_timesteps(r, 300, 1.5, 2, flagsets[f]) != 0 || !ora_verify(r)) bad = 1;
         int64_t a; uint64_t b, c;
         ora_itime_magnetization(r, &a, &b, &c);
+        if (f == 1) { /* one traced directed loop into a buffer shorter than most walks: the rows stop, the walk does not */
+            uint32_t rows[3 * ORA_LOOP_NCOLS], start[2];
+            const uint32_t len = ora_loop_update_trace(r, rows, 3, start);
+            if (len == 0 || rows[ORA_LOOP_P] != start[1] || !ora_verify(r)) bad = 1;
+        }
         ora_replica_destroy(r);
     }
     ora_model *m2 = ora_model_create(9, 18, ea, eb, J, 0.7, 0.0);

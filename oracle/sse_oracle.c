@@ -436,7 +436,7 @@ void ora_flip_free_spins(ora_replica *r) {
 /* qmc_traits/directed_loop.rs:103-171 (start selection) and :217-301 (loop body).
  * Legs are numbered inputs 0..k-1 then outputs 0..k-1 (:233-240). */
 static int next_on_worldline(const ora_replica *r, uint32_t p, uint32_t var, int forward, uint32_t *np,
-                             uint32_t *nrel, int *wrapped) {
+                             uint32_t *nrel, int *wrapped, uint32_t *dist) {
     const ora_model *m = r->m;
     const uint32_t M = r->cutoff;
     *wrapped = 0;
@@ -447,16 +447,19 @@ static int next_on_worldline(const ora_replica *r, uint32_t p, uint32_t var, int
         uint32_t w = r->ops[q];
         if (w == SSE_OP_EMPTY) continue;
         uint32_t b = sse_op_bond(w);
-        if (m->bond_a[b] == var) { *np = q; *nrel = 0; return 1; }
-        if (m->bond_b[b] == var) { *np = q; *nrel = 1; return 1; }
+        if (m->bond_a[b] == var) { *np = q; *nrel = 0; *dist = step + 1; return 1; }
+        if (m->bond_b[b] == var) { *np = q; *nrel = 1; *dist = step + 1; return 1; }
     }
     return 0;
 }
 
-uint32_t ora_loop_update(ora_replica *r) {
+/* One loop update.  rows (NULL, or [cap_rows][ORA_LOOP_NCOLS]) receives one row per visited vertex while there is room: the walk
+ * itself never depends on it.  start (NULL, or [2]) receives nth and p0 (both 0 for a replica without ops). */
+uint32_t ora_loop_update_trace(ora_replica *r, uint32_t *rows, uint32_t cap_rows, uint32_t *start) {
     const ora_model *m = r->m;
     const uint32_t M = r->cutoff;
     uint32_t visited = 0;
+    if (start) start[0] = start[1] = 0;
     if (r->n == 0) { r->epoch += 1; return 0; }
     uint32_t o[4];
     draw(r, SSE_TAG_LOOP, 0, o);
@@ -469,6 +472,7 @@ uint32_t ora_loop_update(ora_replica *r) {
     uint32_t rel0 = mulhi32(o[1], k0);
     uint32_t side0 = (o[2] >> 31) ? 0u : 1u; /* gen() true -> Inputs(0) else Outputs(1) (:153-157) */
     uint32_t p = p0, rel = rel0, side = side0;
+    if (start) { start[0] = nth; start[1] = p0; }
     for (uint32_t step = 1;; ++step) {
         uint32_t w = r->ops[p], b = sse_op_bond(w);
         uint32_t k = (m->bond_b[b] != SSE_NO_VAR) ? 2u : 1u;
@@ -493,19 +497,29 @@ uint32_t ora_loop_update(ora_replica *r) {
         uint32_t xside = exit_leg < k ? 0u : 1u, xrel = exit_leg < k ? exit_leg : exit_leg - k;
         if (xside == 0) in_e ^= 1u << xrel; else out_e ^= 1u << xrel;
         r->ops[p] = sse_op_make(b, in_e, out_e);
+        uint32_t *row = (rows && visited < cap_rows) ? rows + (size_t)visited * ORA_LOOP_NCOLS : NULL;
         visited++;
-        if (p == p0 && xrel == rel0 && xside == side0) break; /* :266 */
+        if (row) {
+            memset(row, 0, sizeof(uint32_t) * ORA_LOOP_NCOLS);
+            row[ORA_LOOP_P] = p; row[ORA_LOOP_ESIDE] = side; row[ORA_LOOP_EREL] = rel;
+            row[ORA_LOOP_XSIDE] = xside; row[ORA_LOOP_XREL] = xrel; row[ORA_LOOP_WORD] = r->ops[p];
+        }
+        if (p == p0 && xrel == rel0 && xside == side0) { if (row) row[ORA_LOOP_CLOSED] = 1; break; } /* :266 */
         uint32_t var = xrel == 0 ? m->bond_a[b] : m->bond_b[b];
-        uint32_t np, nrel;
+        uint32_t np, nrel, dist = M;
         int wrapped;
         /* the op itself is the only one on the worldline => next is itself after a full wrap */
-        if (!next_on_worldline(r, p, var, xside == 1, &np, &nrel, &wrapped)) {
-            np = p; nrel = xrel; wrapped = 1;
+        if (!next_on_worldline(r, p, var, xside == 1, &np, &nrel, &wrapped, &dist)) {
+            np = p; nrel = xrel; wrapped = 1; dist = M;
         }
         if (wrapped) /* :276-288 */
             r->state[var] = (uint8_t)(((xside == 1 ? out_e : in_e) >> xrel) & 1u);
         uint32_t nside = xside ^ 1u;
-        if (np == p0 && nrel == rel0 && nside == side0) break; /* :293 */
+        if (row) {
+            row[ORA_LOOP_VAR] = var; row[ORA_LOOP_DIST] = dist; row[ORA_LOOP_FORWARD] = xside == 1;
+            row[ORA_LOOP_WRAPPED] = (uint32_t)wrapped;
+        }
+        if (np == p0 && nrel == rel0 && nside == side0) { if (row) row[ORA_LOOP_CLOSED] = 2; break; } /* :293 */
         p = np; rel = nrel; side = nside;
         if (step > (1u << 30)) break;
     }
@@ -513,6 +527,7 @@ uint32_t ora_loop_update(ora_replica *r) {
     r->epoch += 1;
     return visited;
 }
+uint32_t ora_loop_update(ora_replica *r) { return ora_loop_update_trace(r, NULL, 0, NULL); }
 
 /* ---------------------------------------------------------------------------- driver --- */
 static void measure(ora_replica *r) {

@@ -55,6 +55,15 @@ void ora_heatbath_update(ora_replica *r, double beta);
 uint32_t ora_cluster_update(ora_replica *r, double prob);
 void ora_flip_free_spins(ora_replica *r);
 uint32_t ora_loop_update(ora_replica *r); /* returns number of vertices visited */
+/* The same loop; rows (NULL, or [cap_rows][ORA_LOOP_NCOLS]) receives one row per visited vertex, start (NULL, or [2]) the rank nth
+ * of the start vertex among the occupied slots and its slot p0.  A walk longer than cap_rows runs to its end and returns its
+ * length; only the rows stop.  P slot; ESIDE, EREL the leg entered (side 0 inputs, 1 outputs); XSIDE, XREL the leg left; WORD the
+ * op word as rewritten; CLOSED 1 the walk ended at this vertex (directed_loop.rs:266: no search follows, the next four are 0),
+ * 2 it ended on arriving at the start leg (:293), 0 it went on.  Of the search that followed: VAR the worldline; DIST the distance
+ * 1..cutoff at which the next op was found (cutoff: the op itself); FORWARD the direction; WRAPPED the search passed p = 0. */
+enum { ORA_LOOP_P = 0, ORA_LOOP_ESIDE, ORA_LOOP_EREL, ORA_LOOP_XSIDE, ORA_LOOP_XREL, ORA_LOOP_VAR, ORA_LOOP_DIST, ORA_LOOP_FORWARD,
+       ORA_LOOP_WRAPPED, ORA_LOOP_CLOSED, ORA_LOOP_WORD, ORA_LOOP_NCOLS };
+uint32_t ora_loop_update_trace(ora_replica *r, uint32_t *rows, uint32_t cap_rows, uint32_t *start);
 /* RvbUpdater::rvb_update_with_ising_weight (qmc_traits/rvb.rs:88-290): `updates` attempts; returns #accepted */
 uint32_t ora_rvb_update(ora_replica *r, uint32_t updates);
 /* The same sweep; stats (NULL, or [updates][ORA_RVB_NSTATS]) receives one row per attempt: the sizes that the device kernels hold

@@ -11,6 +11,8 @@ _LIB = os.path.join(_ORACLE_DIR, "libsse_oracle.so")
 
 FLAG_LOOP, FLAG_NO_CLUSTER, FLAG_HEATBATH, FLAG_RVB = 1, 2, 4, 8
 # columns of Replica.rvb_update(..., stats=True): the enum ORA_RVB_* of oracle/sse_oracle.h, in its order
+# columns of Replica.loop_update_trace(): the enum ORA_LOOP_* of oracle/sse_oracle.h, in its order
+LOOP_TRACE = ("p", "eside", "erel", "xside", "xrel", "var", "dist", "forward", "wrapped", "closed", "word")
 RVB_STATS = ("csize", "ncl", "bf", "bn", "ncand", "nsub", "ntog", "nwin", "bonds_prob", "bonds_mut", "nadj", "accept")
 
 
@@ -36,6 +38,7 @@ def load():
         "ora_cluster_update": (u32, [vp, f64]),
         "ora_flip_free_spins": (None, [vp]),
         "ora_loop_update": (u32, [vp]),
+        "ora_loop_update_trace": (u32, [vp, p(u32), u32, p(u32)]),
         "ora_timestep": (C.c_int, [vp, f64, u32]),
         "ora_timesteps": (C.c_int, [vp, u64, f64, u32, u32]),
         "ora_model_create_generic": (vp, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
@@ -178,6 +181,14 @@ class Replica:
 
     def loop_update(self):
         return lib().ora_loop_update(self.ptr)
+
+    def loop_update_trace(self, cap_rows=1 << 16):
+        """One loop update with its trace: (length, rows [min(length, cap_rows)][len(LOOP_TRACE)], (nth, p0)); sse_oracle.h:
+        ORA_LOOP_*.  A longer walk still runs to its end."""
+        rows = np.zeros((int(cap_rows), len(LOOP_TRACE)), dtype=np.uint32)
+        start = np.zeros(2, dtype=np.uint32)
+        length = lib().ora_loop_update_trace(self.ptr, _ptr(rows, C.c_uint32), int(cap_rows), _ptr(start, C.c_uint32))
+        return length, rows[:min(length, int(cap_rows))], (int(start[0]), int(start[1]))
 
     def rvb_update(self, updates, stats=False):
         """Successes of one sweep; with stats also its working set, [updates][len(RVB_STATS)] (sse_oracle.h: ORA_RVB_*)."""

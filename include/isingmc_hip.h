@@ -425,7 +425,8 @@ typedef struct isingmc_pt_phase {
 int isingmc_pt_plan_phase(isingmc_pt_phase *view);
 
 /* ---- classical Monte Carlo: qmc::classical::GraphState (src/classical/graph.rs) for a batch of replicas --------------------------
- * One handle = R replicas of one graph (edges, couplings, biases common to the batch; beta per replica), resident on one device.
+ * One handle = R replicas of one graph (edges and biases common to the batch; couplings common, or with
+ * ISINGMC_CLASSICAL_CFG_PER_REPLICA_J one row per replica: disorder realisations; beta per replica), resident on one device.
  * The moves are stated once in csrc/classical_rule.h; their random numbers are the Philox streams of sse_format.h (tags CLASSICAL
  * and CLASSICAL_WORM; epoch = the replica's time-step counter), so a run is a function of (seed, replica, epoch) alone: any split of
  * a run into calls, batches or devices gives the same states.  On the device one wave64 owns a replica and evaluates 64 consecutive
@@ -433,6 +434,10 @@ int isingmc_pt_plan_phase(isingmc_pt_phase *view);
 #define ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE 1u /* enable_edge_importance_sampling(true) (graph.rs:320-336); needs every J > 0 */
 #define ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES 2u   /* keep the graph tables in global memory even when they fit in LDS (testing) */
 #define ISINGMC_CLASSICAL_CFG_SERIAL_MOVES 4u    /* the wave takes one move at a time (testing / A-B timing); same results */
+/* J is [R][E], row r for local replica r (as ISINGMC_CFG_PER_REPLICA_J of isingmc_create): disorder realisations on one topology.
+ * Replica r runs exactly as a replica of a shared-coupling batch with J = row r at the same global index replica_offset + r. */
+#define ISINGMC_CLASSICAL_CFG_PER_REPLICA_J 8u
+#define ISINGMC_CLASSICAL_CFG_GLOBAL_CODES 16u /* keep the per-replica coupling codes in global memory (testing / A-B timing); same results */
 /* `kinds` of isingmc_classical_timesteps */
 #define ISINGMC_CLASSICAL_KINDS_ALL 0u   /* spin, edge or worm step, drawn per step as do_time_step does (graph.rs:364-365) */
 #define ISINGMC_CLASSICAL_KINDS_BASIC 1u /* only_basic_moves = Some(true): spin or edge step */
@@ -448,7 +453,7 @@ typedef struct isingmc_classical_config {
     uint32_t nvars;            /* N = biases.len() (graph.rs:69); at most 2^24 */
     uint32_t nedges;           /* E >= 1 (the reference's edge move would panic on an empty edge list) */
     const uint32_t *edges;     /* [2E]: a0,b0,a1,b1,...; a self-loop is ISINGMC_EINVAL as in isingmc_create */
-    const double *J;           /* [E] */
+    const double *J;           /* [E]; [R][E] with ISINGMC_CLASSICAL_CFG_PER_REPLICA_J */
     const double *biases;      /* [N] longitudinal fields, or NULL: all zero */
     uint64_t seed;             /* Philox key */
     uint32_t replica_offset;   /* global index of local replica 0 */
@@ -484,9 +489,12 @@ int isingmc_classical_last_kernel_ms(isingmc_classical *g, float *ms);
 /* Host-only, a device-free test entry: the launch isingmc_classical_create plans for cfg on a device whose workgroups have lds_bytes
  * of LDS, by the function create itself calls, or the code and message it would refuse cfg with.  out[0] waves (= replicas) per
  * workgroup; out[1] which tables live in LDS, bit 0 row starts, 1 row entries, 2 couplings, 3 biases, 4 edge list, 5 cumulative edge
- * weights (a table the model does not have has its bit clear); out[2] dynamic LDS words of the launch; out[3] LDS words per wave
- * (state bits and stamp bytes); out[4] bits of out[1] that the model has at all; out[5] 1 = couplings kept as a dictionary of at most
- * 256 values; out[6] 1 = edges packed into one word; out[7] 0 */
+ * weights, 6 the per-replica coupling table (a table the model does not have has its bit clear); out[2] dynamic LDS words of the
+ * launch; out[3] LDS words per wave (state bits and stamp bytes, and the wave's coupling codes when they are in LDS); out[4] bits of
+ * out[1] that the model has at all; out[5] 1 = couplings kept as a dictionary of at most 256 values; out[6] 1 = edges packed into
+ * one word; out[7] the coupling format: 0 shared by the batch, 1 per-replica code bytes into a dictionary of the whole batch (at most
+ * 256 distinct values over all R E couplings), 2 per-replica doubles.  With per-replica couplings bit 2 is the dictionary (format 1
+ * only), and the doubles of format 2 and the per-replica cumulative weights are read from global memory always. */
 int isingmc_classical_plan(const isingmc_classical_config *cfg, uint32_t lds_bytes, uint32_t out[8]);
 /* The launch this handle runs with: the eight slots of isingmc_classical_plan, as isingmc_classical_create chose them from the LDS
  * size of the handle's own device.  Read-only; no device call. */
@@ -506,7 +514,8 @@ int isingmc_classical_host_steps(const isingmc_classical_config *cfg, uint64_t t
  * computes every slot's energy and magnetisation, records them by temperature (the values before the round's swaps) and takes one
  * tempering step of every chain; pt_step increments per round.
  * Errors (ISINGMC_EINVAL with a message): ntemps < 2, R % ntemps != 0, replica_offset % ntemps != 0, a non-finite beta, a null
- * ladder; pt_run / pt_get / pt_set / pt_swap_counts before pt_attach.  isingmc_classical_timesteps on an attached handle behaves as
+ * ladder; with ISINGMC_CLASSICAL_CFG_PER_REPLICA_J, a chain whose T coupling rows are not bitwise equal (the swap rule holds inside
+ * one Hamiltonian: the batch is C realisations x T temperatures; chains may differ from each other); pt_run / pt_get / pt_set / pt_swap_counts before pt_attach.  isingmc_classical_timesteps on an attached handle behaves as
  * without tempering: it takes its own beta array and leaves the maps alone. */
 /* Allocate (first call) and reset the maps, the swap counters and pt_step. */
 int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const double *betas);

@@ -345,6 +345,8 @@ class QmcIsingGraph:
         assert not np.any(np.asarray(graph.biases) != 0.0), "new_from_graph: every bias of the classical graph must be zero (qmc_ising.rs:157)"
         kw.setdefault("nreplicas", graph.nreplicas)
         kw.setdefault("nvars", graph.nvars)
+        if getattr(graph, "couplings", None) is not None:  # per-replica couplings: the same realisation for each quantum replica
+            kw.setdefault("couplings", graph.couplings)
         return cls(graph.edge_list(), transverse, longitudinal, cutoff, seed, state=graph.state_ref(), **kw)
 
     # ---- lifetime ----

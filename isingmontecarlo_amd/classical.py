@@ -1,5 +1,5 @@
 """Classical Ising Monte Carlo on the device: `GraphState` (qmc::classical::GraphState, src/classical/graph.rs) for a batch of R
-replicas of one graph, over the isingmc_classical_* entry points of include/isingmc_hip.h.  All moves run in gfx950 kernels
+replicas of one graph (with `couplings`: of R disorder realisations on one graph), over the isingmc_classical_* entry points of include/isingmc_hip.h.  All moves run in gfx950 kernels
 (csrc/sse_classical.hip.h), and so does replica exchange between the temperatures of a chain (csrc/sse_classical_pt.hip.h); there is
 no CPU fallback.  `host_steps`, `host_tempering_run` and `plan` are the device-free test entries of the C ABI."""
 import ctypes as C
@@ -9,9 +9,9 @@ import numpy as np
 from . import ALL, IsingMcError, QmcIsingGraph, _ClassicalConfig, _ptr, load_library  # (imported at the end of the package's __init__)
 
 __all__ = ["GraphState", "new_qmc_from_graph", "host_steps", "host_tempering_run", "plan", "CFG_EDGE_IMPORTANCE", "CFG_GLOBAL_TABLES", "CFG_SERIAL_MOVES",
-           "KINDS_ALL", "KINDS_BASIC", "KINDS_SPIN", "KINDS_EDGE", "KINDS_WORM", "KINDS_WORM_NO_DOUBLES", "COUNTERS"]
+           "CFG_PER_REPLICA_J", "CFG_GLOBAL_CODES",           "KINDS_ALL", "KINDS_BASIC", "KINDS_SPIN", "KINDS_EDGE", "KINDS_WORM", "KINDS_WORM_NO_DOUBLES", "COUNTERS"]
 
-CFG_EDGE_IMPORTANCE, CFG_GLOBAL_TABLES, CFG_SERIAL_MOVES = 1, 2, 4
+CFG_EDGE_IMPORTANCE, CFG_GLOBAL_TABLES, CFG_SERIAL_MOVES, CFG_PER_REPLICA_J, CFG_GLOBAL_CODES = 1, 2, 4, 8, 16
 KINDS_ALL, KINDS_BASIC, KINDS_SPIN, KINDS_EDGE, KINDS_WORM, KINDS_WORM_NO_DOUBLES = range(6)
 NONE = 0xFFFFFFFF  # the reference's None for the move counts
 COUNTERS = ("spin_attempted", "spin_accepted", "edge_attempted", "edge_accepted", "worm_attempted", "worm_kept", "worm_failures", "worm_path_entries")
@@ -22,6 +22,19 @@ def _model(edges, biases):
     js = np.ascontiguousarray(np.array([j for _, j in edges], dtype=np.float64))
     hs = np.ascontiguousarray(np.asarray(biases, dtype=np.float64))
     return ed, js, hs
+
+
+def _couplings(couplings, js, nreplicas, flags):
+    """(J array of the config, flags): `couplings` float64 [nreplicas][nedges] replaces the J of the edges and sets CFG_PER_REPLICA_J."""
+    flags = int(flags)
+    if couplings is None:
+        if flags & CFG_PER_REPLICA_J:
+            raise IsingMcError(-1, "CFG_PER_REPLICA_J needs the couplings argument")
+        return js, flags
+    cj = np.ascontiguousarray(np.asarray(couplings, dtype=np.float64))
+    if cj.shape != (int(nreplicas), len(js)):
+        raise IsingMcError(-1, "couplings must have shape [nreplicas][nedges]")
+    return cj, flags | CFG_PER_REPLICA_J
 
 
 def _config(ed, js, hs, seed, nreplicas, replica_offset=0, device=-1, init=None, flags=0):
@@ -40,26 +53,32 @@ def _kinds(only_basic_moves, kinds):
 
 
 def _plan_dict(out):
-    return dict(waves=out[0], in_lds=out[1], lds_words=out[2], wave_words=out[3], tables=out[4], compact_couplings=bool(out[5]), packed_edges=bool(out[6]))
+    return dict(waves=out[0], in_lds=out[1], lds_words=out[2], wave_words=out[3], tables=out[4], compact_couplings=bool(out[5]), packed_edges=bool(out[6]),
+                coupling_format=out[7])
 
 
-def plan(edges, biases, lds_bytes=160 * 1024, flags=0):
-    """isingmc_classical_plan: the launch isingmc_classical_create would choose, without a device."""
+def plan(edges, biases, lds_bytes=160 * 1024, flags=0, couplings=None):
+    """isingmc_classical_plan: the launch isingmc_classical_create would choose, without a device.  `couplings` [R][E]: the plan of a
+    batch of R realisations (coupling_format: 0 shared, 1 per-replica codes, 2 per-replica doubles)."""
     lib = load_library()
     ed, js, hs = _model(edges, biases)
+    nrep = 1 if couplings is None else len(couplings)
+    js, flags = _couplings(couplings, js, nrep, flags)
     out = (C.c_uint32 * 8)()
-    rc = lib.isingmc_classical_plan(C.byref(_config(ed, js, hs, 0, 1, flags=flags)), int(lds_bytes), out)
+    rc = lib.isingmc_classical_plan(C.byref(_config(ed, js, hs, 0, nrep, flags=flags)), int(lds_bytes), out)
     if rc:
         raise IsingMcError(rc, lib.isingmc_classical_last_error(None).decode())
     return _plan_dict(out)
 
 
 def host_steps(edges, biases, seed, states, epochs, t, beta, nspinupdates=None, nedgeupdates=None, nwormupdates=None, only_basic_moves=None,
-               kinds=None, replica_offset=0, flags=0):
-    """isingmc_classical_host_steps: t time steps of the sequential rule on the CPU.  Returns (states, epochs, counters)."""
+               kinds=None, replica_offset=0, flags=0, couplings=None):
+    """isingmc_classical_host_steps: t time steps of the sequential rule on the CPU.  Returns (states, epochs, counters).
+    `couplings` [R][E]: replica r runs on row r."""
     lib = load_library()
     ed, js, hs = _model(edges, biases)
     st = np.ascontiguousarray(np.array(states, dtype=np.uint8).reshape(-1, len(hs)))
+    js, flags = _couplings(couplings, js, len(st), flags)
     ep = np.ascontiguousarray(np.broadcast_to(np.asarray(epochs, dtype=np.uint64), (len(st),)).copy())
     ctr = np.zeros((len(st), 8), dtype=np.uint64)
     b = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64), (len(st),)))
@@ -72,14 +91,16 @@ def host_steps(edges, biases, seed, states, epochs, t, beta, nspinupdates=None, 
 
 
 def host_tempering_run(edges, biases, seed, states, epochs, betas, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None,
-                       only_basic_moves=None, kinds=None, temp_of=None, pt_step=0, replica_offset=0, flags=0, record=True):
+                       only_basic_moves=None, kinds=None, temp_of=None, pt_step=0, replica_offset=0, flags=0, record=True, couplings=None):
     """isingmc_classical_host_pt_run: `rounds` rounds of (`steps` time steps, one tempering step) by the sequential rule on the CPU, for
     R = len(states) slots as chains of T = len(betas) temperatures.  Returns a dict: states [R][N], epochs [R], temp_of [R], pt_step,
-    counters [R][8], attempts and accepts [C][T - 1], and with `record` energy and magnetization [rounds][C][T]."""
+    counters [R][8], attempts and accepts [C][T - 1], and with `record` energy and magnetization [rounds][C][T].  `couplings` [R][E]:
+    the T rows of every chain must be equal (C realisations x T temperatures)."""
     lib = load_library()
     ed, js, hs = _model(edges, biases)
     st = np.ascontiguousarray(np.array(states, dtype=np.uint8).reshape(-1, len(hs)))
     nrep = len(st)
+    js, flags = _couplings(couplings, js, nrep, flags)
     ep = np.ascontiguousarray(np.broadcast_to(np.asarray(epochs, dtype=np.uint64), (nrep,)).copy())
     ladder = None if betas is None else np.ascontiguousarray(np.asarray(betas, dtype=np.float64).reshape(-1))
     ntemps = 0 if ladder is None else len(ladder)
@@ -107,16 +128,19 @@ def host_tempering_run(edges, biases, seed, states, epochs, betas, rounds, steps
 
 class GraphState:
     """R replicas of GraphState::new / new_with_state_and_rng (graph.rs:56-88): `edges` = [((a, b), J), ...], `biases` the
-    longitudinal fields (their length is the number of variables), `seed` in place of the rng; `state` [N] or [R][N] (None: random)."""
+    longitudinal fields (their length is the number of variables), `seed` in place of the rng; `state` [N] or [R][N] (None: random).
+    `couplings` (float64 [nreplicas][nedges]) gives every replica its own J values on the same graph (disorder realisations, as in
+    QmcIsingGraph); the J of `edges` is then ignored.  Replica r runs exactly as a replica of a batch with J = couplings[r]."""
 
-    def __init__(self, edges, biases, seed, state=None, nreplicas=1, replica_offset=0, device=-1, cfg_flags=0):
+    def __init__(self, edges, biases, seed, state=None, nreplicas=1, replica_offset=0, device=-1, cfg_flags=0, couplings=None):
         self._lib = load_library()
         self._h = None
         self._edge_list = [((int(a), int(b)), float(j)) for (a, b), j in edges]
         self.edges, self.J, self.biases = _model(edges, biases)
         self.nvars, self.nreplicas = len(self.biases), int(nreplicas)
         self.seed, self.replica_offset, self.device = int(seed), int(replica_offset), int(device)
-        self._cfg_flags = int(cfg_flags)
+        cj, self._cfg_flags = _couplings(couplings, self.J, self.nreplicas, cfg_flags)
+        self.couplings = None if couplings is None else cj  # [R][E], or None: the batch shares the J of its edges
         self._counter_base = np.zeros((self.nreplicas, 8), dtype=np.uint64)
         self._ladder = None  # the ladder of attach_tempering
         init = None
@@ -130,7 +154,7 @@ class GraphState:
         self._create(init)
 
     def _create(self, init):
-        cfg = _config(self.edges, self.J, self.biases, self.seed, self.nreplicas, self.replica_offset, self.device, init, self._cfg_flags)
+        cfg = _config(self.edges, self.J if self.couplings is None else self.couplings, self.biases, self.seed, self.nreplicas, self.replica_offset, self.device, init, self._cfg_flags)
         h = C.c_void_p()
         rc = self._lib.isingmc_classical_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -315,34 +339,44 @@ class GraphState:
     def save_checkpoint(self, path):
         """States, time-step counters, move counters and options of every replica (.npz).  A batch built on the same model and seed and
         restored with load_checkpoint continues bit-exactly.  With tempering attached the file is format 2: it also holds the ladder, the
-        map of slots to temperatures, the tempering step number and both swap counters; without, it is the format-1 file."""
+        map of slots to temperatures, the tempering step number and both swap counters; without, it is the format-1 file.  A batch with
+        per-replica couplings writes format 3: `couplings` [R][E] next to the keys of format 1, and those of format 2 when tempering is
+        attached."""
         extra = {}
         if self._ladder is not None:
             ladder, temp_of, pt_step, attempts, accepts = self._tempering_state()
             extra = dict(ladder=ladder, temp_of=temp_of, pt_step=np.array([pt_step], dtype=np.uint64), swap_attempts=attempts, swap_accepts=accepts)
-        np.savez_compressed(path, format=np.array([2 if extra else 1], dtype=np.uint32), edges=self.edges, J=self.J, biases=self.biases,
+        fmt = 2 if extra else 1
+        if self.couplings is not None:
+            fmt, extra = 3, dict(extra, couplings=self.couplings)
+        np.savez_compressed(path, format=np.array([fmt], dtype=np.uint32), edges=self.edges, J=self.J, biases=self.biases,
                             seed=np.array([self.seed], dtype=np.uint64), replica_offset=np.array([self.replica_offset], dtype=np.uint32),
                             importance=np.array([bool(self._cfg_flags & CFG_EDGE_IMPORTANCE)]), state=self.state_ref(), epoch=self.get_epoch(),
                             counters=self.counters(), **extra)
 
     def load_checkpoint(self, path):
         z = np.load(path, allow_pickle=False)
-        if int(z["format"][0]) not in (1, 2):
+        fmt = int(z["format"][0])
+        if fmt not in (1, 2, 3):
             raise IsingMcError(-1, "unknown checkpoint format")
         if not np.array_equal(z["edges"], self.edges) or not np.array_equal(z["J"], self.J) or not np.array_equal(z["biases"], self.biases):
             raise IsingMcError(-1, "checkpoint belongs to a different model")
+        if (fmt == 3) != (self.couplings is not None) or (fmt == 3 and not np.array_equal(z["couplings"].view(np.uint64), self.couplings.view(np.uint64))):
+            raise IsingMcError(-1, "checkpoint belongs to a batch with different per-replica couplings")
         if z["state"].shape != (self.nreplicas, self.nvars) or int(z["seed"][0]) != self.seed or int(z["replica_offset"][0]) != self.replica_offset:
             raise IsingMcError(-1, "checkpoint belongs to a different batch (replicas, seed or replica offset)")
         self.enable_edge_importance_sampling(bool(z["importance"][0]))
         self.set_state(z["state"])
         self.set_epoch(z["epoch"])
         self._counter_base = z["counters"].astype(np.uint64) - (self.counters() - self._counter_base)
-        if int(z["format"][0]) == 2:
+        if fmt == 2 or (fmt == 3 and "ladder" in z.files):
             self._restore_tempering(z["ladder"], z["temp_of"], int(z["pt_step"][0]), z["swap_attempts"], z["swap_accepts"])
 
-    def edge_list(self):
-        """The edges as they were given: [((a, b), J), ...]."""
-        return list(self._edge_list)
+    def edge_list(self, r=None):
+        """The edges as they were given: [((a, b), J), ...]; with `r`, the edges of replica r's realisation (its row of `couplings`)."""
+        if r is None or self.couplings is None:
+            return list(self._edge_list)
+        return [(ab, float(j)) for (ab, _), j in zip(self._edge_list, self.couplings[int(r)])]
 
 
 def new_qmc_from_graph(graph, transverse, longitudinal, cutoff, seed, **kw):

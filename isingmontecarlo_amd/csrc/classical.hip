@@ -25,16 +25,23 @@ int cmc_check_config(const isingmc_classical_config *cfg) {
     if (!cfg->edges || !cfg->J) return cmc_refuse(ISINGMC_EINVAL, "edges and J must be non-null");
     if (cfg->nvars > CMC_MAX_VARS) return cmc_refuse(ISINGMC_EINVAL, "too many variables (at most 2^24)");
     if (cfg->nedges > 0x3FFFFFFFu) return cmc_refuse(ISINGMC_EINVAL, "too many edges");
-    if (cfg->flags & ~(ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE | ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES | ISINGMC_CLASSICAL_CFG_SERIAL_MOVES))
+    if (cfg->flags & ~(ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE | ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES | ISINGMC_CLASSICAL_CFG_SERIAL_MOVES |
+                       ISINGMC_CLASSICAL_CFG_PER_REPLICA_J | ISINGMC_CLASSICAL_CFG_GLOBAL_CODES))
         return cmc_refuse(ISINGMC_EINVAL, "unknown flag");
     for (uint32_t e = 0; e < cfg->nedges; ++e) {
         const uint32_t a = cfg->edges[2 * e], b = cfg->edges[2 * e + 1];
         if (a >= cfg->nvars || b >= cfg->nvars) return cmc_refuse(ISINGMC_EINVAL, "edge endpoint out of range");
         if (a == b) return cmc_refuse(ISINGMC_EINVAL, "edge joins a variable to itself (self-loop)");
-        if (!std::isfinite(cfg->J[e])) return cmc_refuse(ISINGMC_EINVAL, "couplings must be finite");
-        if ((cfg->flags & ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE) && !(cfg->J[e] > 0.0))
-            return cmc_refuse(ISINGMC_EINVAL, "edge importance sampling needs every J > 0 (the reference searches their running sums)");
     }
+    const bool per_replica = (cfg->flags & ISINGMC_CLASSICAL_CFG_PER_REPLICA_J) != 0u;
+    for (uint32_t r = 0; r < (per_replica ? cfg->nreplicas : 1u); ++r) // J is [R][E] with per-replica couplings: every row is checked
+        for (uint32_t e = 0; e < cfg->nedges; ++e) {
+            const double j = cfg->J[(size_t)r * cfg->nedges + e];
+            auto where = [&]() { return per_replica ? " (couplings row of replica " + std::to_string(r) + ")" : std::string(); };
+            if (!std::isfinite(j)) return cmc_refuse(ISINGMC_EINVAL, "couplings must be finite" + where());
+            if ((cfg->flags & ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE) && !(j > 0.0))
+                return cmc_refuse(ISINGMC_EINVAL, "edge importance sampling needs every J > 0 (the reference searches their running sums)" + where());
+        }
     for (uint32_t v = 0; cfg->biases && v < cfg->nvars; ++v)
         if (!std::isfinite(cfg->biases[v])) return cmc_refuse(ISINGMC_EINVAL, "biases must be finite");
     return ISINGMC_OK;
@@ -43,17 +50,20 @@ int cmc_check_config(const isingmc_classical_config *cfg) {
 // binding_mat (graph.rs:69-78) and what goes with it, in the packed form of classical_rule.h
 void cmc_build_tables(const isingmc_classical_config *cfg, CmcHostTables &H) {
     const uint32_t N = cfg->nvars, E = cfg->nedges;
-    H.N = N; H.E = E; H.flags = 0;
-    // distinct couplings by bit pattern, in order of first appearance
+    const bool per_replica = (cfg->flags & ISINGMC_CLASSICAL_CFG_PER_REPLICA_J) != 0u;
+    const size_t rows = per_replica ? cfg->nreplicas : 1u; // rows of J
+    H.N = N; H.E = E; H.flags = per_replica ? CMC_T_PER_REPLICA : 0u;
+    // distinct couplings by bit pattern, in order of first appearance (over the rows of J one after the other); the codes matter only
+    // while there are at most 256 of them
     std::map<uint64_t, uint32_t> code_of;
-    std::vector<uint32_t> code(E);
+    std::vector<uint32_t> code(rows * E);
     std::vector<double> dict;
-    for (uint32_t e = 0; e < E; ++e) {
+    for (size_t i = 0; i < rows * E && dict.size() <= 256; ++i) {
         uint64_t bits;
-        std::memcpy(&bits, &cfg->J[e], 8);
+        std::memcpy(&bits, &cfg->J[i], 8);
         auto it = code_of.find(bits);
-        if (it == code_of.end()) { it = code_of.emplace(bits, (uint32_t)dict.size()).first; dict.push_back(cfg->J[e]); }
-        code[e] = it->second;
+        if (it == code_of.end()) { it = code_of.emplace(bits, (uint32_t)dict.size()).first; dict.push_back(cfg->J[i]); }
+        code[i] = it->second;
     }
     const bool compact = dict.size() <= 256;
     if (compact) H.flags |= CMC_T_COMPACT;
@@ -71,10 +81,27 @@ void cmc_build_tables(const isingmc_classical_config *cfg, CmcHostTables &H) {
     for (uint32_t v = 0; v < N; ++v) // ... then the stable sort by neighbour
         std::stable_sort(ents.begin() + H.row[v], ents.begin() + H.row[v + 1], [](const Ent &x, const Ent &y) { return x.nbr < y.nbr; });
     H.ent.resize(ents.size());
-    H.jv = compact ? dict : std::vector<double>(ents.size());
-    for (size_t k = 0; k < ents.size(); ++k) {
-        H.ent[k] = ents[k].nbr | (compact ? code[ents[k].edge] << 24 : 0u);
-        if (!compact) H.jv[k] = cfg->J[ents[k].edge];
+    H.jcode.clear(); H.jr.clear();
+    if (!per_replica) {
+        H.jv = compact ? dict : std::vector<double>(ents.size());
+        for (size_t k = 0; k < ents.size(); ++k) {
+            H.ent[k] = ents[k].nbr | (compact ? code[ents[k].edge] << 24 : 0u);
+            if (!compact) H.jv[k] = cfg->J[ents[k].edge];
+        }
+    } else { // the entries hold the neighbour alone; the couplings are a table by (replica, entry)
+        for (size_t k = 0; k < ents.size(); ++k) H.ent[k] = ents[k].nbr;
+        const size_t stride = 4 * (size_t)cmc_code_words(E);
+        if (compact) {
+            H.jv = dict;
+            H.jcode.assign(rows * stride, 0);
+            for (size_t r = 0; r < rows; ++r)
+                for (size_t k = 0; k < ents.size(); ++k) H.jcode[r * stride + k] = (uint8_t)code[r * E + ents[k].edge];
+        } else {
+            H.jv.clear();
+            H.jr.resize(rows * ents.size());
+            for (size_t r = 0; r < rows; ++r)
+                for (size_t k = 0; k < ents.size(); ++k) H.jr[r * ents.size() + k] = cfg->J[r * E + ents[k].edge];
+        }
     }
     if (N <= 65536u) {
         H.flags |= CMC_T_EDGE16;
@@ -86,14 +113,26 @@ void cmc_build_tables(const isingmc_classical_config *cfg, CmcHostTables &H) {
         H.flags |= CMC_T_BIAS;
         H.bias.assign(cfg->biases, cfg->biases + N);
     }
-    H.cum.clear(); H.totalw = 0.0;
-    if (cfg->flags & ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE) { // the fold of graph.rs:324-331
+    H.cum.clear(); H.totalw_r.clear(); H.totalw = 0.0;
+    if (cfg->flags & ISINGMC_CLASSICAL_CFG_EDGE_IMPORTANCE) { // the fold of graph.rs:324-331, row by row
         H.flags |= CMC_T_CUM;
-        H.cum.resize(E);
-        double accw = 0.0;
-        for (uint32_t e = 0; e < E; ++e) { accw = accw + cfg->J[e]; H.cum[e] = accw; }
-        H.totalw = accw;
+        H.cum.resize(rows * E);
+        for (size_t r = 0; r < rows; ++r) {
+            double accw = 0.0;
+            for (uint32_t e = 0; e < E; ++e) { accw = accw + cfg->J[r * E + e]; H.cum[r * E + e] = accw; }
+            if (per_replica) H.totalw_r.push_back(accw); else H.totalw = accw;
+        }
     }
+}
+
+uint32_t CmcHostTables::first_mixed_chain(uint32_t R, uint32_t T) const {
+    if (!(flags & CMC_T_PER_REPLICA)) return CMC_NONE;
+    // equal codes are equal bit patterns (the dictionary is keyed by them); the doubles are compared as bytes
+    const uint8_t *base = (flags & CMC_T_COMPACT) ? jcode.data() : reinterpret_cast<const uint8_t *>(jr.data());
+    const size_t stride = (flags & CMC_T_COMPACT) ? 4 * (size_t)cmc_code_words(E) : 16 * (size_t)E;
+    for (uint32_t r = 0; r < R; ++r)
+        if (r % T != 0u && std::memcmp(base + (size_t)r * stride, base + (size_t)(r - r % T) * stride, stride) != 0) return r / T;
+    return CMC_NONE;
 }
 
 // checks, tables and the launch plan: everything isingmc_classical_create decides before it touches a device
@@ -101,7 +140,8 @@ static int plan_config(const isingmc_classical_config *cfg, uint32_t lds_bytes, 
     if (const int rc = cmc_check_config(cfg)) return rc;
     cmc_build_tables(cfg, H);
     const size_t total_words = lds_bytes / 4;
-    C = cmc_plan(H.view(), total_words, (cfg->flags & ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES) != 0u);
+    C = cmc_plan(H.view(), total_words, ((cfg->flags & ISINGMC_CLASSICAL_CFG_GLOBAL_TABLES) ? (uint32_t)CMC_FORCE_GLOBAL : 0u) |
+                                            ((cfg->flags & ISINGMC_CLASSICAL_CFG_GLOBAL_CODES) ? (uint32_t)CMC_FORCE_GLOBAL_CODES : 0u));
     if (C.W == 0u) {
         char msg[200];
         std::snprintf(msg, sizeof msg, "model too large: the state bits and move stamps of one replica exceed LDS (at most %u variables in %u bytes)",
@@ -113,7 +153,9 @@ static int plan_config(const isingmc_classical_config *cfg, uint32_t lds_bytes, 
 
 // the eight slots of isingmc_classical_plan / isingmc_classical_launch_plan
 static void plan_slots(const CmcCarve &C, uint32_t table_flags, uint32_t out[8]) {
-    const uint32_t slots[8] = {C.W, C.in_lds, C.words, C.wave_words, C.has, (table_flags & CMC_T_COMPACT) ? 1u : 0u, (table_flags & CMC_T_EDGE16) ? 1u : 0u, 0u};
+    const uint32_t format = !(table_flags & CMC_T_PER_REPLICA) ? 0u : (table_flags & CMC_T_COMPACT) ? 1u : 2u;
+    const uint32_t slots[8] = {C.W, C.in_lds, C.words, C.wave_words + (C.o_jcode != CMC_NONE ? C.code_words : 0u), C.has, (table_flags & CMC_T_COMPACT) ? 1u : 0u,
+                               (table_flags & CMC_T_EDGE16) ? 1u : 0u, format};
     std::copy(slots, slots + 8, out);
 }
 
@@ -134,7 +176,10 @@ static int allocate_and_upload(isingmc_classical *g, const isingmc_classical_con
     if (const int rc = cmc_upload(g, &D.T.ent, H.ent)) return rc;
     if (const int rc = cmc_upload(g, &D.T.jv, H.jv)) return rc;
     if (const int rc = cmc_upload(g, &D.T.edges, H.edges)) return rc;
-    D.T.bias = nullptr; D.T.cum = nullptr;
+    D.T.bias = nullptr; D.T.cum = nullptr; D.T.jcode = nullptr; D.T.jr = nullptr; D.T.totalw_r = nullptr;
+    if (!H.jcode.empty()) if (const int rc = cmc_upload(g, &D.T.jcode, H.jcode)) return rc;
+    if (!H.jr.empty()) if (const int rc = cmc_upload(g, &D.T.jr, H.jr)) return rc;
+    if (!H.totalw_r.empty()) if (const int rc = cmc_upload(g, &D.T.totalw_r, H.totalw_r)) return rc;
     if (!H.bias.empty()) if (const int rc = cmc_upload(g, &D.T.bias, H.bias)) return rc;
     if (!H.cum.empty()) if (const int rc = cmc_upload(g, &D.T.cum, H.cum)) return rc;
     if (const int rc = cmc_alloc(g, &D.state, (size_t)D.R * D.nwords)) return rc;
@@ -345,13 +390,12 @@ int isingmc_classical_host_steps(const isingmc_classical_config *cfg, uint64_t t
     if (kinds >= CMC_KINDS_COUNT) return cmc_refuse(ISINGMC_EINVAL, "kinds must be one of ISINGMC_CLASSICAL_KINDS_*");
     CmcHostTables H;
     cmc_build_tables(cfg, H);
-    const CmcGraphMem g{H.view()};
     const uint32_t N = H.N;
     const CmcHostMoves m{cmc_default_moves(nspin, N / 2u), cmc_default_moves(nedge, H.E / 2u), cmc_default_moves(nworm, 1u), kinds};
     std::vector<uint8_t> mark(N, 0);
     for (uint32_t r = 0; r < cfg->nreplicas; ++r) {
         uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        cmc_host_replica_steps(g, cfg->seed, cfg->replica_offset + r, t, beta[r], m, states + (size_t)r * N, mark.data(), &epochs[r], ctr);
+        cmc_host_replica_steps(cmc_graph_mem(H.view(), r), cfg->seed, cfg->replica_offset + r, t, beta[r], m, states + (size_t)r * N, mark.data(), &epochs[r], ctr);
         for (int i = 0; counters && i < 8; ++i) counters[(size_t)r * 8 + i] += ctr[i];
     }
     return ISINGMC_OK;

@@ -9,7 +9,7 @@
 namespace sse {
 
 struct CmcDev {
-    CmcTables T;        // the graph tables in global memory (shared by the batch)
+    CmcTables T;        // the graph tables in global memory (shared by the batch; with CMC_T_PER_REPLICA the couplings are per replica)
     uint32_t R, nwords; // replicas; state words per replica
     uint32_t *state;    // [R][nwords] bit v of word v >> 5
     uint64_t *epoch;    // [R] time steps taken
@@ -28,47 +28,66 @@ struct CmcStepArgs {
 // couplings, biases, edge list, cumulative weights (the order in which they pay: a move reads its rows more often than anything
 // else); a table that does not fit, or any table with force_global, is read from global memory (offset CMC_NONE).  Tables of doubles
 // start on even words.
-enum { CMC_L_ROW = 1, CMC_L_ENT = 2, CMC_L_JV = 4, CMC_L_BIAS = 8, CMC_L_EDGES = 16, CMC_L_CUM = 32 };
+// Per-replica couplings (CMC_T_PER_REPLICA).  The code bytes are a per-wave item like the state: code_words = cmc_code_words(E) words
+// for each of the W waves (wave w's at o_jcode + w code_words), for all waves or for none, placed behind the row entries and before the
+// dictionary (a move reads one code per row entry).  The doubles of the other format and the per-replica cumulative weights are read
+// from global memory always (cmc_global_only): their bits are in `has` and never in `in_lds`.
+enum { CMC_L_ROW = 1, CMC_L_ENT = 2, CMC_L_JV = 4, CMC_L_BIAS = 8, CMC_L_EDGES = 16, CMC_L_CUM = 32, CMC_L_JREP = 64 };
 struct CmcCarve {
     uint32_t W, wave_words, o_stamp; // a wave's area: wave_words words at wave * wave_words, its stamps o_stamp words in
     uint32_t o_row, o_ent, o_jv, o_bias, o_edges, o_cum;
     uint32_t in_lds, has;            // CMC_L_* of the tables in LDS / of the tables the model has
     uint32_t words;                  // the dynamic LDS of the launch
+    uint32_t o_jcode, code_words;    // the waves' code bytes (CMC_NONE: in global memory, or no codes); words of one wave's codes
 };
 __host__ __device__ inline uint32_t cmc_wave_words(uint32_t N) { return (N + 31u) / 32u + (N + 3u) / 4u; }
 __host__ __device__ inline uint32_t cmc_edge_words(const CmcTables &T) { return (T.flags & CMC_T_EDGE16) ? T.E : 2u * T.E; }
-inline CmcCarve cmc_carve(const CmcTables &T, uint32_t W, size_t total_words, bool force_global) {
+// force: CMC_FORCE_GLOBAL every table is read from global memory, CMC_FORCE_GLOBAL_CODES the per-replica code bytes are (both for
+// tests and A-B timing)
+enum { CMC_FORCE_GLOBAL = 1, CMC_FORCE_GLOBAL_CODES = 2 };
+inline CmcCarve cmc_carve(const CmcTables &T, uint32_t W, size_t total_words, uint32_t force) {
+    const bool force_global = (force & CMC_FORCE_GLOBAL) != 0u;
     CmcCarve c{};
     c.W = W; c.wave_words = cmc_wave_words(T.N); c.o_stamp = (T.N + 31u) / 32u;
     size_t o = (size_t)W * c.wave_words;
-    auto place = [&](uint32_t bit, size_t words, bool dbl, bool present) {
+    auto place = [&](uint32_t bit, size_t words, bool dbl, bool present, bool global_only = false) {
         if (!present) return (uint32_t)CMC_NONE;
         c.has |= bit;
         const size_t at = dbl ? (o + 1) & ~(size_t)1 : o;
-        if (force_global || at + words > total_words) return (uint32_t)CMC_NONE;
+        if (force_global || global_only || at + words > total_words) return (uint32_t)CMC_NONE;
         c.in_lds |= bit; o = at + words;
         return (uint32_t)at;
     };
+    const bool per_replica = (T.flags & CMC_T_PER_REPLICA) != 0u, codes = per_replica && (T.flags & CMC_T_COMPACT) != 0u;
+    c.code_words = codes ? cmc_code_words(T.E) : 0u;
     c.o_row = place(CMC_L_ROW, (size_t)T.N + 1, false, true);
     c.o_ent = place(CMC_L_ENT, 2 * (size_t)T.E, false, true);
-    c.o_jv = place(CMC_L_JV, 2 * (size_t)T.njv, true, true);
+    c.o_jcode = place(CMC_L_JREP, (size_t)W * c.code_words, false, per_replica, !codes || (force & CMC_FORCE_GLOBAL_CODES) != 0u);
+    c.o_jv = place(CMC_L_JV, 2 * (size_t)T.njv, true, !per_replica || codes);
     c.o_bias = place(CMC_L_BIAS, 2 * (size_t)T.N, true, (T.flags & CMC_T_BIAS) != 0u);
     c.o_edges = place(CMC_L_EDGES, cmc_edge_words(T), false, true);
-    c.o_cum = place(CMC_L_CUM, 2 * (size_t)T.E, true, (T.flags & CMC_T_CUM) != 0u);
+    c.o_cum = place(CMC_L_CUM, 2 * (size_t)T.E, true, (T.flags & CMC_T_CUM) != 0u, per_replica);
     c.words = (uint32_t)o;
     return c;
 }
-// The launch of a model: the most waves per workgroup of 4, 2, 1 with every table in LDS; when no count does that, the most waves
-// whose own areas fit, with the tables that still fit.  W = 0: the areas of a single wave exceed LDS.
-inline CmcCarve cmc_plan(const CmcTables &T, size_t total_words, bool force_global) {
+// the tables of a model that no launch keeps in LDS
+inline uint32_t cmc_global_only(const CmcTables &T, uint32_t force) {
+    if (!(T.flags & CMC_T_PER_REPLICA)) return 0u;
+    const bool codes_in_lds = (T.flags & CMC_T_COMPACT) != 0u && !(force & CMC_FORCE_GLOBAL_CODES);
+    return (codes_in_lds ? 0u : (uint32_t)CMC_L_JREP) | ((T.flags & CMC_T_CUM) ? (uint32_t)CMC_L_CUM : 0u);
+}
+// The launch of a model: the most waves per workgroup of 4, 2, 1 with every table in LDS (every table that a launch can keep there:
+// cmc_global_only); when no count does that, the most waves whose own areas (state bits and stamps) fit, with the tables that still fit.
+// W = 0: the areas of a single wave exceed LDS.
+inline CmcCarve cmc_plan(const CmcTables &T, size_t total_words, uint32_t force) {
     const uint32_t counts[3] = {4, 2, 1};
-    if (!force_global)
+    if (!(force & CMC_FORCE_GLOBAL))
         for (uint32_t W : counts) {
-            const CmcCarve c = cmc_carve(T, W, total_words, false);
-            if (c.in_lds == c.has && c.words <= total_words) return c;
+            const CmcCarve c = cmc_carve(T, W, total_words, force);
+            if (c.in_lds == (c.has & ~cmc_global_only(T, force)) && c.words <= total_words) return c;
         }
     for (uint32_t W : counts)
-        if ((size_t)W * cmc_wave_words(T.N) <= total_words) return cmc_carve(T, W, total_words, force_global);
+        if ((size_t)W * cmc_wave_words(T.N) <= total_words) return cmc_carve(T, W, total_words, force);
     CmcCarve none{};
     return none;
 }

@@ -19,6 +19,16 @@ static int check_pt_args(uint32_t R, uint32_t replica_offset, uint32_t ntemps, c
     return ISINGMC_OK;
 }
 
+// The swap rule compares energies of one Hamiltonian: with per-replica couplings the T rows of every chain must be the same
+// realisation, bit for bit (chains may differ from each other)
+static int check_pt_couplings(const CmcHostTables &H, uint32_t R, uint32_t ntemps, std::string &why) {
+    const uint32_t c = H.first_mixed_chain(R, ntemps);
+    if (c == CMC_NONE) return ISINGMC_OK;
+    why = "tempering needs one set of couplings per chain: the coupling rows of chain " + std::to_string(c) + " (replicas " + std::to_string(c * ntemps) + " .. " +
+          std::to_string(c * ntemps + ntemps - 1u) + ") differ; tempering between different graphs is not built";
+    return ISINGMC_EINVAL;
+}
+
 static int need_attached(isingmc_classical *g, const char *who) {
     if (g->pt.attached) return ISINGMC_OK;
     g->err = std::string(who) + ": call isingmc_classical_pt_attach first";
@@ -50,6 +60,7 @@ extern "C" {
 int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const double *betas) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = check_pt_args(g->dev.R, g->dev.replica_offset, ntemps, betas, g->err)) return rc;
+    if (const int rc = check_pt_couplings(g->host, g->dev.R, ntemps, g->err)) return rc;
     CMC_TRY(g, hipSetDevice(g->device));
     CMC_TRY(g, hipStreamSynchronize(g->stream));
     const uint32_t R = g->dev.R;
@@ -171,7 +182,7 @@ int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t 
     if (!cmc_pt_is_permutation(temp_of, R, T, seen.data())) return cmc_refuse(ISINGMC_EINVAL, "temp_of must be a permutation of the temperatures within every chain");
     CmcHostTables H;
     cmc_build_tables(cfg, H);
-    const CmcGraphMem g{H.view()};
+    if (const int rc = check_pt_couplings(H, R, T, why)) return cmc_refuse(rc, why);
     const uint32_t N = H.N;
     const CmcHostMoves m{cmc_default_moves(nspin, N / 2u), cmc_default_moves(nedge, H.E / 2u), cmc_default_moves(nworm, 1u), kinds};
     std::vector<uint8_t> mark(N, 0);
@@ -181,6 +192,7 @@ int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t 
     for (uint64_t round = 0; round < rounds; ++round, ++*pt_step) {
         for (uint32_t r = 0; r < R; ++r) {
             uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            const CmcGraphMem g = cmc_graph_mem(H.view(), r);
             cmc_host_replica_steps(g, cfg->seed, cfg->replica_offset + r, steps, betas[temp_of[r]], m, states + (size_t)r * N, mark.data(), &epochs[r], ctr);
             for (int i = 0; counters && i < 8; ++i) counters[(size_t)r * 8 + i] += ctr[i];
             const CmcBytes s{states + (size_t)r * N};

@@ -14,19 +14,27 @@
 #pragma once
 #include <float.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/sse_format.h" // SSE_HD, SSE_TAG_CLASSICAL, SSE_TAG_CLASSICAL_WORM
 
 // ---- the graph tables ----
 // binding_mat (graph.rs:69-78) as a CSR: variable v's row is entries row[v] .. row[v + 1], (neighbour, J) sorted by neighbour with a
 // stable sort in edge order; multi-edges stay separate entries.  An entry is  neighbour | code << 24 : with CMC_T_COMPACT the model has
-// at most 256 distinct couplings and jv[code] is the entry's J; otherwise code = 0 and jv[k] is the J of entry k.
+// at most 256 distinct couplings and jv[code] is the entry's J; otherwise code = 0 and jv[k] is the J of entry k.  (This is the batch
+// that shares its couplings; CMC_T_PER_REPLICA below.)
 #define CMC_MAX_VARS (1u << 24)
 #define CMC_NBR_MASK 0xFFFFFFu
 #define CMC_T_COMPACT 1u // jv is a dictionary of the distinct couplings
 #define CMC_T_EDGE16 2u  // N <= 65536: an edge is one word a | b << 16 (otherwise two words a, b)
 #define CMC_T_BIAS 4u    // some bias is non-zero (otherwise bias is null: all zero)
 #define CMC_T_CUM 8u     // edge importance sampling: cum[e] = J_0 + .. + J_e, totalw = cum[E - 1] (graph.rs:320-336)
+// Per-replica couplings (disorder realisations on one topology): the code bits of every entry are 0 and the couplings are a table of
+// their own, indexed by (local replica r, row entry k); both entries of edge e carry J[r][e].  With CMC_T_COMPACT the batch has at most
+// 256 distinct couplings over all R E values: jv is their dictionary (order of first appearance, r-major) and jcode holds one byte per
+// entry, in rows of cmc_code_words(E) words (the bytes behind 2E are 0).  Otherwise jr holds one double per entry and jv is empty.
+// With CMC_T_CUM the running sums are per replica as well: cum [R][E], totalw_r [R].
+#define CMC_T_PER_REPLICA 16u
 #define CMC_NONE 0xFFFFFFFFu
 struct CmcTables {
     uint32_t N, E, flags, njv; // njv: entries of jv
@@ -35,9 +43,13 @@ struct CmcTables {
     const double *jv;          // [njv]
     const double *bias;        // [N] or null
     const uint32_t *edges;     // [E] or [2E]
-    const double *cum;         // [E] or null
+    const double *cum;         // [E] ([R][E] per replica) or null
     double totalw;
+    const uint8_t *jcode;      // [R][4 cmc_code_words(E)] or null
+    const double *jr;          // [R][2E] or null
+    const double *totalw_r;    // [R] or null
 };
+SSE_HD inline uint32_t cmc_code_words(uint32_t E) { return (2u * E + 3u) / 4u; } // the words of one replica's code bytes
 // what a time step draws its kind from (isingmc_classical_timesteps `kinds`)
 #define CMC_KINDS_ALL 0u   // spin, edge or worm steps, as do_time_step draws them (:364-365)
 #define CMC_KINDS_BASIC 1u // only_basic_moves: spin or edge steps
@@ -49,23 +61,37 @@ struct CmcTables {
 // counters [8]: attempted and accepted moves per kind, worm failures, worm path entries
 enum { CMC_C_SPIN = 0, CMC_C_SPIN_ACC = 1, CMC_C_EDGE = 2, CMC_C_EDGE_ACC = 3, CMC_C_WORM = 4, CMC_C_WORM_ACC = 5, CMC_C_WORM_FAIL = 6, CMC_C_WORM_PATH = 7 };
 
-// the graph accessor over tables in plain memory
+// the graph accessor over tables in plain memory: the view of one replica (cmc_graph_mem).  J(k), cum(e) and totalw() are the only
+// places that know the coupling format
 struct CmcGraphMem {
     CmcTables T;
+    const uint8_t *jcode; // the replica's codes / doubles (per-replica couplings), its running sums and their total
+    const double *jr, *cum_r;
+    double totalw_r;
     SSE_HD uint32_t N() const { return T.N; }
     SSE_HD uint32_t E() const { return T.E; }
     SSE_HD uint32_t row(uint32_t v) const { return T.row[v]; }
     SSE_HD uint32_t nbr(uint32_t k) const { return T.ent[k] & CMC_NBR_MASK; }
-    SSE_HD double J(uint32_t k) const { return T.jv[(T.flags & CMC_T_COMPACT) ? T.ent[k] >> 24 : k]; }
+    SSE_HD double J(uint32_t k) const {
+        if (T.flags & CMC_T_PER_REPLICA) return (T.flags & CMC_T_COMPACT) ? T.jv[jcode[k]] : jr[k];
+        return T.jv[(T.flags & CMC_T_COMPACT) ? T.ent[k] >> 24 : k];
+    }
     SSE_HD double bias(uint32_t v) const { return (T.flags & CMC_T_BIAS) ? T.bias[v] : 0.0; }
     SSE_HD void edge(uint32_t e, uint32_t &a, uint32_t &b) const {
         if (T.flags & CMC_T_EDGE16) { a = T.edges[e] & 0xFFFFu; b = T.edges[e] >> 16; }
         else { a = T.edges[2 * e]; b = T.edges[2 * e + 1]; }
     }
     SSE_HD bool importance() const { return (T.flags & CMC_T_CUM) != 0u; }
-    SSE_HD double cum(uint32_t e) const { return T.cum[e]; }
-    SSE_HD double totalw() const { return T.totalw; }
+    SSE_HD double cum(uint32_t e) const { return cum_r[e]; }
+    SSE_HD double totalw() const { return totalw_r; }
 };
+// the view of local replica r (with shared couplings every r gives the same view)
+SSE_HD inline CmcGraphMem cmc_graph_mem(const CmcTables &T, uint32_t r) {
+    if (!(T.flags & CMC_T_PER_REPLICA)) return CmcGraphMem{T, nullptr, nullptr, T.cum, T.totalw};
+    const bool cum = (T.flags & CMC_T_CUM) != 0u;
+    return CmcGraphMem{T, T.jcode ? T.jcode + (size_t)r * 4u * cmc_code_words(T.E) : nullptr, T.jr ? T.jr + (size_t)r * 2u * T.E : nullptr,
+                       cum ? T.cum + (size_t)r * T.E : nullptr, cum ? T.totalw_r[r] : 0.0};
+}
 
 // ---- the random stream ----
 SSE_HD inline uint32_t cmc_range(uint32_t word, uint32_t n) { return (uint32_t)(((uint64_t)word * (uint64_t)n) >> 32); } // __umulhi

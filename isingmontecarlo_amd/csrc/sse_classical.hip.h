@@ -13,18 +13,32 @@
 // state that the sequential rule shows them (by induction over the lanes: the accepted moves before them touch nothing they read), so
 // the result is the sequential one, move for move.
 // Worm steps are the cold path: lane 0 walks (cmc_worm), with the stamp bytes as the marks of the flipped variables.
+//
+// Per-replica couplings (CMC_T_PER_REPLICA) are a variant of their own at compile time, classical_steps_per_replica_kernel: the
+// kernel of a batch that shares its couplings carries none of it.  There a wave stages its own replica's code bytes into its LDS area
+// (word copies: a row of codes is whole words) when the plan puts them there, and otherwise reads its codes, or its doubles, from
+// global memory; the tables are indexed by the local replica, the Philox stream by the global one.  Everything else is shared.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "classical_launch.h"
 #include "sse_core.hip.h" // philox4x32_10, lds_raw, sse_ballot
 
 namespace sse {
 
-// the graph tables, each in LDS or in global memory
-struct CmcGraphDev {
+// the graph tables, each in LDS or in global memory.  PR: the view of one replica of a batch with per-replica couplings
+struct CmcNoReplica {};
+struct CmcReplicaDev {
+    uint32_t o_jcode;     // the wave's code bytes in LDS (word offset), or CMC_NONE
+    const uint8_t *jcode; // the replica's rows in global memory (cmc_graph_mem)
+    const double *jr, *cum_r;
+    double totalw_r;
+};
+template <bool PR> struct CmcGraphDevT {
     const CmcTables &T;
     const CmcCarve &C;
+    typename std::conditional<PR, CmcReplicaDev, CmcNoReplica>::type P;
     __device__ __forceinline__ uint32_t N() const { return T.N; }
     __device__ __forceinline__ uint32_t E() const { return T.E; }
     __device__ __forceinline__ uint32_t row(uint32_t v) const { return C.o_row != CMC_NONE ? LDSW(C.o_row, v) : T.row[v]; }
@@ -33,7 +47,12 @@ struct CmcGraphDev {
         return off != CMC_NONE ? *reinterpret_cast<const double *>(&lds_raw[off + 2u * i]) : g[i];
     }
     __device__ __forceinline__ uint32_t nbr(uint32_t k) const { return ent(k) & CMC_NBR_MASK; }
-    __device__ __forceinline__ double J(uint32_t k) const { return dbl(C.o_jv, T.jv, (T.flags & CMC_T_COMPACT) ? ent(k) >> 24 : k); }
+    __device__ __forceinline__ double J(uint32_t k) const {
+        if constexpr (PR) {
+            if (!(T.flags & CMC_T_COMPACT)) return P.jr[k];
+            return dbl(C.o_jv, T.jv, P.o_jcode != CMC_NONE ? (uint32_t)LDSB(P.o_jcode, k) : (uint32_t)P.jcode[k]);
+        } else return dbl(C.o_jv, T.jv, (T.flags & CMC_T_COMPACT) ? ent(k) >> 24 : k);
+    }
     __device__ __forceinline__ double bias(uint32_t v) const { return (T.flags & CMC_T_BIAS) ? dbl(C.o_bias, T.bias, v) : 0.0; }
     __device__ __forceinline__ uint32_t edge_word(uint32_t i) const { return C.o_edges != CMC_NONE ? LDSW(C.o_edges, i) : T.edges[i]; }
     __device__ __forceinline__ void edge(uint32_t e, uint32_t &a, uint32_t &b) const {
@@ -41,9 +60,14 @@ struct CmcGraphDev {
         else { a = edge_word(2u * e); b = edge_word(2u * e + 1u); }
     }
     __device__ __forceinline__ bool importance() const { return (T.flags & CMC_T_CUM) != 0u; }
-    __device__ __forceinline__ double cum(uint32_t e) const { return dbl(C.o_cum, T.cum, e); }
-    __device__ __forceinline__ double totalw() const { return T.totalw; }
+    __device__ __forceinline__ double cum(uint32_t e) const {
+        if constexpr (PR) return P.cum_r[e]; else return dbl(C.o_cum, T.cum, e);
+    }
+    __device__ __forceinline__ double totalw() const {
+        if constexpr (PR) return P.totalw_r; else return T.totalw;
+    }
 };
+using CmcGraphDev = CmcGraphDevT<false>;
 // a wave's state bits and stamp bytes.  flip() is for one lane at a time (the worm): it toggles the variable's mark too
 struct CmcStateDev {
     uint32_t o_state, o_stamp;
@@ -61,7 +85,7 @@ struct CmcDrawDev {
 
 // is a stamp of an earlier lane on v?  (stamp 0 = none: 0 - 1 wraps to the largest value)
 __device__ __forceinline__ bool cmc_stamped_before(const CmcStateDev &s, uint32_t v, uint32_t lane) { return (uint32_t)(s.stamp(v) - 1u) < lane; }
-__device__ __forceinline__ bool cmc_row_stamped_before(const CmcGraphDev &g, const CmcStateDev &s, uint32_t v, uint32_t lane) {
+template <class G> __device__ __forceinline__ bool cmc_row_stamped_before(const G &g, const CmcStateDev &s, uint32_t v, uint32_t lane) {
     bool hit = cmc_stamped_before(s, v, lane);
     for (uint32_t k = g.row(v), end = g.row(v + 1u); k < end; ++k) hit |= cmc_stamped_before(s, g.nbr(k), lane);
     return hit;
@@ -74,7 +98,8 @@ __device__ __forceinline__ bool cmc_stamp_lower(const CmcStateDev &s, uint32_t v
 }
 
 // nmoves spin (edge_step = false) or edge moves of one step; returns the number accepted
-__device__ __forceinline__ uint32_t cmc_moves(const CmcGraphDev &g, CmcStateDev &s, const CmcDrawDev &draw, double beta, uint32_t nmoves, bool edge_step,
+template <class G>
+__device__ __forceinline__ uint32_t cmc_moves(const G &g, CmcStateDev &s, const CmcDrawDev &draw, double beta, uint32_t nmoves, bool edge_step,
                                               bool serial, int lane) {
     uint32_t accepted = 0;
     for (uint32_t base = 0; base < nmoves; base += 64u) {
@@ -125,7 +150,7 @@ __device__ __forceinline__ uint32_t cmc_moves(const CmcGraphDev &g, CmcStateDev 
     return accepted;
 }
 
-__global__ __launch_bounds__(256) void classical_steps_kernel(CmcDev D, CmcCarve C, CmcStepArgs A) {
+template <bool PR> __device__ __forceinline__ void cmc_steps(const CmcDev &D, const CmcCarve &C, const CmcStepArgs &A) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t r = blockIdx.x * C.W + (uint32_t)wave;
     // the graph tables that live in LDS, staged by the whole workgroup (waves without a replica help and leave behind the barrier)
@@ -145,9 +170,19 @@ __global__ __launch_bounds__(256) void classical_steps_kernel(CmcDev D, CmcCarve
         for (uint32_t i = lane; i < D.nwords; i += 64u) LDSW(s.o_state, i) = D.state[(size_t)r * D.nwords + i];
         for (uint32_t i = lane; i < C.wave_words - C.o_stamp; i += 64u) LDSW(s.o_stamp, i) = 0u;
     }
+    CmcGraphDevT<PR> g{T, C, {}};
+    if constexpr (PR) { // the tables of the local replica r; its code bytes into the wave's own words (a row is code_words whole words)
+        if (live) {
+            const CmcGraphMem m = cmc_graph_mem(T, r);
+            g.P = CmcReplicaDev{C.o_jcode != CMC_NONE ? C.o_jcode + (uint32_t)wave * C.code_words : (uint32_t)CMC_NONE, m.jcode, m.jr, m.cum_r, m.totalw_r};
+            if (g.P.o_jcode != CMC_NONE) {
+                const uint32_t *codes = reinterpret_cast<const uint32_t *>(m.jcode);
+                for (uint32_t i = lane; i < C.code_words; i += 64u) LDSW(g.P.o_jcode, i) = codes[i];
+            }
+        }
+    }
     __syncthreads();
     if (!live) return;
-    const CmcGraphDev g{T, C};
     const double beta = A.beta[r];
     const uint32_t nspin = cmc_default_moves(A.nspin, T.N / 2u), nedge = cmc_default_moves(A.nedge, T.E / 2u), nworm = cmc_default_moves(A.nworm, 1u);
     uint64_t epoch = D.epoch[r];
@@ -179,10 +214,13 @@ __global__ __launch_bounds__(256) void classical_steps_kernel(CmcDev D, CmcCarve
     }
 }
 
+__global__ __launch_bounds__(256) void classical_steps_kernel(CmcDev D, CmcCarve C, CmcStepArgs A) { cmc_steps<false>(D, C, A); }
+__global__ __launch_bounds__(256) void classical_steps_per_replica_kernel(CmcDev D, CmcCarve C, CmcStepArgs A) { cmc_steps<true>(D, C, A); }
+
 // get_energy (graph.rs:430-447), one wave per replica: the lanes share the variables and their sums are added across the wave
 __global__ __launch_bounds__(64) void classical_energies_kernel(CmcDev D, double *out) {
     const uint32_t r = blockIdx.x, lane = threadIdx.x;
-    const CmcGraphMem g{D.T};
+    const CmcGraphMem g = cmc_graph_mem(D.T, r);
     struct Bits {
         const uint32_t *w;
         __device__ bool get(uint32_t v) const { return ((w[v >> 5] >> (v & 31u)) & 1u) != 0u; }

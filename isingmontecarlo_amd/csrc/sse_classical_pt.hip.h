@@ -30,9 +30,9 @@ __global__ __launch_bounds__(64 * CMC_PT_MAX_WAVES) void classical_tempering_ker
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     if (threadIdx.x == 0u) s_err = 0u;
     __syncthreads();
-    const CmcGraphMem g{D.T};
     for (uint32_t i = wave; i < T; i += nwaves) { // the wave's slots
         const uint32_t r = base + i;
+        const CmcGraphMem g = cmc_graph_mem(D.T, r); // the slot's own couplings (equal along a chain when they are per replica)
         const CmcBitsMem s{D.state + (size_t)r * D.nwords};
         double e = cmc_pt_lane_energy(g, s, lane);
         for (int o = 32; o > 0; o >>= 1) e += __shfl_down(e, o, 64);

@@ -5,7 +5,8 @@
 namespace sse {
 hipError_t launch_classical_steps(hipStream_t stream, const CmcDev &D, const CmcCarve &C, const CmcStepArgs &A) {
     if (C.W == 0u || C.W > 4u || D.R == 0u) return hipErrorInvalidValue;
-    return launch_lds(classical_steps_kernel, dim3((D.R + C.W - 1u) / C.W), dim3(C.W * 64u), lds_bytes_of(C.words), stream, D, C, A);
+    // per-replica couplings run the variant compiled for them: the shared-coupling kernel is the one it always was
+    return launch_lds((D.T.flags & CMC_T_PER_REPLICA) ? classical_steps_per_replica_kernel : classical_steps_kernel, dim3((D.R + C.W - 1u) / C.W), dim3(C.W * 64u), lds_bytes_of(C.words), stream, D, C, A);
 }
 hipError_t launch_classical_energies(hipStream_t stream, const CmcDev &D, double *out) {
     hipLaunchKernelGGL(classical_energies_kernel, dim3(D.R), dim3(64), 0, stream, D, out);

@@ -8,6 +8,12 @@ kernel, counted by replaying a replica's rounds from its moves.  The two device 
 (isingmc_classical_last_kernel_ms), after a warm-up; their final states must be equal.  Writes profiles/classical_bench.json.
 
     python tools/bench_classical.py [--steps 200] [--repeats 5] [--out profiles/classical_bench.json]
+
+--per-replica times the same workload with R = 1024 independent +-J sign realisations of the lattice's bonds (GraphState(couplings=...))
+instead: the planned launch (2 waves per workgroup, the coupling codes in LDS), the launch with the codes kept in global memory
+(CFG_GLOBAL_CODES: 4 waves per workgroup) and the shared-coupling batch of the same session, alternately; every replica of the first
+two must end in the same state, and replica 0 in the state of the host's sequential rule.  Writes
+profiles/classical_per_replica_bench.json.
 """
 import argparse
 import json
@@ -54,14 +60,48 @@ def committed_share(edges, nvars, before, after_fn, nmoves, words):
     return committed / active, rounds / batches, state
 
 
+def per_replica(a, im, cl, edges, biases, L, R, beta, seed):
+    """The 64 x 64 workload on R independent +-J realisations: kernel ms per call of the planned launch, of the launch with the codes in
+    global memory and of the shared-coupling batch, timed alternately."""
+    N = L * L
+    cj = np.ascontiguousarray(np.random.default_rng(seed).choice([-1.0, 1.0], (R, len(edges))))
+    graphs = {"shared": im.GraphState(edges, biases, seed, nreplicas=R),
+              "per_replica": im.GraphState(edges, biases, seed, nreplicas=R, couplings=cj),
+              "per_replica_global_codes": im.GraphState(edges, biases, seed, nreplicas=R, couplings=cj, cfg_flags=cl.CFG_GLOBAL_CODES)}
+    plans = {k: g.launch_plan() for k, g in graphs.items()}
+    assert plans["per_replica"]["waves"] == 2 and plans["per_replica"]["in_lds"] & 64, plans
+    assert plans["per_replica_global_codes"]["waves"] == 4 and not plans["per_replica_global_codes"]["in_lds"] & 64, plans
+    start = graphs["per_replica"].state_ref()[:1]
+    for g in graphs.values():
+        g.timesteps(a.warmup, beta, nspinupdates=N, kinds=cl.KINDS_SPIN)
+    ms = {k: [] for k in graphs}
+    for _ in range(a.repeats):
+        for k, g in graphs.items():  # alternating
+            g.timesteps(a.steps, beta, nspinupdates=N, kinds=cl.KINDS_SPIN)
+            ms[k].append(g.last_kernel_ms())
+    assert np.array_equal(graphs["per_replica"].state_ref(), graphs["per_replica_global_codes"].state_ref()), "the two launches must agree"
+    host = cl.host_steps(edges, biases, seed, start, 0, a.warmup + a.host_steps, beta, nspinupdates=N, kinds=cl.KINDS_SPIN, couplings=cj[:1])
+    check = im.GraphState(edges, biases, seed, nreplicas=1, couplings=cj[:1])
+    check.timesteps(a.warmup + a.host_steps, beta, nspinupdates=N, kinds=cl.KINDS_SPIN)
+    assert np.array_equal(check.state_ref(), host[0]), "replica 0 must follow the sequential rule"
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    return {"lattice": f"{L}x{L} periodic, independent +-J signs per replica", "replicas": R, "beta_abs_J": beta, "nspin": N, "steps_per_call": a.steps,
+            "repeats": a.repeats, "kernel_ms": {k: [float(x) for x in v] for k, v in ms.items()}, "kernel_ms_median": med,
+            "kernel_ms_spread": {k: [float(min(v)), float(max(v))] for k, v in ms.items()},
+            "over_shared": {k: med[k] / med["shared"] for k in ("per_replica", "per_replica_global_codes")}, "plans": plans}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--host-steps", type=int, default=4)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "classical_bench.json"))
+    ap.add_argument("--per-replica", action="store_true", help="time per-replica +-J couplings against the shared-coupling batch")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "classical_per_replica_bench.json" if a.per_replica else "classical_bench.json")
     import torch
     torch.cuda.is_available()
     import isingmontecarlo_amd as im
@@ -72,6 +112,14 @@ def main():
     L, R, beta, seed = 64, 1024, 0.44, 2024
     N = L * L
     edges, biases = lat.two_d_periodic(L), [0.0] * N
+    if a.per_replica:
+        out = per_replica(a, im, cl, edges, biases, L, R, beta, seed)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
     graphs = {"batched": im.GraphState(edges, biases, seed, nreplicas=R), "serial": im.GraphState(edges, biases, seed, nreplicas=R, cfg_flags=cl.CFG_SERIAL_MOVES)}
     for g in graphs.values():
         g.timesteps(a.warmup, beta, nspinupdates=N, kinds=cl.KINDS_SPIN)

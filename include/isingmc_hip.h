@@ -539,6 +539,36 @@ int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t 
                                   uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
                                   uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out);
 
+/* ---- overlaps between copies of a realisation under tempering; the definitions are stated once in csrc/classical_overlap_rule.h ----
+ * With ncopies = K >= 2 consecutive chains form G = C / K groups of K independent copies of one realisation; the pairs of a group are
+ * (a, b), 0 <= a < b < K, a-major, P = K (K - 1) / 2.  A measured round compares, after its time steps and before its swaps, the two
+ * states that hold temperature t in the chains g K + a and g K + b: nq variables differ (spin overlap Q = N - 2 nq) and nl entries of
+ * the edge list have one endpoint that differs and one that does not (link overlap QL = E - 2 nl; multi-edges count apiece, the
+ * value of J does not matter).  The histograms hq [G][P][T][N + 1] (by nq) and hl [G][P][T][E + 1] (by nl), uint64, gain one count
+ * per measured round and accumulate over calls until reset.
+ * ISINGMC_EINVAL: ncopies == 1; C not a multiple of K; replica_offset / T not a multiple of K (a batch splits over handles at whole
+ * groups); per-replica couplings whose rows differ within a group (compared as bits: +0 and -0 differ); tempering not attached; the
+ * other overlap calls before overlap_attach. */
+/* Needs isingmc_classical_pt_attach.  Allocates and zeroes both histograms; ncopies == 0 detaches and frees them.
+ * isingmc_classical_pt_attach on a handle with overlaps detaches them: the shape of the batch changed. */
+int isingmc_classical_overlap_attach(isingmc_classical *g, uint32_t ncopies);
+/* The loop of isingmc_classical_pt_run with the overlap launch between the steps launch and the tempering launch of every round, one
+ * synchronisation at the end.  q_out and ql_out: int32 [rounds][G][P][T], Q and QL; each of the four series may be NULL.  The
+ * histograms always accumulate.  (isingmc_classical_pt_run on a handle with overlaps attached measures nothing and leaves the
+ * histograms alone: that is how to thermalise.) */
+int isingmc_classical_pt_run_overlaps(isingmc_classical *g, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
+                                      double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out);
+/* read (either may be NULL), restore from a checkpoint (both non-NULL), zero */
+int isingmc_classical_overlap_histograms(isingmc_classical *g, uint64_t *hq, uint64_t *hl);
+int isingmc_classical_overlap_set_histograms(isingmc_classical *g, const uint64_t *hq, const uint64_t *hl);
+int isingmc_classical_overlap_reset(isingmc_classical *g);
+/* Host-only, a device-free test entry: isingmc_classical_host_pt_run with the measurement, by the sequential rule on the CPU and
+ * with overlap_attach's argument checks.  q_out and ql_out as above; hq and hl are added to in place; all four may be NULL. */
+int isingmc_classical_host_pt_run_overlaps(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint32_t ncopies, uint64_t rounds,
+                                           uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs,
+                                           uint32_t *temp_of, uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts,
+                                           double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl);
+
 #ifdef __cplusplus
 }
 #endif

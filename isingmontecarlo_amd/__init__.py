@@ -191,6 +191,14 @@ SYMBOLS = {
     "isingmc_classical_pt_set_swap_counts": (C.c_int, [_vp, _P(_u64), _P(_u64)]),
     "isingmc_classical_host_pt_run": (C.c_int, [_P(_ClassicalConfig), _u32, _P(_f64), _u64, _u64, _u32, _u32, _u32, _u32, _P(C.c_uint8), _P(_u64),
                                                 _P(_u32), _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_f64), _P(C.c_int32)]),
+    "isingmc_classical_overlap_attach": (C.c_int, [_vp, _u32]),
+    "isingmc_classical_pt_run_overlaps": (C.c_int, [_vp, _u64, _u64, _u32, _u32, _u32, _u32, _P(_f64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    "isingmc_classical_overlap_histograms": (C.c_int, [_vp, _P(_u64), _P(_u64)]),
+    "isingmc_classical_overlap_set_histograms": (C.c_int, [_vp, _P(_u64), _P(_u64)]),
+    "isingmc_classical_overlap_reset": (C.c_int, [_vp]),
+    "isingmc_classical_host_pt_run_overlaps": (C.c_int, [_P(_ClassicalConfig), _u32, _P(_f64), _u32, _u64, _u64, _u32, _u32, _u32, _u32, _P(C.c_uint8),
+                                                         _P(_u64), _P(_u32), _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_f64), _P(C.c_int32),
+                                                         _P(C.c_int32), _P(C.c_int32), _P(_u64), _P(_u64)]),
 }
 
 _LIB = None

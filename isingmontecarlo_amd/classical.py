@@ -1,7 +1,7 @@
 """Classical Ising Monte Carlo on the device: `GraphState` (qmc::classical::GraphState, src/classical/graph.rs) for a batch of R
 replicas of one graph (with `couplings`: of R disorder realisations on one graph), over the isingmc_classical_* entry points of include/isingmc_hip.h.  All moves run in gfx950 kernels
-(csrc/sse_classical.hip.h), and so does replica exchange between the temperatures of a chain (csrc/sse_classical_pt.hip.h); there is
-no CPU fallback.  `host_steps`, `host_tempering_run` and `plan` are the device-free test entries of the C ABI."""
+(csrc/sse_classical.hip.h), and so do replica exchange between the temperatures of a chain (csrc/sse_classical_pt.hip.h) and the overlaps between copies of a
+realisation (csrc/sse_classical_overlap.hip.h); there is no CPU fallback.  `host_steps`, `host_tempering_run` and `plan` are the device-free test entries of the C ABI."""
 import ctypes as C
 
 import numpy as np
@@ -91,11 +91,15 @@ def host_steps(edges, biases, seed, states, epochs, t, beta, nspinupdates=None, 
 
 
 def host_tempering_run(edges, biases, seed, states, epochs, betas, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None,
-                       only_basic_moves=None, kinds=None, temp_of=None, pt_step=0, replica_offset=0, flags=0, record=True, couplings=None):
+                       only_basic_moves=None, kinds=None, temp_of=None, pt_step=0, replica_offset=0, flags=0, record=True, couplings=None, ncopies=None,
+                       histograms=None):
     """isingmc_classical_host_pt_run: `rounds` rounds of (`steps` time steps, one tempering step) by the sequential rule on the CPU, for
     R = len(states) slots as chains of T = len(betas) temperatures.  Returns a dict: states [R][N], epochs [R], temp_of [R], pt_step,
     counters [R][8], attempts and accepts [C][T - 1], and with `record` energy and magnetization [rounds][C][T].  `couplings` [R][E]:
-    the T rows of every chain must be equal (C realisations x T temperatures)."""
+    the T rows of every chain must be equal (C realisations x T temperatures).
+    With `ncopies` = K it is isingmc_classical_host_pt_run_overlaps: consecutive chains are G = C / K groups of K copies with
+    P = K (K - 1) / 2 pairs, and the dict gains overlap_hist uint64 [G][P][T][N + 1] and link_hist [G][P][T][E + 1] (`histograms`:
+    the pair (hq, hl) they continue from) and, with `record`, overlap and link_overlap int32 [rounds][G][P][T]."""
     lib = load_library()
     ed, js, hs = _model(edges, biases)
     st = np.ascontiguousarray(np.array(states, dtype=np.uint8).reshape(-1, len(hs)))
@@ -113,17 +117,41 @@ def host_tempering_run(edges, biases, seed, states, epochs, betas, rounds, steps
     att, acc = (np.zeros((chains, max(ntemps, 1) - 1), dtype=np.uint64) for _ in range(2))
     energy = np.zeros((int(rounds), chains, ntemps), dtype=np.float64) if record else None
     mag = np.zeros((int(rounds), chains, ntemps), dtype=np.int32) if record else None
-    rc = lib.isingmc_classical_host_pt_run(C.byref(_config(ed, js, hs, seed, nrep, replica_offset, flags=flags)), ntemps,
-                                           None if ladder is None else _ptr(ladder, C.c_double), int(rounds), int(steps), _count(nspinupdates),
-                                           _count(nedgeupdates), _count(nwormupdates), _kinds(only_basic_moves, kinds), _ptr(st, C.c_uint8),
-                                           _ptr(ep, C.c_uint64), _ptr(tof, C.c_uint32), C.byref(step), _ptr(ctr, C.c_uint64), _ptr(att, C.c_uint64),
-                                           _ptr(acc, C.c_uint64), _ptr(energy, C.c_double) if record else None, _ptr(mag, C.c_int32) if record else None)
+    cfg = _config(ed, js, hs, seed, nrep, replica_offset, flags=flags)
+    run = (int(rounds), int(steps), _count(nspinupdates), _count(nedgeupdates), _count(nwormupdates), _kinds(only_basic_moves, kinds), _ptr(st, C.c_uint8),
+           _ptr(ep, C.c_uint64), _ptr(tof, C.c_uint32), C.byref(step), _ptr(ctr, C.c_uint64), _ptr(att, C.c_uint64), _ptr(acc, C.c_uint64),
+           _ptr(energy, C.c_double) if record else None, _ptr(mag, C.c_int32) if record else None)
+    betas_ptr = None if ladder is None else _ptr(ladder, C.c_double)
+    if ncopies is None:
+        rc = lib.isingmc_classical_host_pt_run(C.byref(cfg), ntemps, betas_ptr, *run)
+    else:
+        k = int(ncopies)
+        groups, pairs = (chains // k, k * (k - 1) // 2) if k >= 2 and chains % k == 0 else (0, 0)  # (a shape the library refuses: empty outputs)
+        shape = (groups, pairs, ntemps)
+        q, ql = (np.zeros((int(rounds),) + shape, dtype=np.int32) if record else None for _ in range(2))
+        hq, hl = np.zeros(shape + (len(hs) + 1,), dtype=np.uint64), np.zeros(shape + (len(ed) + 1,), dtype=np.uint64)
+        if histograms is not None:
+            hq, hl = _histograms(histograms, hq.shape, hl.shape)
+        rc = lib.isingmc_classical_host_pt_run_overlaps(C.byref(cfg), ntemps, betas_ptr, k, *run, _ptr(q, C.c_int32) if record else None,
+                                                        _ptr(ql, C.c_int32) if record else None, _ptr(hq, C.c_uint64), _ptr(hl, C.c_uint64))
     if rc:
         raise IsingMcError(rc, lib.isingmc_classical_last_error(None).decode())
     out = dict(states=st, epochs=ep, temp_of=tof, pt_step=int(step.value), counters=ctr, attempts=att, accepts=acc)
     if record:
         out.update(energy=energy, magnetization=mag)
+    if ncopies is not None:
+        out.update(overlap_hist=hq, link_hist=hl)
+        if record:
+            out.update(overlap=q, link_overlap=ql)
     return out
+
+
+def _histograms(pair, hq_shape, hl_shape):
+    """Copies of the histograms (hq, hl) as contiguous uint64 arrays of the given shapes."""
+    hq, hl = (np.ascontiguousarray(np.array(x, dtype=np.uint64)) for x in pair)
+    if hq.shape != tuple(hq_shape) or hl.shape != tuple(hl_shape):
+        raise IsingMcError(-1, "overlap histograms have the wrong shape")
+    return hq, hl
 
 
 class GraphState:
@@ -143,6 +171,7 @@ class GraphState:
         self.couplings = None if couplings is None else cj  # [R][E], or None: the batch shares the J of its edges
         self._counter_base = np.zeros((self.nreplicas, 8), dtype=np.uint64)
         self._ladder = None  # the ladder of attach_tempering
+        self._ncopies = None  # the copies per group of attach_overlaps
         init = None
         if state is not None:
             st = np.asarray(state, dtype=np.uint8)
@@ -192,6 +221,7 @@ class GraphState:
             return
         state, epoch, counters = self.state_ref(), self.get_epoch(), self.counters()
         tempering = self._tempering_state() if self._ladder is not None else None
+        overlaps = (self._ncopies,) + self.overlap_histograms() if self._ncopies is not None else None
         old, self._cfg_flags = self._cfg_flags, flags
         handle, self._h = self._h, None
         try:
@@ -204,31 +234,87 @@ class GraphState:
         self._counter_base = counters
         if tempering is not None:
             self._restore_tempering(*tempering)
+        if overlaps is not None:
+            self._restore_overlaps(*overlaps)
 
     # ---- parallel tempering (csrc/classical_pt_rule.h) ----
     def attach_tempering(self, betas):
         """The batch as C chains of T = len(betas) temperatures, slot r = c T + i starting at betas[i]; one ladder for all chains.
-        Attaching again resets the maps, the swap counters and the step number."""
+        Attaching again resets the maps, the swap counters and the step number, and detaches the overlaps (attach_overlaps)."""
         ladder = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).reshape(-1))
         self._check(self._lib.isingmc_classical_pt_attach(self._h, len(ladder), _ptr(ladder, C.c_double)))
-        self._ladder = ladder
+        self._ladder, self._ncopies = ladder, None
 
     def _chains(self):
         if self._ladder is None:
             raise IsingMcError(-1, "tempering is not attached (attach_tempering)")
         return self.nreplicas // len(self._ladder), len(self._ladder)
 
-    def tempering_run(self, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None, only_basic_moves=None, kinds=None, record=True):
+    def tempering_run(self, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None, only_basic_moves=None, kinds=None, record=True,
+                      overlaps=False):
         """`rounds` rounds of (`steps` time steps of every slot at its temperature, one tempering step of every chain), enqueued on the
         device with one synchronisation at the end.  With `record`: {"energy": float64 [rounds][C][T], "magnetization": int32
-        [rounds][C][T]}, by temperature, the values before each round's swaps; otherwise None."""
+        [rounds][C][T]}, by temperature, the values before each round's swaps; otherwise None.
+        `overlaps` (after attach_overlaps): every round also measures the overlaps between the copies of every group, after its steps
+        and before its swaps.  The histograms accumulate, and with `record` the dict also holds "overlap" and "link_overlap", int32
+        [rounds][G][P][T].  Without `overlaps` nothing is measured and the histograms stay as they are (thermalisation)."""
         c, t = self._chains()
         energy = np.zeros((int(rounds), c, t), dtype=np.float64) if record else None
         mag = np.zeros((int(rounds), c, t), dtype=np.int32) if record else None
-        self._check(self._lib.isingmc_classical_pt_run(self._h, int(rounds), int(steps), _count(nspinupdates), _count(nedgeupdates), _count(nwormupdates),
-                                                       _kinds(only_basic_moves, kinds), _ptr(energy, C.c_double) if record else None,
-                                                       _ptr(mag, C.c_int32) if record else None))
-        return {"energy": energy, "magnetization": mag} if record else None
+        run = (self._h, int(rounds), int(steps), _count(nspinupdates), _count(nedgeupdates), _count(nwormupdates), _kinds(only_basic_moves, kinds),
+               _ptr(energy, C.c_double) if record else None, _ptr(mag, C.c_int32) if record else None)
+        if not overlaps:
+            self._check(self._lib.isingmc_classical_pt_run(*run))
+            return {"energy": energy, "magnetization": mag} if record else None
+        shape = self._overlap_shape()
+        q, ql = (np.zeros((int(rounds),) + shape, dtype=np.int32) if record else None for _ in range(2))
+        self._check(self._lib.isingmc_classical_pt_run_overlaps(*run, _ptr(q, C.c_int32) if record else None, _ptr(ql, C.c_int32) if record else None))
+        return {"energy": energy, "magnetization": mag, "overlap": q, "link_overlap": ql} if record else None
+
+    # ---- overlaps between copies of a realisation (csrc/classical_overlap_rule.h) ----
+    def attach_overlaps(self, ncopies=2):
+        """Consecutive chains as G = C / ncopies groups of `ncopies` independent copies of one realisation (with `couplings`: the chains
+        of a group must hold the same rows); the P = K (K - 1) / 2 pairs of a group are (a, b), a < b, a-major.  Needs
+        attach_tempering.  The histograms start at zero; ncopies = 0 detaches."""
+        self._chains()
+        self._check(self._lib.isingmc_classical_overlap_attach(self._h, int(ncopies)))
+        self._ncopies = int(ncopies) if ncopies else None
+
+    def _overlap_shape(self):
+        """(G, P, T)"""
+        if self._ncopies is None:
+            raise IsingMcError(-1, "overlaps are not attached (attach_overlaps)")
+        c, t = self._chains()
+        return c // self._ncopies, self._ncopies * (self._ncopies - 1) // 2, t
+
+    def overlap_histograms(self):
+        """(hq, hl): uint64 [G][P][T][N + 1] by the number of differing variables nq (spin overlap Q = N - 2 nq) and uint64
+        [G][P][T][E + 1] by the number of differing edges nl (link overlap QL = E - 2 nl); one count per measured round since
+        attach_overlaps or reset_overlaps."""
+        shape = self._overlap_shape()
+        hq, hl = np.zeros(shape + (self.nvars + 1,), dtype=np.uint64), np.zeros(shape + (len(self.edges) + 1,), dtype=np.uint64)
+        self._check(self._lib.isingmc_classical_overlap_histograms(self._h, _ptr(hq, C.c_uint64), _ptr(hl, C.c_uint64)))
+        return hq, hl
+
+    def reset_overlaps(self):
+        self._overlap_shape()
+        self._check(self._lib.isingmc_classical_overlap_reset(self._h))
+
+    def overlap_moments(self):
+        """From the spin-overlap histogram summed over the pairs of a group, per (group, temperature): {"q2": <q^2>, "q4": <q^4>,
+        "binder": (3 - <q^4> / <q^2>^2) / 2}, float64 [G][T] each, q = Q / N.  NaN where nothing was measured."""
+        hq = self.overlap_histograms()[0].sum(axis=1).astype(np.float64)  # [G][T][N + 1]
+        q = (self.nvars - 2.0 * np.arange(self.nvars + 1)) / self.nvars
+        with np.errstate(invalid="ignore", divide="ignore"):
+            w = hq / hq.sum(axis=2, keepdims=True)
+            q2, q4 = (w * q ** 2).sum(axis=2), (w * q ** 4).sum(axis=2)
+            return {"q2": q2, "q4": q4, "binder": 0.5 * (3.0 - q4 / q2 ** 2)}
+
+    def _restore_overlaps(self, ncopies, hq, hl):
+        self.attach_overlaps(int(ncopies))
+        shape = self._overlap_shape()
+        hq, hl = _histograms((hq, hl), shape + (self.nvars + 1,), shape + (len(self.edges) + 1,))
+        self._check(self._lib.isingmc_classical_overlap_set_histograms(self._h, _ptr(hq, C.c_uint64), _ptr(hl, C.c_uint64)))
 
     def temperature_of(self):
         """uint32 [R]: the index into the ladder of the temperature each slot holds."""
@@ -341,7 +427,8 @@ class GraphState:
         restored with load_checkpoint continues bit-exactly.  With tempering attached the file is format 2: it also holds the ladder, the
         map of slots to temperatures, the tempering step number and both swap counters; without, it is the format-1 file.  A batch with
         per-replica couplings writes format 3: `couplings` [R][E] next to the keys of format 1, and those of format 2 when tempering is
-        attached."""
+        attached.  A batch with overlaps attached writes format 4: the keys it would otherwise write, and `ncopies`, `overlap_hist`,
+        `link_hist`."""
         extra = {}
         if self._ladder is not None:
             ladder, temp_of, pt_step, attempts, accepts = self._tempering_state()
@@ -349,6 +436,9 @@ class GraphState:
         fmt = 2 if extra else 1
         if self.couplings is not None:
             fmt, extra = 3, dict(extra, couplings=self.couplings)
+        if self._ncopies is not None:
+            hq, hl = self.overlap_histograms()
+            fmt, extra = 4, dict(extra, ncopies=np.array([self._ncopies], dtype=np.uint32), overlap_hist=hq, link_hist=hl)
         np.savez_compressed(path, format=np.array([fmt], dtype=np.uint32), edges=self.edges, J=self.J, biases=self.biases,
                             seed=np.array([self.seed], dtype=np.uint64), replica_offset=np.array([self.replica_offset], dtype=np.uint32),
                             importance=np.array([bool(self._cfg_flags & CFG_EDGE_IMPORTANCE)]), state=self.state_ref(), epoch=self.get_epoch(),
@@ -357,11 +447,12 @@ class GraphState:
     def load_checkpoint(self, path):
         z = np.load(path, allow_pickle=False)
         fmt = int(z["format"][0])
-        if fmt not in (1, 2, 3):
+        if fmt not in (1, 2, 3, 4):
             raise IsingMcError(-1, "unknown checkpoint format")
+        has_couplings = fmt == 3 or (fmt == 4 and "couplings" in z.files)
         if not np.array_equal(z["edges"], self.edges) or not np.array_equal(z["J"], self.J) or not np.array_equal(z["biases"], self.biases):
             raise IsingMcError(-1, "checkpoint belongs to a different model")
-        if (fmt == 3) != (self.couplings is not None) or (fmt == 3 and not np.array_equal(z["couplings"].view(np.uint64), self.couplings.view(np.uint64))):
+        if has_couplings != (self.couplings is not None) or (has_couplings and not np.array_equal(z["couplings"].view(np.uint64), self.couplings.view(np.uint64))):
             raise IsingMcError(-1, "checkpoint belongs to a batch with different per-replica couplings")
         if z["state"].shape != (self.nreplicas, self.nvars) or int(z["seed"][0]) != self.seed or int(z["replica_offset"][0]) != self.replica_offset:
             raise IsingMcError(-1, "checkpoint belongs to a different batch (replicas, seed or replica offset)")
@@ -369,8 +460,10 @@ class GraphState:
         self.set_state(z["state"])
         self.set_epoch(z["epoch"])
         self._counter_base = z["counters"].astype(np.uint64) - (self.counters() - self._counter_base)
-        if fmt == 2 or (fmt == 3 and "ladder" in z.files):
+        if fmt == 2 or (fmt >= 3 and "ladder" in z.files):
             self._restore_tempering(z["ladder"], z["temp_of"], int(z["pt_step"][0]), z["swap_attempts"], z["swap_accepts"])
+        if fmt == 4:
+            self._restore_overlaps(int(z["ncopies"][0]), z["overlap_hist"], z["link_hist"])
 
     def edge_list(self, r=None):
         """The edges as they were given: [((a, b), J), ...]; with `r`, the edges of replica r's realisation (its row of `couplings`)."""

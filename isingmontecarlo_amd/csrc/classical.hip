@@ -269,6 +269,8 @@ void isingmc_classical_destroy(isingmc_classical *g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     for (void *p : g->allocs) (void)hipFree(p);
+    if (g->ov.dev.hq) (void)hipFree(g->ov.dev.hq);
+    if (g->ov.dev.hl) (void)hipFree(g->ov.dev.hl);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     delete g;

@@ -37,6 +37,13 @@ struct CmcPtHandle {
     std::vector<double> betas;
 };
 
+// overlaps between copies (isingmc_classical_overlap_attach): the histograms live from attach to detach
+struct CmcOvHandle {
+    bool attached = false;
+    sse::CmcOvDev dev{};
+    size_t hq_count = 0, hl_count = 0; // entries of the two histograms
+};
+
 struct isingmc_classical {
     sse::CmcDev dev{};
     sse::CmcCarve carve{};
@@ -48,6 +55,7 @@ struct isingmc_classical {
     bool timed = false;
     double *d_beta = nullptr, *d_energy = nullptr;
     CmcPtHandle pt;
+    CmcOvHandle ov;
     std::vector<void *> allocs;
     mutable std::string err;
 };

@@ -120,4 +120,15 @@ struct CmcPtDev {
 // one tempering step of every chain at step number pt_step; energy_row / mag_row: [C][T] by temperature, or null
 hipError_t launch_classical_tempering(hipStream_t stream, const CmcDev &D, const CmcPtDev &P, uint64_t pt_step, double *energy_row, int32_t *mag_row);
 
+// The overlap launch (classical_overlap_rule.h; sse_classical_overlap.hip.h, unit sweep_classical_overlap.hip): G groups of K copies,
+// P = K (K - 1) / 2 pairs a group, one wave per item (g, p, t)
+#define CMC_OV_MAX_ITEMS 0x80000000ull // G P T at most: four items a workgroup keep the grid inside 2^31
+struct CmcOvDev {
+    uint32_t K, G, P; // copies a group, groups, pairs a group
+    uint64_t *hq;     // [G][P][T][N + 1] by the differing variables nq
+    uint64_t *hl;     // [G][P][T][E + 1] by the differing edges nl
+};
+// one measurement of every item with the maps as they stand; q_row / ql_row: [G][P][T], or null.  The histograms gain one count each.
+hipError_t launch_classical_overlaps(hipStream_t stream, const CmcDev &D, const CmcPtDev &P, const CmcOvDev &O, int32_t *q_row, int32_t *ql_row);
+
 } // namespace sse

@@ -1,7 +1,10 @@
 // classical_pt.hip — the C ABI of classical parallel tempering (include/isingmc_hip.h, isingmc_classical_pt_*): attach, the run of
 // rounds (steps launch, tempering launch) without a host synchronisation in between, the checkpoint accessors, and the same rounds by
-// the sequential rule on the CPU (isingmc_classical_host_pt_run).  The rule is classical_pt_rule.h.
+// the sequential rule on the CPU (isingmc_classical_host_pt_run).  The rule is classical_pt_rule.h.  The overlaps between copies of a
+// realisation (isingmc_classical_overlap_*, classical_overlap_rule.h) are measured inside those rounds, so they live here as well: one
+// round loop on the device and one on the host, with and without the measurement.
 #include "classical_handle.h"
+#include "classical_overlap_rule.h"
 #include "classical_pt_rule.h"
 
 #include <cmath>
@@ -26,6 +29,48 @@ static int check_pt_couplings(const CmcHostTables &H, uint32_t R, uint32_t ntemp
     if (c == CMC_NONE) return ISINGMC_OK;
     why = "tempering needs one set of couplings per chain: the coupling rows of chain " + std::to_string(c) + " (replicas " + std::to_string(c * ntemps) + " .. " +
           std::to_string(c * ntemps + ntemps - 1u) + ") differ; tempering between different graphs is not built";
+    return ISINGMC_EINVAL;
+}
+
+// The batch as groups of copies (classical_overlap_rule.h): what overlap_attach and the host entry ask, and the sizes that follow
+static const char *const kNeedCopies = "overlaps need ncopies >= 2 (copies of one realisation are compared in pairs)";
+struct CmcOvShape {
+    uint32_t K, G, P;
+    uint64_t items;            // G P T
+    size_t hq_count, hl_count; // entries of the histograms
+};
+static int check_overlap_args(const CmcHostTables &H, uint32_t R, uint32_t replica_offset, uint32_t T, uint32_t K, CmcOvShape &S, std::string &why) {
+    if (K < 2u) { why = kNeedCopies; return ISINGMC_EINVAL; }
+    const uint32_t C = R / T;
+    if (C % K != 0u) { why = "the number of chains (nreplicas / ntemps) must be a multiple of ncopies (a batch is whole groups)"; return ISINGMC_EINVAL; }
+    if ((replica_offset / T) % K != 0u) { why = "replica_offset / ntemps must be a multiple of ncopies (a group does not straddle batches)"; return ISINGMC_EINVAL; }
+    // a chain's rows are equal already: the K chains of a group are copies when its K T rows are
+    const uint32_t grp = H.first_mixed_chain(R, K * T);
+    if (grp != CMC_NONE) {
+        why = "overlaps compare copies of one realisation: the coupling rows of group " + std::to_string(grp) + " (replicas " + std::to_string((uint64_t)grp * K * T) +
+              " .. " + std::to_string((uint64_t)grp * K * T + (uint64_t)K * T - 1u) + ") differ";
+        return ISINGMC_EINVAL;
+    }
+    S.K = K; S.G = C / K;
+    S.items = (uint64_t)S.G * cmc_ov_pairs(K) * T;
+    if (S.items > CMC_OV_MAX_ITEMS) { why = "too many overlaps to measure: groups x pairs x temperatures exceeds 2^31"; return ISINGMC_EINVAL; }
+    S.P = (uint32_t)cmc_ov_pairs(K);
+    const size_t most = SIZE_MAX / 8u / (size_t)S.items;
+    if ((size_t)H.N + 1u > most || (size_t)H.E + 1u > most) { why = "the overlap histograms of this batch do not fit a size_t"; return ISINGMC_EINVAL; }
+    S.hq_count = (size_t)S.items * ((size_t)H.N + 1u);
+    S.hl_count = (size_t)S.items * ((size_t)H.E + 1u);
+    return ISINGMC_OK;
+}
+
+static void detach_overlaps(isingmc_classical *g) {
+    if (g->ov.dev.hq) (void)hipFree(g->ov.dev.hq);
+    if (g->ov.dev.hl) (void)hipFree(g->ov.dev.hl);
+    g->ov = CmcOvHandle{};
+}
+
+static int need_overlaps(isingmc_classical *g, const char *who) {
+    if (g->ov.attached) return ISINGMC_OK;
+    g->err = std::string(who) + ": call isingmc_classical_overlap_attach first";
     return ISINGMC_EINVAL;
 }
 
@@ -55,6 +100,43 @@ struct CmcBytes { // a state as bytes, read only
     bool get(uint32_t v) const { return s[v] != 0; }
 };
 
+// rounds x (steps launch, [overlap launch,] tempering launch) enqueued back to back, one synchronisation at the end: the loop of
+// isingmc_classical_pt_run and isingmc_classical_pt_run_overlaps.  measure: the overlap launch runs between the two (the handle has overlaps attached)
+static int run_rounds(isingmc_classical *g, bool measure, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
+                      double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out) {
+    if (kinds >= CMC_KINDS_COUNT) { g->err = "kinds must be one of ISINGMC_CLASSICAL_KINDS_*"; return ISINGMC_EINVAL; }
+    if (rounds == 0) return ISINGMC_OK;
+    const size_t R = g->dev.R, items = measure ? (size_t)g->ov.dev.G * g->ov.dev.P * g->pt.dev.T : 0u;
+    if ((energy_out || mag_out || q_out || ql_out) && rounds > (SIZE_MAX / 16u) / std::max(R, items)) { g->err = "the recorded series of this many rounds does not fit"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    struct Series { void *host, *dev; size_t row; }; // a recorded series: its rows are `row` bytes a round
+    Series series[4] = {{energy_out, nullptr, R * 8}, {mag_out, nullptr, R * 4}, {q_out, nullptr, items * 4}, {ql_out, nullptr, items * 4}};
+    auto release = [&]() { for (Series &x : series) if (x.dev) (void)hipFree(x.dev); };
+    for (Series &x : series)
+        if (x.host && hipMalloc(&x.dev, (size_t)rounds * x.row) != hipSuccess) {
+            release();
+            g->err = "hipMalloc of a recorded series failed (" + std::to_string((size_t)rounds * x.row) + " bytes)";
+            return ISINGMC_ENODEVICE;
+        }
+    auto row = [&](int k, uint64_t i) { return series[k].dev ? static_cast<char *>(series[k].dev) + i * series[k].row : nullptr; };
+    const CmcStepArgs A{steps, g->pt.dev.beta_slot, nspin, nedge, nworm, kinds, (g->flags & ISINGMC_CLASSICAL_CFG_SERIAL_MOVES) ? 1u : 0u};
+    hipError_t e = hipEventRecord(g->ev0, g->stream);
+    for (uint64_t i = 0; i < rounds && e == hipSuccess; ++i) { // enqueued back to back: the tempering launch leaves the next steps launch its betas
+        if (steps) e = launch_classical_steps(g->stream, g->dev, g->carve, A);
+        if (e == hipSuccess && measure) // after the steps, before the swaps: the maps still say where every temperature is
+            e = launch_classical_overlaps(g->stream, g->dev, g->pt.dev, g->ov.dev, reinterpret_cast<int32_t *>(row(2, i)), reinterpret_cast<int32_t *>(row(3, i)));
+        if (e == hipSuccess) e = launch_classical_tempering(g->stream, g->dev, g->pt.dev, g->pt.step, reinterpret_cast<double *>(row(0, i)), reinterpret_cast<int32_t *>(row(1, i)));
+        if (e == hipSuccess) g->pt.step++;
+    }
+    if (e == hipSuccess) e = hipEventRecord(g->ev1, g->stream);
+    if (e == hipSuccess) { g->timed = true; e = hipStreamSynchronize(g->stream); }
+    for (Series &x : series)
+        if (e == hipSuccess && x.dev) e = hipMemcpy(x.host, x.dev, (size_t)rounds * x.row, hipMemcpyDeviceToHost);
+    release();
+    if (e != hipSuccess) { g->err = std::string("classical tempering run: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    return ISINGMC_OK;
+}
+
 extern "C" {
 
 int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const double *betas) {
@@ -77,6 +159,7 @@ int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const dou
         P.dev.betas = P.d_betas;
     }
     P.attached = false;
+    detach_overlaps(g); // the shape of the batch changes: groups and histograms belong to the ladder they were attached under
     P.dev.T = ntemps; P.dev.C = R / ntemps;
     P.betas.assign(betas, betas + ntemps);
     P.step = 0;
@@ -94,29 +177,68 @@ int isingmc_classical_pt_run(isingmc_classical *g, uint64_t rounds, uint64_t ste
                              double *energy_out, int32_t *mag_out) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_attached(g, "isingmc_classical_pt_run")) return rc;
-    if (kinds >= CMC_KINDS_COUNT) { g->err = "kinds must be one of ISINGMC_CLASSICAL_KINDS_*"; return ISINGMC_EINVAL; }
-    if (rounds == 0) return ISINGMC_OK;
-    const size_t R = g->dev.R;
-    if ((energy_out || mag_out) && rounds > (SIZE_MAX / 16u) / R) { g->err = "the recorded series of this many rounds does not fit"; return ISINGMC_EINVAL; }
+    return run_rounds(g, false, rounds, steps, nspin, nedge, nworm, kinds, energy_out, mag_out, nullptr, nullptr);
+}
+
+int isingmc_classical_pt_run_overlaps(isingmc_classical *g, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
+                                      double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_attached(g, "isingmc_classical_pt_run_overlaps")) return rc;
+    if (const int rc = need_overlaps(g, "isingmc_classical_pt_run_overlaps")) return rc;
+    return run_rounds(g, true, rounds, steps, nspin, nedge, nworm, kinds, energy_out, mag_out, q_out, ql_out);
+}
+
+int isingmc_classical_overlap_attach(isingmc_classical *g, uint32_t ncopies) {
+    if (!g) return ISINGMC_EINVAL;
     CMC_TRY(g, hipSetDevice(g->device));
-    double *d_e = nullptr;
-    int32_t *d_m = nullptr;
-    auto release = [&]() { if (d_e) (void)hipFree(d_e); if (d_m) (void)hipFree(d_m); };
-    if (energy_out) CMC_TRY(g, hipMalloc(reinterpret_cast<void **>(&d_e), (size_t)rounds * R * 8));
-    if (mag_out && hipMalloc(reinterpret_cast<void **>(&d_m), (size_t)rounds * R * 4) != hipSuccess) { release(); g->err = "hipMalloc of the magnetisation series failed"; return ISINGMC_ENODEVICE; }
-    const CmcStepArgs A{steps, g->pt.dev.beta_slot, nspin, nedge, nworm, kinds, (g->flags & ISINGMC_CLASSICAL_CFG_SERIAL_MOVES) ? 1u : 0u};
-    hipError_t e = hipEventRecord(g->ev0, g->stream);
-    for (uint64_t i = 0; i < rounds && e == hipSuccess; ++i) { // enqueued back to back: the tempering launch leaves the next steps launch its betas
-        if (steps) e = launch_classical_steps(g->stream, g->dev, g->carve, A);
-        if (e == hipSuccess) e = launch_classical_tempering(g->stream, g->dev, g->pt.dev, g->pt.step, d_e ? d_e + i * R : nullptr, d_m ? d_m + i * R : nullptr);
-        if (e == hipSuccess) g->pt.step++;
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    if (ncopies == 0u) { detach_overlaps(g); return ISINGMC_OK; }
+    if (const int rc = need_attached(g, "isingmc_classical_overlap_attach")) return rc;
+    CmcOvShape S{};
+    if (const int rc = check_overlap_args(g->host, g->dev.R, g->dev.replica_offset, g->pt.dev.T, ncopies, S, g->err)) return rc;
+    detach_overlaps(g);
+    uint64_t *hq = nullptr, *hl = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&hq), S.hq_count * 8u) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&hl), S.hl_count * 8u) != hipSuccess) {
+        if (hq) (void)hipFree(hq);
+        g->err = "hipMalloc of the overlap histograms failed (" + std::to_string(S.hq_count * 8u) + " and " + std::to_string(S.hl_count * 8u) + " bytes)";
+        return ISINGMC_ENODEVICE;
     }
-    if (e == hipSuccess) e = hipEventRecord(g->ev1, g->stream);
-    if (e == hipSuccess) { g->timed = true; e = hipStreamSynchronize(g->stream); }
-    if (e == hipSuccess && d_e) e = hipMemcpy(energy_out, d_e, (size_t)rounds * R * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && d_m) e = hipMemcpy(mag_out, d_m, (size_t)rounds * R * 4, hipMemcpyDeviceToHost);
-    release();
-    if (e != hipSuccess) { g->err = std::string("classical tempering run: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    g->ov.dev = sse::CmcOvDev{S.K, S.G, S.P, hq, hl};
+    g->ov.hq_count = S.hq_count; g->ov.hl_count = S.hl_count;
+    CMC_TRY(g, hipMemset(hq, 0, S.hq_count * 8u));
+    CMC_TRY(g, hipMemset(hl, 0, S.hl_count * 8u));
+    g->ov.attached = true;
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_overlap_histograms(isingmc_classical *g, uint64_t *hq, uint64_t *hl) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_overlaps(g, "isingmc_classical_overlap_histograms")) return rc;
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    if (hq) CMC_TRY(g, hipMemcpy(hq, g->ov.dev.hq, g->ov.hq_count * 8u, hipMemcpyDeviceToHost));
+    if (hl) CMC_TRY(g, hipMemcpy(hl, g->ov.dev.hl, g->ov.hl_count * 8u, hipMemcpyDeviceToHost));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_overlap_set_histograms(isingmc_classical *g, const uint64_t *hq, const uint64_t *hl) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_overlaps(g, "isingmc_classical_overlap_set_histograms")) return rc;
+    if (!hq || !hl) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    CMC_TRY(g, hipMemcpy(g->ov.dev.hq, hq, g->ov.hq_count * 8u, hipMemcpyHostToDevice));
+    CMC_TRY(g, hipMemcpy(g->ov.dev.hl, hl, g->ov.hl_count * 8u, hipMemcpyHostToDevice));
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_overlap_reset(isingmc_classical *g) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_overlaps(g, "isingmc_classical_overlap_reset")) return rc;
+    CMC_TRY(g, hipSetDevice(g->device));
+    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    CMC_TRY(g, hipMemset(g->ov.dev.hq, 0, g->ov.hq_count * 8u));
+    CMC_TRY(g, hipMemset(g->ov.dev.hl, 0, g->ov.hl_count * 8u));
     return ISINGMC_OK;
 }
 
@@ -169,9 +291,13 @@ int isingmc_classical_pt_set_swap_counts(isingmc_classical *g, const uint64_t *a
     return ISINGMC_OK;
 }
 
-int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint64_t rounds, uint64_t steps,
-                                  uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
-                                  uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out) {
+} // extern "C"
+
+// The rounds of isingmc_classical_host_pt_run and isingmc_classical_host_pt_run_overlaps: ncopies = 0 measures nothing
+static int host_rounds(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint32_t ncopies, uint64_t rounds, uint64_t steps,
+                       uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
+                       uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out,
+                       int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl) {
     if (const int rc = cmc_check_config(cfg)) return rc;
     std::string why;
     if (const int rc = check_pt_args(cfg->nreplicas, cfg->replica_offset, ntemps, betas, why)) return cmc_refuse(rc, why);
@@ -183,6 +309,9 @@ int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t 
     CmcHostTables H;
     cmc_build_tables(cfg, H);
     if (const int rc = check_pt_couplings(H, R, T, why)) return cmc_refuse(rc, why);
+    CmcOvShape ov{};
+    if (ncopies != 0u)
+        if (const int rc = check_overlap_args(H, R, cfg->replica_offset, T, ncopies, ov, why)) return cmc_refuse(rc, why);
     const uint32_t N = H.N;
     const CmcHostMoves m{cmc_default_moves(nspin, N / 2u), cmc_default_moves(nedge, H.E / 2u), cmc_default_moves(nworm, 1u), kinds};
     std::vector<uint8_t> mark(N, 0);
@@ -201,6 +330,18 @@ int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t 
             if (energy_out) energy_out[at] = energy[r];
             if (mag_out) mag_out[at] = cmc_pt_magnetization(g, s);
         }
+        for (uint64_t item = 0; item < ov.items; ++item) { // after the steps, before the swaps (ncopies = 0: no items)
+            uint32_t grp, p, t, a, b;
+            cmc_ov_item(item, ov.P, T, grp, p, t);
+            cmc_ov_pair(ov.K, p, a, b);
+            const uint32_t ra = cmc_ov_slot(slot_at.data(), T, grp * ov.K + a, t), rb = cmc_ov_slot(slot_at.data(), T, grp * ov.K + b, t);
+            const CmcBytes A{states + (size_t)ra * N}, B{states + (size_t)rb * N};
+            const uint32_t nq = cmc_ov_count_spins(N, A, B, 0u, 1u), nl = cmc_ov_count_links(cmc_graph_mem(H.view(), ra), A, B, 0u, 1u);
+            if (q_out) q_out[(size_t)round * ov.items + item] = cmc_ov_overlap(N, nq);
+            if (ql_out) ql_out[(size_t)round * ov.items + item] = cmc_ov_overlap(H.E, nl);
+            if (hq) hq[(size_t)item * ((size_t)N + 1u) + nq] += 1u;
+            if (hl) hl[(size_t)item * ((size_t)H.E + 1u) + nl] += 1u;
+        }
         for (uint32_t c = 0; c < C; ++c) {
             const size_t base = (size_t)c * T, cbase = (size_t)c * (T - 1u);
             const CmcPtChainView cv{T, betas, temp_of + base, slot_at.data() + base, energy.data() + base, attempts ? attempts + cbase : nullptr,
@@ -209,6 +350,25 @@ int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t 
         }
     }
     return ISINGMC_OK;
+}
+
+extern "C" {
+
+int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint64_t rounds, uint64_t steps,
+                                  uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
+                                  uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out) {
+    return host_rounds(cfg, ntemps, betas, 0u, rounds, steps, nspin, nedge, nworm, kinds, states, epochs, temp_of, pt_step, counters, attempts, accepts, energy_out, mag_out,
+                       nullptr, nullptr, nullptr, nullptr);
+}
+
+int isingmc_classical_host_pt_run_overlaps(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint32_t ncopies, uint64_t rounds, uint64_t steps,
+                                           uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
+                                           uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out,
+                                           int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl) {
+    if (const int rc = cmc_check_config(cfg)) return rc;
+    if (ncopies == 0u) return cmc_refuse(ISINGMC_EINVAL, kNeedCopies);
+    return host_rounds(cfg, ntemps, betas, ncopies, rounds, steps, nspin, nedge, nworm, kinds, states, epochs, temp_of, pt_step, counters, attempts, accepts, energy_out,
+                       mag_out, q_out, ql_out, hq, hl);
 }
 
 } // extern "C"

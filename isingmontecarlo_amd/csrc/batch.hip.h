@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/isingmc_hip.h"
+#include "hip_host.h"
 #include "lds_plan.h"
 #include "sse_batch.h"
 
@@ -37,6 +39,7 @@ struct isingmc_batch : BatchGeometry {
     uint32_t acc_rows = 0;
     uint32_t rvb_updates = 0;
     uint32_t *d_acc_row = nullptr;
+    DevBuf acc;                         // the accumulator table behind dev.acc: [acc_rows][8], replaced by isingmc_set_accumulator_rows
     bool acc_follow_slots = false;      // the caller passed the tempering slots as accumulator rows: isingmc_pt_step keeps row = slot
     uint32_t max_ntrans = 0;
     int device = 0;
@@ -63,29 +66,19 @@ struct isingmc_batch : BatchGeometry {
     uint32_t *d_out = nullptr;
     uint32_t *d_vstate = nullptr;
     uint8_t *d_ok = nullptr;
-    std::vector<void *> allocs;
+    std::vector<DevBuf> allocs;         // what lives as long as the batch (dalloc)
+    DevBuf rvb_prod, rvb_tbl;           // the blocks behind dev.rvb_prod / dev.rvb_tbl (driver.hip allocates them on first use)
     mutable std::string err;
     struct PtState *pt = nullptr;       // native parallel tempering (isingmc_pt_*, pt.hip)
     std::vector<uint32_t> ham_row_host; // [R] bond-table row of each local replica (tempering between different Hamiltonians), empty = identity
-    // sample record (isingmc_record_*, record.hip): [rec_cap][R][nwords] words, rows 0 .. rec_count - 1 written; nullptr = none attached
-    uint32_t *rec = nullptr;
+    // sample record (isingmc_record_*, record.hip): [rec_cap][R][nwords] words, rows 0 .. rec_count - 1 written; empty = none attached
+    DevBuf rec;
     uint32_t rec_cap = 0, rec_count = 0;
     // scratch of the record's observables, grown on demand: observable groups, bit series [R][ngroups][Tw], autocorrelations [R][T]
-    void *obs_groups = nullptr, *obs_series = nullptr, *obs_out = nullptr;
-    size_t obs_groups_bytes = 0, obs_series_bytes = 0, obs_out_bytes = 0;
+    DevBuf obs_groups, obs_series, obs_out;
     // scratch of the imaginary-time folds (isingmc_itime_groups, isingmc_bond_counts), grown on demand: results, groups, variable -> groups lists
-    void *itime_buf = nullptr;
-    size_t itime_buf_bytes = 0;
+    DevBuf itime_buf;
 };
-
-#define HIP_TRY(b, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            (b)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                             \
-            return ISINGMC_ENODEVICE;                                                                 \
-        }                                                                                             \
-    } while (0)
 
 namespace sse {
 
@@ -96,16 +89,29 @@ inline uint32_t lds_edges(const isingmc_batch *b) { return lds_edges(b->mode, b-
 inline LdsNeeds lds_needs(const isingmc_batch *b) { return {b->dev, b->mode, b->lds_total_words, b->uf_ids_limit, b->max_ntrans}; }
 inline LdsPlan plan_lds(const isingmc_batch *b, uint32_t W) { return plan_lds(lds_needs(b), W); }
 
-// count elements of device memory that live as long as the batch
+// count elements of device memory that live as long as the batch, or in `owner` (whose previous block is freed)
 template <typename T>
-int dalloc(isingmc_batch *b, T **p, size_t count, bool zero = true) {
-    void *q = nullptr;
-    size_t bytes = (count ? count : 1) * sizeof(T);
-    HIP_TRY(b, hipMalloc(&q, bytes));
-    b->allocs.push_back(q);
-    if (zero) HIP_TRY(b, hipMemset(q, 0, bytes));
-    *p = reinterpret_cast<T *>(q);
+int dalloc(isingmc_batch *b, T **p, size_t count, bool zero = true, DevBuf *owner = nullptr) {
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    DevBuf q;
+    if (const hipError_t e = q.alloc(bytes)) { b->err = std::string("hipMalloc(&q, bytes): ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    if (zero) HIP_TRY(b, hipMemset(q.as<void>(), 0, bytes));
+    *p = q.as<T>();
+    if (owner) *owner = std::move(q); else b->allocs.push_back(std::move(q));
     return ISINGMC_OK;
+}
+
+// The observable groups of a call (group g = group_vars[group_start[g] .. group_start[g + 1])): non-empty groups of variables below N
+inline int check_groups(isingmc_batch *b, const char *prefix, uint32_t ngroups, const uint32_t *group_start, const uint32_t *group_vars, uint32_t N) {
+    const char *why = nullptr;
+    if (group_start[0] != 0u) why = ": group_start[0] must be 0";
+    for (uint32_t g = 0; !why && g < ngroups; ++g)
+        if (group_start[g + 1] <= group_start[g]) why = ": every observable group needs at least one variable";
+    for (uint32_t k = 0; !why && k < group_start[ngroups]; ++k)
+        if (group_vars[k] >= N) why = ": group variable out of range";
+    if (!why) return ISINGMC_OK;
+    b->err = std::string(prefix) + why;
+    return ISINGMC_EINVAL;
 }
 
 int ensure_materialized(isingmc_batch *b);   // driver.hip: apply the flip bytes that replicas' strings still wait for

@@ -159,13 +159,6 @@ static void plan_slots(const CmcCarve &C, uint32_t table_flags, uint32_t out[8])
     std::copy(slots, slots + 8, out);
 }
 
-static void pack_states(const uint8_t *in, uint32_t rows, uint32_t N, uint32_t nwords, std::vector<uint32_t> &out) {
-    out.assign((size_t)rows * nwords, 0u);
-    for (uint32_t r = 0; r < rows; ++r)
-        for (uint32_t v = 0; v < N; ++v)
-            if (in[(size_t)r * N + v]) out[(size_t)r * nwords + (v >> 5)] |= 1u << (v & 31u);
-}
-
 static int allocate_and_upload(isingmc_classical *g, const isingmc_classical_config *cfg) {
     const CmcHostTables &H = g->host;
     CmcDev &D = g->dev;
@@ -188,15 +181,15 @@ static int allocate_and_upload(isingmc_classical *g, const isingmc_classical_con
     if (const int rc = cmc_alloc(g, &D.err, D.R)) return rc;
     if (const int rc = cmc_alloc(g, &g->d_beta, D.R)) return rc;
     if (const int rc = cmc_alloc(g, &g->d_energy, D.R)) return rc;
-    CMC_TRY(g, hipEventCreate(&g->ev0));
-    CMC_TRY(g, hipEventCreate(&g->ev1));
+    HIP_TRY(g, hipEventCreate(&g->ev0));
+    HIP_TRY(g, hipEventCreate(&g->ev1));
     if (cfg->init_state) {
-        std::vector<uint32_t> words;
-        pack_states(cfg->init_state, D.R, H.N, D.nwords, words);
-        CMC_TRY(g, hipMemcpy(D.state, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+        std::vector<uint32_t> words((size_t)D.R * D.nwords);
+        pack_bits(cfg->init_state, D.R, H.N, D.nwords, words.data());
+        HIP_TRY(g, hipMemcpy(D.state, words.data(), words.size() * 4, hipMemcpyHostToDevice));
     } else {
-        CMC_TRY(g, launch_classical_init_state(nullptr, D, H.N));
-        CMC_TRY(g, hipDeviceSynchronize());
+        HIP_TRY(g, launch_classical_init_state(nullptr, D, H.N));
+        HIP_TRY(g, hipDeviceSynchronize());
     }
     return ISINGMC_OK;
 }
@@ -250,13 +243,8 @@ int isingmc_classical_create(const isingmc_classical_config *cfg, isingmc_classi
     if (!out) return cmc_refuse(ISINGMC_EINVAL, "null output");
     *out = nullptr;
     if (const int rc = cmc_check_config(cfg)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return cmc_refuse(ISINGMC_ENODEVICE, "no HIP device available (this library has no CPU fallback)");
-    int dev = cfg->device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipSetDevice(dev) != hipSuccess) return cmc_refuse(ISINGMC_ENODEVICE, "hipSetDevice failed");
-    int max_lds = 0;
-    if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || max_lds <= 0) max_lds = 65536;
+    int dev = 0, max_lds = 0;
+    if (const char *why = probe_device(cfg->device, &dev, &max_lds)) return cmc_refuse(ISINGMC_ENODEVICE, why);
     isingmc_classical *g = new isingmc_classical();
     g->device = dev; g->flags = cfg->flags;
     if (const int rc = plan_config(cfg, (uint32_t)max_lds, g->host, g->carve)) { delete g; return rc; }
@@ -268,9 +256,6 @@ int isingmc_classical_create(const isingmc_classical_config *cfg, isingmc_classi
 void isingmc_classical_destroy(isingmc_classical *g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
-    for (void *p : g->allocs) (void)hipFree(p);
-    if (g->ov.dev.hq) (void)hipFree(g->ov.dev.hq);
-    if (g->ov.dev.hl) (void)hipFree(g->ov.dev.hl);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     delete g;
@@ -285,80 +270,63 @@ int isingmc_classical_timesteps(isingmc_classical *g, uint64_t t, const double *
     for (uint32_t r = 0; r < g->dev.R; ++r)
         if (std::isnan(beta[r])) { g->err = "beta must not be NaN"; return ISINGMC_EINVAL; }
     if (t == 0) return ISINGMC_OK;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipMemcpyAsync(g->d_beta, beta, (size_t)g->dev.R * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipMemcpyAsync(g->d_beta, beta, (size_t)g->dev.R * sizeof(double), hipMemcpyHostToDevice, g->stream));
     const CmcStepArgs A{t, g->d_beta, nspin, nedge, nworm, kinds, (g->flags & ISINGMC_CLASSICAL_CFG_SERIAL_MOVES) ? 1u : 0u};
-    CMC_TRY(g, hipEventRecord(g->ev0, g->stream));
+    HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
     const hipError_t e = launch_classical_steps(g->stream, g->dev, g->carve, A);
     if (e != hipSuccess) { g->err = std::string("classical steps launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
-    CMC_TRY(g, hipEventRecord(g->ev1, g->stream));
+    HIP_TRY(g, hipEventRecord(g->ev1, g->stream));
     g->timed = true;
     // beta is borrowed for the call only, and its copy was asynchronous from pageable memory: wait for the stream
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
     return ISINGMC_OK;
 }
 
 int isingmc_classical_get_state(isingmc_classical *g, uint32_t r, uint8_t *out) {
     if (!g) return ISINGMC_EINVAL;
     if (!out || (r != UINT32_MAX && r >= g->dev.R)) { g->err = "bad replica index or null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    const uint32_t r0 = r == UINT32_MAX ? 0u : r, rows = r == UINT32_MAX ? g->dev.R : 1u, nw = g->dev.nwords, N = g->host.N;
+    const uint32_t r0 = r == UINT32_MAX ? 0u : r, rows = r == UINT32_MAX ? g->dev.R : 1u, nw = g->dev.nwords;
     std::vector<uint32_t> words((size_t)rows * nw);
-    CMC_TRY(g, hipMemcpy(words.data(), g->dev.state + (size_t)r0 * nw, words.size() * 4, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < rows; ++i)
-        for (uint32_t v = 0; v < N; ++v) out[(size_t)i * N + v] = (uint8_t)((words[(size_t)i * nw + (v >> 5)] >> (v & 31u)) & 1u);
+    if (const int rc = copy_down(g, words.data(), g->dev.state + (size_t)r0 * nw, words.size(), true)) return rc;
+    unpack_bits(words.data(), rows, g->host.N, nw, out);
     return ISINGMC_OK;
 }
 
 int isingmc_classical_set_state(isingmc_classical *g, uint32_t r, const uint8_t *in) {
     if (!g) return ISINGMC_EINVAL;
     if (!in || (r != UINT32_MAX && r >= g->dev.R)) { g->err = "bad replica index or null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
     const uint32_t r0 = r == UINT32_MAX ? 0u : r, rows = r == UINT32_MAX ? g->dev.R : 1u, nw = g->dev.nwords;
-    std::vector<uint32_t> words;
-    pack_states(in, rows, g->host.N, nw, words);
-    CMC_TRY(g, hipMemcpy(g->dev.state + (size_t)r0 * nw, words.data(), words.size() * 4, hipMemcpyHostToDevice));
-    return ISINGMC_OK;
+    std::vector<uint32_t> words((size_t)rows * nw);
+    pack_bits(in, rows, g->host.N, nw, words.data());
+    return copy_up(g, g->dev.state + (size_t)r0 * nw, words.data(), words.size(), true);
 }
 
 int isingmc_classical_get_epoch(isingmc_classical *g, uint64_t *out) {
     if (!g) return ISINGMC_EINVAL;
     if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    CMC_TRY(g, hipMemcpy(out, g->dev.epoch, (size_t)g->dev.R * 8, hipMemcpyDeviceToHost));
-    return ISINGMC_OK;
+    return copy_down(g, out, g->dev.epoch, g->dev.R, true);
 }
 
 int isingmc_classical_set_epoch(isingmc_classical *g, const uint64_t *epochs) {
     if (!g) return ISINGMC_EINVAL;
     if (!epochs) { g->err = "null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    CMC_TRY(g, hipMemcpy(g->dev.epoch, epochs, (size_t)g->dev.R * 8, hipMemcpyHostToDevice));
-    return ISINGMC_OK;
+    return copy_up(g, g->dev.epoch, epochs, g->dev.R, true);
 }
 
 int isingmc_classical_energies(isingmc_classical *g, double *out) {
     if (!g) return ISINGMC_EINVAL;
     if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipSetDevice(g->device));
     const hipError_t e = launch_classical_energies(g->stream, g->dev, g->d_energy);
     if (e != hipSuccess) { g->err = std::string("classical energies launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    CMC_TRY(g, hipMemcpy(out, g->d_energy, (size_t)g->dev.R * 8, hipMemcpyDeviceToHost));
-    return ISINGMC_OK;
+    return copy_down(g, out, g->d_energy, g->dev.R, true);
 }
 
 int isingmc_classical_counters(isingmc_classical *g, uint64_t *out) {
     if (!g) return ISINGMC_EINVAL;
     if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    CMC_TRY(g, hipMemcpy(out, g->dev.counters, (size_t)g->dev.R * 64, hipMemcpyDeviceToHost));
-    return ISINGMC_OK;
+    return copy_down(g, out, g->dev.counters, (size_t)g->dev.R * 8, true);
 }
 
 int isingmc_classical_set_stream(isingmc_classical *g, void *hip_stream) {
@@ -369,8 +337,8 @@ int isingmc_classical_set_stream(isingmc_classical *g, void *hip_stream) {
 
 int isingmc_classical_synchronize(isingmc_classical *g) {
     if (!g) return ISINGMC_EINVAL;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
     return ISINGMC_OK;
 }
 
@@ -379,9 +347,9 @@ int isingmc_classical_last_kernel_ms(isingmc_classical *g, float *ms) {
     if (!ms) { g->err = "null buffer"; return ISINGMC_EINVAL; }
     *ms = 0.f;
     if (!g->timed) return ISINGMC_OK;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipEventSynchronize(g->ev1));
-    CMC_TRY(g, hipEventElapsedTime(ms, g->ev0, g->ev1));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipEventSynchronize(g->ev1));
+    HIP_TRY(g, hipEventElapsedTime(ms, g->ev0, g->ev1));
     return ISINGMC_OK;
 }
 

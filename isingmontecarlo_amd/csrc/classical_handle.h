@@ -4,9 +4,11 @@
 #pragma once
 #include "../../include/isingmc_hip.h"
 #include "classical_launch.h"
+#include "hip_host.h"
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 // the graph tables of classical_rule.h on the host
@@ -41,6 +43,7 @@ struct CmcPtHandle {
 struct CmcOvHandle {
     bool attached = false;
     sse::CmcOvDev dev{};
+    DevBuf hq, hl;                     // the blocks behind dev.hq / dev.hl
     size_t hq_count = 0, hl_count = 0; // entries of the two histograms
 };
 
@@ -56,37 +59,29 @@ struct isingmc_classical {
     double *d_beta = nullptr, *d_energy = nullptr;
     CmcPtHandle pt;
     CmcOvHandle ov;
-    std::vector<void *> allocs;
+    std::vector<DevBuf> allocs;
     mutable std::string err;
 };
 
-#define CMC_TRY(g, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            (g)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                             \
-            return ISINGMC_ENODEVICE;                                                                 \
-        }                                                                                             \
-    } while (0)
-
-template <typename T>
-static int cmc_upload(isingmc_classical *g, const T **p, const std::vector<T> &v) {
-    void *q = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    CMC_TRY(g, hipMalloc(&q, bytes));
-    g->allocs.push_back(q);
-    if (!v.empty()) CMC_TRY(g, hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *p = reinterpret_cast<const T *>(q);
-    return ISINGMC_OK;
-}
+// count zeroed elements of device memory that live as long as the handle
 template <typename T>
 static int cmc_alloc(isingmc_classical *g, T **p, size_t count) {
-    void *q = nullptr;
     const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    CMC_TRY(g, hipMalloc(&q, bytes));
-    g->allocs.push_back(q);
-    CMC_TRY(g, hipMemset(q, 0, bytes));
-    *p = reinterpret_cast<T *>(q);
+    DevBuf q;
+    if (const hipError_t e = q.alloc(bytes)) { g->err = std::string("hipMalloc(&q, bytes): ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    HIP_TRY(g, hipMemset(q.as<void>(), 0, bytes));
+    *p = q.as<T>();
+    g->allocs.push_back(std::move(q));
+    return ISINGMC_OK;
+}
+// ... a copy of v (at least one element is allocated)
+template <typename T>
+static int cmc_upload(isingmc_classical *g, const T **p, const std::vector<T> &v) {
+    DevBuf q;
+    if (const hipError_t e = q.alloc(std::max<size_t>(v.size(), 1) * sizeof(T))) { g->err = std::string("hipMalloc(&q, bytes): ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
+    if (!v.empty()) HIP_TRY(g, hipMemcpy(q.as<void>(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *p = q.as<T>();
+    g->allocs.push_back(std::move(q));
     return ISINGMC_OK;
 }
 

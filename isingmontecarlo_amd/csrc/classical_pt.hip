@@ -62,11 +62,7 @@ static int check_overlap_args(const CmcHostTables &H, uint32_t R, uint32_t repli
     return ISINGMC_OK;
 }
 
-static void detach_overlaps(isingmc_classical *g) {
-    if (g->ov.dev.hq) (void)hipFree(g->ov.dev.hq);
-    if (g->ov.dev.hl) (void)hipFree(g->ov.dev.hl);
-    g->ov = CmcOvHandle{};
-}
+static void detach_overlaps(isingmc_classical *g) { g->ov = CmcOvHandle{}; } // (frees the histograms)
 
 static int need_overlaps(isingmc_classical *g, const char *who) {
     if (g->ov.attached) return ISINGMC_OK;
@@ -89,10 +85,9 @@ static int upload_maps(isingmc_classical *g, const uint32_t *temp_of) {
         slot_at[(r / T) * T + temp_of[r]] = r % T;
         beta_slot[r] = g->pt.betas[temp_of[r]];
     }
-    CMC_TRY(g, hipMemcpy(g->pt.dev.temp_of, temp_of, (size_t)R * 4, hipMemcpyHostToDevice));
-    CMC_TRY(g, hipMemcpy(g->pt.dev.slot_at, slot_at.data(), (size_t)R * 4, hipMemcpyHostToDevice));
-    CMC_TRY(g, hipMemcpy(g->pt.dev.beta_slot, beta_slot.data(), (size_t)R * 8, hipMemcpyHostToDevice));
-    return ISINGMC_OK;
+    if (const int rc = copy_up(g, g->pt.dev.temp_of, temp_of, R)) return rc;
+    if (const int rc = copy_up(g, g->pt.dev.slot_at, slot_at.data(), R)) return rc;
+    return copy_up(g, g->pt.dev.beta_slot, beta_slot.data(), R);
 }
 
 struct CmcBytes { // a state as bytes, read only
@@ -108,17 +103,15 @@ static int run_rounds(isingmc_classical *g, bool measure, uint64_t rounds, uint6
     if (rounds == 0) return ISINGMC_OK;
     const size_t R = g->dev.R, items = measure ? (size_t)g->ov.dev.G * g->ov.dev.P * g->pt.dev.T : 0u;
     if ((energy_out || mag_out || q_out || ql_out) && rounds > (SIZE_MAX / 16u) / std::max(R, items)) { g->err = "the recorded series of this many rounds does not fit"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    struct Series { void *host, *dev; size_t row; }; // a recorded series: its rows are `row` bytes a round
-    Series series[4] = {{energy_out, nullptr, R * 8}, {mag_out, nullptr, R * 4}, {q_out, nullptr, items * 4}, {ql_out, nullptr, items * 4}};
-    auto release = [&]() { for (Series &x : series) if (x.dev) (void)hipFree(x.dev); };
+    HIP_TRY(g, hipSetDevice(g->device));
+    struct Series { void *host; DevBuf dev; size_t row; }; // a recorded series: its rows are `row` bytes a round (per call: freed on every way out)
+    Series series[4] = {{energy_out, {}, R * 8}, {mag_out, {}, R * 4}, {q_out, {}, items * 4}, {ql_out, {}, items * 4}};
     for (Series &x : series)
-        if (x.host && hipMalloc(&x.dev, (size_t)rounds * x.row) != hipSuccess) {
-            release();
+        if (x.host && x.dev.alloc((size_t)rounds * x.row) != hipSuccess) {
             g->err = "hipMalloc of a recorded series failed (" + std::to_string((size_t)rounds * x.row) + " bytes)";
             return ISINGMC_ENODEVICE;
         }
-    auto row = [&](int k, uint64_t i) { return series[k].dev ? static_cast<char *>(series[k].dev) + i * series[k].row : nullptr; };
+    auto row = [&](int k, uint64_t i) { return series[k].dev ? series[k].dev.as<char>() + i * series[k].row : nullptr; };
     const CmcStepArgs A{steps, g->pt.dev.beta_slot, nspin, nedge, nworm, kinds, (g->flags & ISINGMC_CLASSICAL_CFG_SERIAL_MOVES) ? 1u : 0u};
     hipError_t e = hipEventRecord(g->ev0, g->stream);
     for (uint64_t i = 0; i < rounds && e == hipSuccess; ++i) { // enqueued back to back: the tempering launch leaves the next steps launch its betas
@@ -131,8 +124,7 @@ static int run_rounds(isingmc_classical *g, bool measure, uint64_t rounds, uint6
     if (e == hipSuccess) e = hipEventRecord(g->ev1, g->stream);
     if (e == hipSuccess) { g->timed = true; e = hipStreamSynchronize(g->stream); }
     for (Series &x : series)
-        if (e == hipSuccess && x.dev) e = hipMemcpy(x.host, x.dev, (size_t)rounds * x.row, hipMemcpyDeviceToHost);
-    release();
+        if (e == hipSuccess && x.dev) e = hipMemcpy(x.host, x.dev.as<void>(), (size_t)rounds * x.row, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { g->err = std::string("classical tempering run: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
     return ISINGMC_OK;
 }
@@ -143,8 +135,8 @@ int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const dou
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = check_pt_args(g->dev.R, g->dev.replica_offset, ntemps, betas, g->err)) return rc;
     if (const int rc = check_pt_couplings(g->host, g->dev.R, ntemps, g->err)) return rc;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
     const uint32_t R = g->dev.R;
     CmcPtHandle &P = g->pt;
     if (!P.dev.temp_of) { // once: R entries hold any ladder of this batch
@@ -163,9 +155,9 @@ int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const dou
     P.dev.T = ntemps; P.dev.C = R / ntemps;
     P.betas.assign(betas, betas + ntemps);
     P.step = 0;
-    CMC_TRY(g, hipMemcpy(P.d_betas, betas, (size_t)ntemps * 8, hipMemcpyHostToDevice));
-    CMC_TRY(g, hipMemset(P.dev.attempts, 0, (size_t)R * 8));
-    CMC_TRY(g, hipMemset(P.dev.accepts, 0, (size_t)R * 8));
+    HIP_TRY(g, hipMemcpy(P.d_betas, betas, (size_t)ntemps * 8, hipMemcpyHostToDevice));
+    HIP_TRY(g, hipMemset(P.dev.attempts, 0, (size_t)R * 8));
+    HIP_TRY(g, hipMemset(P.dev.accepts, 0, (size_t)R * 8));
     std::vector<uint32_t> temp_of(R);
     for (uint32_t r = 0; r < R; ++r) temp_of[r] = r % ntemps;
     if (const int rc = upload_maps(g, temp_of.data())) return rc;
@@ -190,23 +182,23 @@ int isingmc_classical_pt_run_overlaps(isingmc_classical *g, uint64_t rounds, uin
 
 int isingmc_classical_overlap_attach(isingmc_classical *g, uint32_t ncopies) {
     if (!g) return ISINGMC_EINVAL;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
     if (ncopies == 0u) { detach_overlaps(g); return ISINGMC_OK; }
     if (const int rc = need_attached(g, "isingmc_classical_overlap_attach")) return rc;
     CmcOvShape S{};
     if (const int rc = check_overlap_args(g->host, g->dev.R, g->dev.replica_offset, g->pt.dev.T, ncopies, S, g->err)) return rc;
     detach_overlaps(g);
-    uint64_t *hq = nullptr, *hl = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&hq), S.hq_count * 8u) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&hl), S.hl_count * 8u) != hipSuccess) {
-        if (hq) (void)hipFree(hq);
+    CmcOvHandle &O = g->ov;
+    if (O.hq.alloc(S.hq_count * 8u) != hipSuccess || O.hl.alloc(S.hl_count * 8u) != hipSuccess) {
+        detach_overlaps(g);
         g->err = "hipMalloc of the overlap histograms failed (" + std::to_string(S.hq_count * 8u) + " and " + std::to_string(S.hl_count * 8u) + " bytes)";
         return ISINGMC_ENODEVICE;
     }
-    g->ov.dev = sse::CmcOvDev{S.K, S.G, S.P, hq, hl};
-    g->ov.hq_count = S.hq_count; g->ov.hl_count = S.hl_count;
-    CMC_TRY(g, hipMemset(hq, 0, S.hq_count * 8u));
-    CMC_TRY(g, hipMemset(hl, 0, S.hl_count * 8u));
+    O.dev = sse::CmcOvDev{S.K, S.G, S.P, O.hq.as<uint64_t>(), O.hl.as<uint64_t>()};
+    O.hq_count = S.hq_count; O.hl_count = S.hl_count;
+    HIP_TRY(g, hipMemset(O.dev.hq, 0, S.hq_count * 8u));
+    HIP_TRY(g, hipMemset(O.dev.hl, 0, S.hl_count * 8u));
     g->ov.attached = true;
     return ISINGMC_OK;
 }
@@ -214,40 +206,33 @@ int isingmc_classical_overlap_attach(isingmc_classical *g, uint32_t ncopies) {
 int isingmc_classical_overlap_histograms(isingmc_classical *g, uint64_t *hq, uint64_t *hl) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_overlaps(g, "isingmc_classical_overlap_histograms")) return rc;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    if (hq) CMC_TRY(g, hipMemcpy(hq, g->ov.dev.hq, g->ov.hq_count * 8u, hipMemcpyDeviceToHost));
-    if (hl) CMC_TRY(g, hipMemcpy(hl, g->ov.dev.hl, g->ov.hl_count * 8u, hipMemcpyDeviceToHost));
-    return ISINGMC_OK;
+    if (const int rc = isingmc_classical_synchronize(g)) return rc;
+    if (hq) if (const int rc = copy_down(g, hq, g->ov.dev.hq, g->ov.hq_count)) return rc;
+    return hl ? copy_down(g, hl, g->ov.dev.hl, g->ov.hl_count) : ISINGMC_OK;
 }
 
 int isingmc_classical_overlap_set_histograms(isingmc_classical *g, const uint64_t *hq, const uint64_t *hl) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_overlaps(g, "isingmc_classical_overlap_set_histograms")) return rc;
     if (!hq || !hl) { g->err = "null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    CMC_TRY(g, hipMemcpy(g->ov.dev.hq, hq, g->ov.hq_count * 8u, hipMemcpyHostToDevice));
-    CMC_TRY(g, hipMemcpy(g->ov.dev.hl, hl, g->ov.hl_count * 8u, hipMemcpyHostToDevice));
-    return ISINGMC_OK;
+    if (const int rc = copy_up(g, g->ov.dev.hq, hq, g->ov.hq_count, true)) return rc;
+    return copy_up(g, g->ov.dev.hl, hl, g->ov.hl_count);
 }
 
 int isingmc_classical_overlap_reset(isingmc_classical *g) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_overlaps(g, "isingmc_classical_overlap_reset")) return rc;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    CMC_TRY(g, hipMemset(g->ov.dev.hq, 0, g->ov.hq_count * 8u));
-    CMC_TRY(g, hipMemset(g->ov.dev.hl, 0, g->ov.hl_count * 8u));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    HIP_TRY(g, hipMemset(g->ov.dev.hq, 0, g->ov.hq_count * 8u));
+    HIP_TRY(g, hipMemset(g->ov.dev.hl, 0, g->ov.hl_count * 8u));
     return ISINGMC_OK;
 }
 
 int isingmc_classical_pt_get(isingmc_classical *g, uint32_t *temp_of, uint64_t *pt_step) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_attached(g, "isingmc_classical_pt_get")) return rc;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    if (temp_of) CMC_TRY(g, hipMemcpy(temp_of, g->pt.dev.temp_of, (size_t)g->dev.R * 4, hipMemcpyDeviceToHost));
+    if (const int rc = temp_of ? copy_down(g, temp_of, g->pt.dev.temp_of, g->dev.R, true) : isingmc_classical_synchronize(g)) return rc;
     if (pt_step) *pt_step = g->pt.step;
     return ISINGMC_OK;
 }
@@ -261,8 +246,8 @@ int isingmc_classical_pt_set(isingmc_classical *g, const uint32_t *temp_of, uint
         g->err = "temp_of must be a permutation of the temperatures within every chain";
         return ISINGMC_EINVAL;
     }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
     if (const int rc = upload_maps(g, temp_of)) return rc;
     g->pt.step = pt_step;
     return ISINGMC_OK;
@@ -271,24 +256,19 @@ int isingmc_classical_pt_set(isingmc_classical *g, const uint32_t *temp_of, uint
 int isingmc_classical_pt_swap_counts(isingmc_classical *g, uint64_t *attempts, uint64_t *accepts) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_attached(g, "isingmc_classical_pt_swap_counts")) return rc;
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    const size_t bytes = (size_t)g->pt.dev.C * (g->pt.dev.T - 1u) * 8;
-    if (attempts) CMC_TRY(g, hipMemcpy(attempts, g->pt.dev.attempts, bytes, hipMemcpyDeviceToHost));
-    if (accepts) CMC_TRY(g, hipMemcpy(accepts, g->pt.dev.accepts, bytes, hipMemcpyDeviceToHost));
-    return ISINGMC_OK;
+    if (const int rc = isingmc_classical_synchronize(g)) return rc;
+    const size_t pairs = (size_t)g->pt.dev.C * (g->pt.dev.T - 1u);
+    if (attempts) if (const int rc = copy_down(g, attempts, g->pt.dev.attempts, pairs)) return rc;
+    return accepts ? copy_down(g, accepts, g->pt.dev.accepts, pairs) : ISINGMC_OK;
 }
 
 int isingmc_classical_pt_set_swap_counts(isingmc_classical *g, const uint64_t *attempts, const uint64_t *accepts) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_attached(g, "isingmc_classical_pt_set_swap_counts")) return rc;
     if (!attempts || !accepts) { g->err = "null buffer"; return ISINGMC_EINVAL; }
-    CMC_TRY(g, hipSetDevice(g->device));
-    CMC_TRY(g, hipStreamSynchronize(g->stream));
-    const size_t bytes = (size_t)g->pt.dev.C * (g->pt.dev.T - 1u) * 8;
-    CMC_TRY(g, hipMemcpy(g->pt.dev.attempts, attempts, bytes, hipMemcpyHostToDevice));
-    CMC_TRY(g, hipMemcpy(g->pt.dev.accepts, accepts, bytes, hipMemcpyHostToDevice));
-    return ISINGMC_OK;
+    const size_t pairs = (size_t)g->pt.dev.C * (g->pt.dev.T - 1u);
+    if (const int rc = copy_up(g, g->pt.dev.attempts, attempts, pairs, true)) return rc;
+    return copy_up(g, g->pt.dev.accepts, accepts, pairs);
 }
 
 } // extern "C"

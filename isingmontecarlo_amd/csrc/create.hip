@@ -363,7 +363,7 @@ static int allocate_and_upload(isingmc_batch *b, const isingmc_config *cfg, cons
     CREATE_TRY(dalloc(b, &D.err, R));
     CREATE_TRY(dalloc(b, &D.aux, R));
     CREATE_TRY(dalloc(b, &D.epoch, R));
-    CREATE_TRY(dalloc(b, &D.acc, R * 8));
+    CREATE_TRY(dalloc(b, &D.acc, R * 8, true, &b->acc));
     b->acc_rows = D.R;
     std::vector<uint32_t> ident(R);
     for (uint32_t i = 0; i < R; ++i) ident[i] = i;
@@ -448,13 +448,8 @@ int isingmc_create(const isingmc_config *cfg, isingmc_batch **out) {
     if (!cfg || !out || cfg->struct_size != sizeof(isingmc_config)) return refuse(ISINGMC_EINVAL, "bad config pointer or struct_size");
     *out = nullptr;
     if (const int rc = check_config(cfg)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return refuse(ISINGMC_ENODEVICE, "no HIP device available (this library has no CPU fallback)");
-    int dev = cfg->device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipSetDevice(dev) != hipSuccess) return refuse(ISINGMC_ENODEVICE, "hipSetDevice failed");
-    int max_lds = 0;
-    if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || max_lds <= 0) max_lds = 65536;
+    int dev = 0, max_lds = 0;
+    if (const char *why = probe_device(cfg->device, &dev, &max_lds)) return refuse(ISINGMC_ENODEVICE, why);
     DevBatch model; Tables tables; BatchPlan plan;
     if (const int rc = plan_config(cfg, (uint32_t)max_lds, model, tables, plan)) return rc;
     isingmc_batch *b = new isingmc_batch();
@@ -483,10 +478,6 @@ void isingmc_destroy(isingmc_batch *b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     pt_free(b);
-    for (void *p : b->allocs) (void)hipFree(p);
-    if (b->dev.rvb_prod) (void)hipFree(b->dev.rvb_prod);
-    if (b->dev.rvb_tbl) (void)hipFree(b->dev.rvb_tbl);
-    for (void *p : {(void *)b->rec, b->obs_groups, b->obs_series, b->obs_out, b->itime_buf}) if (p) (void)hipFree(p);
     for (hipEvent_t ev : b->evpool) (void)hipEventDestroy(ev);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);

@@ -165,15 +165,14 @@ static int prepare(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32
     if (rvb_g && !b->dev.rvb_tbl) { // the per-replica table scratch of RVB_G launches, on the first one (no fall-back when it cannot be had)
         const size_t words = rvb_tbl_words(b->dev);
         if (words > 0xFFFFFFFFull) { b->err = "RVB table scratch: more than 2^32 words per replica"; return ISINGMC_ECAPACITY; }
-        void *q = nullptr;
-        if (hipMalloc(&q, (size_t)b->dev.R * words * sizeof(uint32_t)) != hipSuccess) {
+        if (b->rvb_tbl.alloc((size_t)b->dev.R * words * sizeof(uint32_t)) != hipSuccess) {
             (void)hipGetLastError();
             char buf[160];
             snprintf(buf, sizeof buf, "RVB table scratch (ISINGMC_CFG_RVB_GLOBAL_TABLES): hipMalloc of %zu bytes failed", (size_t)b->dev.R * words * sizeof(uint32_t));
             b->err = buf;
             return ISINGMC_ENODEVICE;
         }
-        b->dev.rvb_tbl = (uint32_t *)q;
+        b->dev.rvb_tbl = b->rvb_tbl.as<uint32_t>();
     }
     if (rvb_g && rvb_global_lds_words(b->dev, lds_edges(b), 0) > b->lds_total_words) { b->err = "RVB scratch (ISINGMC_CFG_RVB_GLOBAL_TABLES): the spin-state bit arrays and the fixed RVB regions exceed LDS"; return ISINGMC_ENOTIMPL; }
     if (domask & SSE_DO_RVB) b->last_rvb_global = false;
@@ -192,10 +191,10 @@ static int prepare(isingmc_batch *b, const double *beta, uint64_t nsteps, uint32
     const size_t pstride = rvb_split_prod_stride(b->dev.Nb);
     const bool rvb_own_launch = c.split ? split_rvb_own_launch(b, A.domask) : rvb_alone(A.domask);
     if (rvb_own_launch && !b->rvb_global && b->rvb_split && c.chunk == 1 && pstride && b->dev.rvb_prod_cap < updates) {
-        if (b->dev.rvb_prod) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->dev.rvb_prod); b->dev.rvb_prod = nullptr; b->dev.rvb_prod_cap = 0; }
-        void *q = nullptr;
-        if (hipMalloc(&q, (size_t)b->dev.R * updates * pstride * sizeof(uint32_t)) == hipSuccess) { b->dev.rvb_prod = (uint32_t *)q; b->dev.rvb_prod_cap = updates; b->dev.rvb_prod_stride = (uint32_t)pstride; }
-        else { (void)hipGetLastError(); b->rvb_split = false; } // no room for the records: the fused kernel from now on
+        // (more attempts than rvb_prod_cap are more bytes than the block has: it grows)
+        if (b->rvb_prod.reserve((size_t)b->dev.R * updates * pstride * sizeof(uint32_t), b->stream) == hipSuccess) { b->dev.rvb_prod_cap = updates; b->dev.rvb_prod_stride = (uint32_t)pstride; }
+        else { (void)hipGetLastError(); b->dev.rvb_prod_cap = 0; b->rvb_split = false; } // no room for the records: the fused kernel from now on
+        b->dev.rvb_prod = b->rvb_prod.as<uint32_t>();
     }
     const size_t want_ev = c.split ? 4 * (size_t)(c.nsteps < MAX_TIMED ? c.nsteps : MAX_TIMED) : 0;
     while (b->evpool.size() < want_ev) { hipEvent_t ev; HIP_TRY(b, hipEventCreate(&ev)); b->evpool.push_back(ev); }

@@ -129,23 +129,6 @@ __global__ __launch_bounds__(256) void debug_counts_kernel(DevBatch B, uint32_t 
     if (threadIdx.x < 3) out[3 * r + threadIdx.x] = red[threadIdx.x];
 }
 
-// The plain accessors: null checks, hipSetDevice, `count` elements copied down or up (up: behind the stream's work where `drain` asks)
-template <typename T>
-static int copy_down(isingmc_batch *b, T *out, const T *src, size_t count) {
-    if (!b || !out) return ISINGMC_EINVAL;
-    HIP_TRY(b, hipSetDevice(b->device));
-    HIP_TRY(b, hipMemcpy(out, src, sizeof(T) * count, hipMemcpyDeviceToHost));
-    return ISINGMC_OK;
-}
-template <typename T>
-static int copy_up(isingmc_batch *b, T *dst, const T *in, size_t count, bool drain = false) {
-    if (!b || !in) return ISINGMC_EINVAL;
-    HIP_TRY(b, hipSetDevice(b->device));
-    if (drain) HIP_TRY(b, hipStreamSynchronize(b->stream));
-    HIP_TRY(b, hipMemcpy(dst, in, sizeof(T) * count, hipMemcpyHostToDevice));
-    return ISINGMC_OK;
-}
-
 // The launch behind isingmc_itime_groups (ngroups checked groups -> sum_all / sum_occ [R][ngroups]) and isingmc_bond_counts (ngroups = 0,
 // counts [R][Nb]): what LDS cannot serve is refused before anything is launched; then the pending flip bytes are brought in, the groups and
 // the variable -> groups lists built from them go up, itime_kernel runs on the batch's stream and the results come down.
@@ -167,13 +150,8 @@ static int itime_run(isingmc_batch *b, uint32_t ngroups, const uint32_t *group_s
     const size_t w_vars = (size_t)ngroups + 1, w_vstart = w_vars + nv, w_vgroups = w_vstart + N + 1, w_flip = w_vgroups + nv, w_fbits = w_flip + (ngroups + 3) / 4,
                  meta_words = ngroups ? w_fbits + 2 * (((size_t)ngroups + 63) / 64) : 0;
     const size_t bytes = o_meta + 4 * meta_words;
-    if (b->itime_buf_bytes < bytes || !b->itime_buf) {
-        if (b->itime_buf) { (void)hipStreamSynchronize(b->stream); (void)hipFree(b->itime_buf); b->itime_buf = nullptr; b->itime_buf_bytes = 0; }
-        void *q = nullptr;
-        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); b->err = "itime fold: allocation of the device scratch failed"; return ISINGMC_ENODEVICE; }
-        b->itime_buf = q; b->itime_buf_bytes = bytes;
-    }
-    char *buf = (char *)b->itime_buf;
+    if (b->itime_buf.reserve(bytes, b->stream) != hipSuccess) { (void)hipGetLastError(); b->err = "itime fold: allocation of the device scratch failed"; return ISINGMC_ENODEVICE; }
+    char *buf = b->itime_buf.as<char>();
     ItimeArgs A{};
     A.W = plan.W; A.hist_lds = plan.hist_lds; A.csr_lds = plan.csr_lds; A.nv = nv;
     std::vector<uint32_t> meta(meta_words); // (lives until the stream has been drained below)
@@ -238,10 +216,7 @@ int isingmc_set_accumulator_rows(isingmc_batch *b, uint32_t nrows, const uint32_
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     if (const int rc = pt_rows_are_slots(b, nrows, rows, &b->acc_follow_slots)) return rc;
     if (nrows != b->acc_rows) {
-        uint64_t *na = nullptr;
-        int rc = dalloc(b, &na, (size_t)nrows * 8);
-        if (rc) return rc;
-        b->dev.acc = na; // the previous table stays in the allocation list until destroy
+        if (const int rc = dalloc(b, &b->dev.acc, (size_t)nrows * 8, true, &b->acc)) return rc; // (the stream is idle: the previous table goes here)
         b->acc_rows = nrows;
     }
     HIP_TRY(b, hipMemcpy(b->d_acc_row, rows, sizeof(uint32_t) * b->dev.R, hipMemcpyHostToDevice));
@@ -270,17 +245,14 @@ int isingmc_get_state(isingmc_batch *b, uint32_t r, uint8_t *out) {
     const uint32_t r0 = r == UINT32_MAX ? 0 : r, cnt = r == UINT32_MAX ? b->dev.R : 1;
     std::vector<uint32_t> w((size_t)cnt * b->dev.nwords);
     if (const int rc = copy_down(b, w.data(), b->dev.state + (size_t)r0 * b->dev.nwords, w.size())) return rc;
-    for (uint32_t i = 0; i < cnt; ++i)
-        for (uint32_t v = 0; v < b->dev.N; ++v) out[(size_t)i * b->dev.N + v] = (w[(size_t)i * b->dev.nwords + (v >> 5)] >> (v & 31)) & 1u;
+    unpack_bits(w.data(), cnt, b->dev.N, b->dev.nwords, out);
     return ISINGMC_OK;
 }
 int isingmc_set_state(isingmc_batch *b, uint32_t r, const uint8_t *in) {
     if (!b || !in || (r != UINT32_MAX && r >= b->dev.R)) { if (b) b->err = "bad replica index"; return ISINGMC_EINVAL; }
     const uint32_t r0 = r == UINT32_MAX ? 0 : r, cnt = r == UINT32_MAX ? b->dev.R : 1;
-    std::vector<uint32_t> w((size_t)cnt * b->dev.nwords, 0u);
-    for (uint32_t i = 0; i < cnt; ++i)
-        for (uint32_t v = 0; v < b->dev.N; ++v)
-            if (in[(size_t)i * b->dev.N + v]) w[(size_t)i * b->dev.nwords + (v >> 5)] |= 1u << (v & 31);
+    std::vector<uint32_t> w((size_t)cnt * b->dev.nwords);
+    pack_bits(in, cnt, b->dev.N, b->dev.nwords, w.data());
     return copy_up(b, b->dev.state + (size_t)r0 * b->dev.nwords, w.data(), w.size());
 }
 
@@ -346,18 +318,16 @@ int isingmc_itime_magnetization(isingmc_batch *b, int64_t *sum_m, uint64_t *sum_
     HIP_TRY(b, hipSetDevice(b->device));
     { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
     const uint32_t R = b->dev.R;
-    long long *d1 = nullptr; unsigned long long *d2 = nullptr, *d3 = nullptr;
-    HIP_TRY(b, hipMalloc(&d1, sizeof(long long) * R));
-    if (hipMalloc(&d2, sizeof(unsigned long long) * R) != hipSuccess || hipMalloc(&d3, sizeof(unsigned long long) * R) != hipSuccess) {
-        (void)hipFree(d1); if (d2) (void)hipFree(d2);
+    DevBuf d1, d2, d3; // (per call: freed on every way out)
+    HIP_TRY(b, d1.alloc(sizeof(long long) * R));
+    if (d2.alloc(sizeof(unsigned long long) * R) != hipSuccess || d3.alloc(sizeof(unsigned long long) * R) != hipSuccess) {
         b->err = "itime_magnetization: allocation failed"; return ISINGMC_ENODEVICE;
     }
-    hipLaunchKernelGGL(itime_magnetization_kernel, dim3(R), dim3(256), 0, b->stream, b->dev, d1, d2, d3);
+    hipLaunchKernelGGL(itime_magnetization_kernel, dim3(R), dim3(256), 0, b->stream, b->dev, d1.as<long long>(), d2.as<unsigned long long>(), d3.as<unsigned long long>());
     hipError_t e = hipStreamSynchronize(b->stream);
-    if (e == hipSuccess) e = hipMemcpy(sum_m, d1, sizeof(long long) * R, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(sum_m2, d2, sizeof(unsigned long long) * R, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(sum_abs_m, d3, sizeof(unsigned long long) * R, hipMemcpyDeviceToHost);
-    (void)hipFree(d1); (void)hipFree(d2); (void)hipFree(d3);
+    if (e == hipSuccess) e = hipMemcpy(sum_m, d1.as<void>(), sizeof(long long) * R, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sum_m2, d2.as<void>(), sizeof(unsigned long long) * R, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sum_abs_m, d3.as<void>(), sizeof(unsigned long long) * R, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { b->err = std::string("itime_magnetization: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
     return ISINGMC_OK;
 }
@@ -377,12 +347,7 @@ int isingmc_itime_groups(isingmc_batch *b, uint32_t ngroups, const uint32_t *gro
     if (!b) return ISINGMC_EINVAL;
     if (!ngroups || !group_start || !group_vars) { b->err = "itime_groups: no observable groups"; return ISINGMC_EINVAL; }
     if (!sum_all && !sum_occ) { b->err = "itime_groups: no output buffer"; return ISINGMC_EINVAL; }
-    if (group_start[0] != 0u) { b->err = "itime_groups: group_start[0] must be 0"; return ISINGMC_EINVAL; }
-    for (uint32_t g = 0; g < ngroups; ++g)
-        if (group_start[g + 1] <= group_start[g]) { b->err = "itime_groups: every observable group needs at least one variable"; return ISINGMC_EINVAL; }
-    const uint32_t nv = group_start[ngroups];
-    for (uint32_t k = 0; k < nv; ++k)
-        if (group_vars[k] >= b->dev.N) { b->err = "itime_groups: group variable out of range"; return ISINGMC_EINVAL; }
+    if (const int rc = check_groups(b, "itime_groups", ngroups, group_start, group_vars, b->dev.N)) return rc;
     return itime_run(b, ngroups, group_start, group_vars, group_flip, sum_all, sum_occ, nullptr);
 }
 int isingmc_bond_counts(isingmc_batch *b, uint32_t *out) {
@@ -395,12 +360,11 @@ int isingmc_debug_counts(isingmc_batch *b, uint32_t *out) {
     if (!b || !out) return ISINGMC_EINVAL;
     HIP_TRY(b, hipSetDevice(b->device));
     { const int rcm = ensure_materialized(b); if (rcm) return rcm; }
-    uint32_t *d = nullptr;
-    HIP_TRY(b, hipMalloc((void **)&d, 12 * (size_t)b->dev.R));
-    hipLaunchKernelGGL(debug_counts_kernel, dim3(b->dev.R), dim3(256), 0, b->stream, b->dev, d);
-    hipError_t e = hipMemcpyAsync(out, d, 12 * (size_t)b->dev.R, hipMemcpyDeviceToHost, b->stream);
+    DevBuf d; // (per call)
+    HIP_TRY(b, d.alloc(12 * (size_t)b->dev.R));
+    hipLaunchKernelGGL(debug_counts_kernel, dim3(b->dev.R), dim3(256), 0, b->stream, b->dev, d.as<uint32_t>());
+    hipError_t e = hipMemcpyAsync(out, d.as<void>(), 12 * (size_t)b->dev.R, hipMemcpyDeviceToHost, b->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { b->err = std::string("debug_counts: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
     return ISINGMC_OK;
 }

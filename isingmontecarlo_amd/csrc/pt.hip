@@ -44,7 +44,7 @@ struct PtState {
     uint64_t seed = 0, step = 0, total_swaps = 0;
     std::vector<uint32_t> slot_of; // [R] global slot t*nchains + chain labelling local replica r
     std::vector<uint32_t> rid;     // [R] configuration identity (global id it was created with)
-    uint32_t *d_rid = nullptr, *d_ham_row = nullptr;
+    DevBuf d_rid, d_ham_row;       // [R] u32 each: the device copies of rid and of the batch's ham_row_host
     isingmc_pt_transport tr{};
     bool have_tr = false;
     // RCCL, loaded on first use
@@ -59,19 +59,19 @@ struct PtState {
     // decisions on the device (single rank, one Hamiltonian for all temperatures): labels, betas per replica and the swap count live
     // in device memory; the host mirrors (slot_of) are refreshed on demand
     bool dev_decide = false, host_stale = false;
-    uint32_t *d_slot_of = nullptr, *d_at = nullptr, *d_result = nullptr; // d_result: [0] swaps of the last step, [1] error flag
-    double *d_betas = nullptr, *d_beta_r = nullptr;
-    unsigned long long *d_total = nullptr; // total swaps since isingmc_pt_create / set_state
-    uint32_t *d_items = nullptr; // [3 * nchains] accepted boundary swaps of one turn: (replica, word offset, cutoff)
-    uint32_t *d_small = nullptr; // [4][nchains] staging of the boundary operator counts / cutoffs on the device (RCCL path)
+    DevBuf d_slot_of, d_at, d_result; // u32: [R], [R]; d_result: [0] swaps of the last step, [1] error flag
+    DevBuf d_betas, d_beta_r;         // double: [ntemps], [R]
+    DevBuf d_total;                   // unsigned long long: total swaps since isingmc_pt_create / set_state
+    DevBuf d_items; // u32 [3 * nchains] accepted boundary swaps of one turn: (replica, word offset, cutoff)
+    DevBuf d_small; // u32 [4][nchains] staging of the boundary operator counts / cutoffs on the device (RCCL path)
     // different Hamiltonians per temperature (per-replica couplings)
     bool hams_differ = false;
     std::vector<double> ham;      // [nchains + R + nchains][E + 2] Hamiltonian row (pt_ham_row) of local slot ls at row nchains + ls; the halo
                                   // rows are the lower neighbour's last and the upper neighbour's first temperature
-    uint32_t *d_counts = nullptr; // [R][Nb] bond counts (only when hams_differ)
+    DevBuf d_counts;              // u32 [R][Nb] bond counts (only when hams_differ)
     PtSide side[2];
     // configuration exchange
-    uint32_t *d_pack_s = nullptr, *d_pack_r = nullptr;
+    DevBuf d_pack_s, d_pack_r;    // u32 [pack_cap_words] each
     size_t pack_cap_words = 0;
     std::vector<uint32_t> h_pack_s, h_pack_r;
 };
@@ -80,9 +80,6 @@ void sse::pt_free(isingmc_batch *b) {
     if (!b->pt) return;
     PtState *P = b->pt;
     if (P->comm && P->p_destroy) (void)P->p_destroy(P->comm);
-    for (void *q : {(void *)P->d_rid, (void *)P->d_ham_row, (void *)P->d_small, (void *)P->d_counts, (void *)P->d_pack_s, (void *)P->d_pack_r, (void *)P->d_items,
-                    (void *)P->d_slot_of, (void *)P->d_at, (void *)P->d_result, (void *)P->d_betas, (void *)P->d_beta_r, (void *)P->d_total})
-        if (q) (void)hipFree(q);
     delete P;
     b->pt = nullptr;
 }
@@ -212,9 +209,9 @@ static int pt_sendrecv(isingmc_batch *b, int peer, const uint32_t *dev_s, uint32
 static int pt_allreduce_max(isingmc_batch *b, std::vector<uint32_t> &v) {
     PtState *P = b->pt;
     if (P->comm) {
-        HIP_TRY(b, hipMemcpyAsync(P->d_small, v.data(), 4 * v.size(), hipMemcpyHostToDevice, b->stream));
-        if (P->p_allreduce(P->d_small, P->d_small, v.size(), (int)ncclUint32, (int)ncclMax, P->comm, b->stream)) { b->err = "ncclAllReduce failed"; return ISINGMC_ENODEVICE; }
-        HIP_TRY(b, hipMemcpyAsync(v.data(), P->d_small, 4 * v.size(), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(b, hipMemcpyAsync(P->d_small.as<uint32_t>(), v.data(), 4 * v.size(), hipMemcpyHostToDevice, b->stream));
+        if (P->p_allreduce(P->d_small.as<uint32_t>(), P->d_small.as<uint32_t>(), v.size(), (int)ncclUint32, (int)ncclMax, P->comm, b->stream)) { b->err = "ncclAllReduce failed"; return ISINGMC_ENODEVICE; }
+        HIP_TRY(b, hipMemcpyAsync(v.data(), P->d_small.as<uint32_t>(), 4 * v.size(), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(b, hipStreamSynchronize(b->stream));
     } else if (P->tr.allreduce_max_u32(P->tr.ctx, v.data(), v.size())) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
     return ISINGMC_OK;
@@ -287,11 +284,11 @@ static int pt_upload_labels(isingmc_batch *b) {
     const unsigned long long tot = P->total_swaps;
     const uint32_t zero[2] = {0u, 0u};
     HIP_TRY(b, hipStreamSynchronize(b->stream));
-    HIP_TRY(b, hipMemcpy(P->d_slot_of, P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(P->d_at, at.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(P->d_beta_r, br.data(), 8 * (size_t)R, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(P->d_total, &tot, 8, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(P->d_result, zero, 8, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(P->d_slot_of.as<uint32_t>(), P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(P->d_at.as<uint32_t>(), at.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(P->d_beta_r.as<double>(), br.data(), 8 * (size_t)R, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(P->d_total.as<unsigned long long>(), &tot, 8, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(P->d_result.as<uint32_t>(), zero, 8, hipMemcpyHostToDevice));
     P->host_stale = false;
     return ISINGMC_OK;
 }
@@ -302,9 +299,9 @@ static int pt_sync_host(isingmc_batch *b) {
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     unsigned long long tot = 0;
     uint32_t res[2] = {0u, 0u};
-    HIP_TRY(b, hipMemcpy(P->slot_of.data(), P->d_slot_of, 4 * (size_t)b->dev.R, hipMemcpyDeviceToHost));
-    HIP_TRY(b, hipMemcpy(&tot, P->d_total, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(b, hipMemcpy(res, P->d_result, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(b, hipMemcpy(P->slot_of.data(), P->d_slot_of.as<uint32_t>(), 4 * (size_t)b->dev.R, hipMemcpyDeviceToHost));
+    HIP_TRY(b, hipMemcpy(&tot, P->d_total.as<unsigned long long>(), 8, hipMemcpyDeviceToHost));
+    HIP_TRY(b, hipMemcpy(res, P->d_result.as<uint32_t>(), 8, hipMemcpyDeviceToHost));
     P->total_swaps = tot;
     P->host_stale = false;
     if (res[1]) { b->err = "cutoff exceeds capacity"; return ISINGMC_ECAPACITY; }
@@ -329,26 +326,26 @@ int isingmc_pt_create(isingmc_batch *b, const isingmc_pt_layout *lay) {
     const uint32_t R = b->dev.R;
     P->slot_of.resize(R); P->rid.resize(R);
     for (uint32_t r = 0; r < R; ++r) { P->slot_of[r] = P->rank * R + r; P->rid[r] = b->dev.replica_offset + r; }
-    HIP_TRY(b, hipMalloc((void **)&P->d_rid, 4 * (size_t)R));
-    HIP_TRY(b, hipMemcpy(P->d_rid, P->rid.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
-    b->dev.rid = P->d_rid;
-    HIP_TRY(b, hipMalloc((void **)&P->d_small, 4 * 4 * (size_t)(P->nchains * 2 + 2)));
-    HIP_TRY(b, hipMalloc((void **)&P->d_items, 4 * 3 * (size_t)P->nchains));
+    HIP_TRY(b, P->d_rid.alloc(4 * (size_t)R));
+    HIP_TRY(b, hipMemcpy(P->d_rid.as<uint32_t>(), P->rid.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+    b->dev.rid = P->d_rid.as<uint32_t>();
+    HIP_TRY(b, P->d_small.alloc(4 * 4 * (size_t)(P->nchains * 2 + 2)));
+    HIP_TRY(b, P->d_items.alloc(4 * 3 * (size_t)P->nchains));
     P->side[0].peer = P->rank > 0 ? (int)P->rank - 1 : -1;
     P->side[1].peer = P->rank + 1 < P->world ? (int)P->rank + 1 : -1;
     for (PtSide &S : P->side) { S.sent.resize(P->nchains); S.got.resize(P->nchains); S.items.resize(3 * (size_t)P->nchains); }
     P->pack_cap_words = (size_t)P->nchains * (PT_HDR + b->dev.nwords + 2 * SSE_MAX_CHUNKS + b->dev.cap);
-    HIP_TRY(b, hipMalloc((void **)&P->d_pack_s, 4 * P->pack_cap_words));
-    HIP_TRY(b, hipMalloc((void **)&P->d_pack_r, 4 * P->pack_cap_words));
+    HIP_TRY(b, P->d_pack_s.alloc(4 * P->pack_cap_words));
+    HIP_TRY(b, P->d_pack_r.alloc(4 * P->pack_cap_words));
     if (b->per_replica_J) {
         // different Hamiltonians between temperatures: the bond-table row belongs to the slot; neighbours' boundary rows once
         P->hams_differ = true;
         b->ham_row_host.resize(R);
         for (uint32_t r = 0; r < R; ++r) b->ham_row_host[r] = r;
-        HIP_TRY(b, hipMalloc((void **)&P->d_ham_row, 4 * (size_t)R));
-        HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
-        b->dev.ham_row = P->d_ham_row;
-        HIP_TRY(b, hipMalloc((void **)&P->d_counts, 4 * (size_t)R * b->dev.Nb));
+        HIP_TRY(b, P->d_ham_row.alloc(4 * (size_t)R));
+        HIP_TRY(b, hipMemcpy(P->d_ham_row.as<uint32_t>(), b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+        b->dev.ham_row = P->d_ham_row.as<uint32_t>();
+        HIP_TRY(b, P->d_counts.alloc(4 * (size_t)R * b->dev.Nb));
         const uint32_t K = P->nchains, HS = b->dev.E + 2; // a Hamiltonian row: [E] couplings, Gamma, h
         const size_t edge = (size_t)K * HS;               // one temperature's rows: what a neighbour needs
         P->ham.assign((size_t)(R + 2 * K) * HS, 0.0);
@@ -359,13 +356,13 @@ int isingmc_pt_create(isingmc_batch *b, const isingmc_pt_layout *lay) {
             if (P->side[s].peer >= 0 && P->tr.sendrecv(P->tr.ctx, P->side[s].peer, P->ham.data() + mine[s], 8 * edge, P->ham.data() + halo[s], 8 * edge)) { b->err = "tempering transport failed"; return ISINGMC_EINVAL; }
     }
     if (P->world == 1 && !P->hams_differ) { // every pair is interior and weighs one Hamiltonian: the decisions run on the device
-        HIP_TRY(b, hipMalloc((void **)&P->d_slot_of, 4 * (size_t)R));
-        HIP_TRY(b, hipMalloc((void **)&P->d_at, 4 * (size_t)R));
-        HIP_TRY(b, hipMalloc((void **)&P->d_result, 8));
-        HIP_TRY(b, hipMalloc((void **)&P->d_betas, 8 * (size_t)P->ntemps));
-        HIP_TRY(b, hipMalloc((void **)&P->d_beta_r, 8 * (size_t)R));
-        HIP_TRY(b, hipMalloc((void **)&P->d_total, 8));
-        HIP_TRY(b, hipMemcpy(P->d_betas, P->betas.data(), 8 * (size_t)P->ntemps, hipMemcpyHostToDevice));
+        HIP_TRY(b, P->d_slot_of.alloc(4 * (size_t)R));
+        HIP_TRY(b, P->d_at.alloc(4 * (size_t)R));
+        HIP_TRY(b, P->d_result.alloc(8));
+        HIP_TRY(b, P->d_betas.alloc(8 * (size_t)P->ntemps));
+        HIP_TRY(b, P->d_beta_r.alloc(8 * (size_t)R));
+        HIP_TRY(b, P->d_total.alloc(8));
+        HIP_TRY(b, hipMemcpy(P->d_betas.as<double>(), P->betas.data(), 8 * (size_t)P->ntemps, hipMemcpyHostToDevice));
         const int rcu = pt_upload_labels(b);
         if (rcu) return rcu;
         P->dev_decide = true;
@@ -391,7 +388,7 @@ int isingmc_pt_timesteps(isingmc_batch *b, uint64_t t, uint32_t sampling_freq, u
     if (!b || !b->pt) { if (b) b->err = "isingmc_pt_create first"; return ISINGMC_EINVAL; }
     PtState *P = b->pt;
     if (P->dev_decide) {
-        b->beta_dev = P->d_beta_r;
+        b->beta_dev = P->d_beta_r.as<double>();
         const int rc = isingmc_timesteps(b, t, nullptr, sampling_freq, flags);
         b->beta_dev = nullptr;
         return rc;
@@ -469,10 +466,10 @@ int isingmc_pt_set_state(isingmc_batch *b, const uint32_t *slot_of_replica, cons
     }
     HIP_TRY(b, hipSetDevice(b->device));
     for (uint32_t r = 0; r < R; ++r) { P->slot_of[r] = slot_of_replica[r]; P->rid[r] = config_id_of_replica[r]; }
-    HIP_TRY(b, hipMemcpy(P->d_rid, P->rid.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(P->d_rid.as<uint32_t>(), P->rid.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
     if (P->hams_differ) {
         for (uint32_t r = 0; r < R; ++r) b->ham_row_host[r] = P->slot_of[r] - lo;
-        HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(P->d_ham_row.as<uint32_t>(), b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
     }
     P->step = step; P->total_swaps = total_swaps;
     if (b->acc_follow_slots) HIP_TRY(b, hipMemcpy(b->d_acc_row, P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
@@ -489,7 +486,7 @@ static int pt_step_on_device(isingmc_batch *b, uint64_t *nswaps) {
     const uint32_t K = P->nchains;
     if (P->ntemps <= 1) { P->step++; return ISINGMC_OK; }
     PtDev D{};
-    D.slot_of = P->d_slot_of; D.at = P->d_at; D.result = P->d_result; D.betas = P->d_betas; D.beta_r = P->d_beta_r; D.total = P->d_total;
+    D.slot_of = P->d_slot_of.as<uint32_t>(); D.at = P->d_at.as<uint32_t>(); D.result = P->d_result.as<uint32_t>(); D.betas = P->d_betas.as<double>(); D.beta_r = P->d_beta_r.as<double>(); D.total = P->d_total.as<unsigned long long>();
     D.acc_row = b->acc_follow_slots ? b->d_acc_row : nullptr; // per-slot accumulators (isingmc_set_accumulator_rows with the slots) follow the labels
     D.K = K; D.T = P->ntemps; D.seed = P->seed; D.step = P->step;
     hipLaunchKernelGGL(pt_decide_kernel, dim3(1), dim3(K < 256 ? ((K + 63) / 64) * 64 : 256), 0, b->stream, b->dev, D);
@@ -499,7 +496,7 @@ static int pt_step_on_device(isingmc_batch *b, uint64_t *nswaps) {
     if (nswaps) { // one small read-back
         uint32_t res[2] = {0u, 0u};
         HIP_TRY(b, hipStreamSynchronize(b->stream));
-        HIP_TRY(b, hipMemcpy(res, P->d_result, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(b, hipMemcpy(res, P->d_result.as<uint32_t>(), 8, hipMemcpyDeviceToHost));
         if (res[1]) { b->err = "cutoff exceeds capacity"; return ISINGMC_ECAPACITY; }
         *nswaps += res[0];
     }
@@ -546,9 +543,9 @@ static int pt_equalise_cutoffs(isingmc_batch *b, PtHostStep &S) {
 // bond counts of every local configuration (again in the second phase: a boundary swap of the first one replaced configurations)
 static int pt_bond_counts(isingmc_batch *b, PtHostStep &S) {
     const uint32_t R = b->dev.R;
-    hipLaunchKernelGGL(pt_bond_count_kernel, dim3(R), dim3(256), 0, b->stream, b->dev, b->pt->d_counts);
+    hipLaunchKernelGGL(pt_bond_count_kernel, dim3(R), dim3(256), 0, b->stream, b->dev, b->pt->d_counts.as<uint32_t>());
     S.counts.resize((size_t)R * b->dev.Nb);
-    HIP_TRY(b, hipMemcpyAsync(S.counts.data(), b->pt->d_counts, 4 * S.counts.size(), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipMemcpyAsync(S.counts.data(), b->pt->d_counts.as<uint32_t>(), 4 * S.counts.size(), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     return ISINGMC_OK;
 }
@@ -577,7 +574,7 @@ static int pt_exchange_counts(isingmc_batch *b, const PtHostStep &S) {
             P->side[s].sent[k] = {S.n[r], 0u, P->hams_differ ? S.rel[r] : 1.0};
         }
     const size_t words = 4 * (size_t)K;
-    uint32_t *ds = P->d_small, *dr = P->d_small + words;
+    uint32_t *ds = P->d_small.as<uint32_t>(), *dr = P->d_small.as<uint32_t>() + words;
     for (int turn = 0; turn < 2; ++turn) {
         PtSide &N = pt_turn_side(P, turn);
         if (N.peer < 0) continue;
@@ -619,20 +616,20 @@ static int pt_move_configurations(isingmc_batch *b) {
         const PtSide &N = pt_turn_side(P, turn);
         if (N.peer < 0 || N.nitems == 0) continue;
         const size_t words = N.words;
-        uint32_t *d_it = P->d_items; // (at most one item per chain and turn)
+        uint32_t *d_it = P->d_items.as<uint32_t>(); // (at most one item per chain and turn)
         HIP_TRY(b, hipMemcpyAsync(d_it, N.items.data(), 4 * 3 * (size_t)N.nitems, hipMemcpyHostToDevice, b->stream));
-        hipLaunchKernelGGL(pt_pack_kernel, dim3(N.nitems), dim3(256), 0, b->stream, b->dev, P->d_rid, d_it, P->d_pack_s);
+        hipLaunchKernelGGL(pt_pack_kernel, dim3(N.nitems), dim3(256), 0, b->stream, b->dev, P->d_rid.as<uint32_t>(), d_it, P->d_pack_s.as<uint32_t>());
         if (!P->comm) {
             P->h_pack_s.resize(words); P->h_pack_r.resize(words);
-            HIP_TRY(b, hipMemcpyAsync(P->h_pack_s.data(), P->d_pack_s, 4 * words, hipMemcpyDeviceToHost, b->stream));
+            HIP_TRY(b, hipMemcpyAsync(P->h_pack_s.data(), P->d_pack_s.as<uint32_t>(), 4 * words, hipMemcpyDeviceToHost, b->stream));
             HIP_TRY(b, hipStreamSynchronize(b->stream));
         }
-        if (const int rc = pt_sendrecv(b, N.peer, P->d_pack_s, P->d_pack_r, P->h_pack_s.data(), P->h_pack_r.data(), words)) return rc;
-        if (!P->comm) HIP_TRY(b, hipMemcpyAsync(P->d_pack_r, P->h_pack_r.data(), 4 * words, hipMemcpyHostToDevice, b->stream));
-        hipLaunchKernelGGL(pt_unpack_kernel, dim3(N.nitems), dim3(256), 0, b->stream, b->dev, P->d_rid, d_it, P->d_pack_r);
+        if (const int rc = pt_sendrecv(b, N.peer, P->d_pack_s.as<uint32_t>(), P->d_pack_r.as<uint32_t>(), P->h_pack_s.data(), P->h_pack_r.data(), words)) return rc;
+        if (!P->comm) HIP_TRY(b, hipMemcpyAsync(P->d_pack_r.as<uint32_t>(), P->h_pack_r.data(), 4 * words, hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(pt_unpack_kernel, dim3(N.nitems), dim3(256), 0, b->stream, b->dev, P->d_rid.as<uint32_t>(), d_it, P->d_pack_r.as<uint32_t>());
         HIP_TRY(b, hipStreamSynchronize(b->stream));
     }
-    if (P->side[0].nitems || P->side[1].nitems) HIP_TRY(b, hipMemcpy(P->rid.data(), P->d_rid, 4 * (size_t)b->dev.R, hipMemcpyDeviceToHost));
+    if (P->side[0].nitems || P->side[1].nitems) HIP_TRY(b, hipMemcpy(P->rid.data(), P->d_rid.as<uint32_t>(), 4 * (size_t)b->dev.R, hipMemcpyDeviceToHost));
     return ISINGMC_OK;
 }
 
@@ -642,7 +639,7 @@ static int pt_finish(isingmc_batch *b, uint64_t swaps, uint64_t *nswaps) {
     const uint32_t R = b->dev.R;
     if (P->hams_differ) {
         for (uint32_t r = 0; r < R; ++r) b->ham_row_host[r] = P->slot_of[r] - P->rank * R;
-        HIP_TRY(b, hipMemcpy(P->d_ham_row, b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(P->d_ham_row.as<uint32_t>(), b->ham_row_host.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
     }
     if (b->acc_follow_slots) HIP_TRY(b, hipMemcpy(b->d_acc_row, P->slot_of.data(), 4 * (size_t)R, hipMemcpyHostToDevice));
     P->step++;

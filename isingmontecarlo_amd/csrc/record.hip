@@ -13,7 +13,7 @@ using namespace sse;
 hipError_t sse::record_append(isingmc_batch *b) {
     const size_t row = (size_t)b->dev.R * b->dev.nwords;
     if (b->rec_count >= b->rec_cap) return hipErrorInvalidValue;
-    const hipError_t e = hipMemcpyAsync(b->rec + (size_t)b->rec_count * row, b->dev.state, row * sizeof(uint32_t), hipMemcpyDeviceToDevice, b->stream);
+    const hipError_t e = hipMemcpyAsync(b->rec.as<uint32_t>() + (size_t)b->rec_count * row, b->dev.state, row * sizeof(uint32_t), hipMemcpyDeviceToDevice, b->stream);
     if (e == hipSuccess) b->rec_count++;
     return e;
 }
@@ -25,14 +25,9 @@ static int rec_fail_alloc(isingmc_batch *b, const char *what, size_t bytes) {
     b->err = buf;
     return ISINGMC_ENODEVICE;
 }
-// a scratch buffer of at least `bytes`, kept for the next call (the stream is drained before an old one is freed)
-static int rec_grow(isingmc_batch *b, void **p, size_t *have, size_t bytes, const char *what) {
-    if (*have >= bytes && *p) return ISINGMC_OK;
-    if (*p) { (void)hipStreamSynchronize(b->stream); (void)hipFree(*p); *p = nullptr; *have = 0; }
-    void *q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) return rec_fail_alloc(b, what, bytes);
-    *p = q; *have = bytes;
-    return ISINGMC_OK;
+// a scratch buffer of at least `bytes`, kept for the next call
+static int rec_grow(isingmc_batch *b, DevBuf &buf, size_t bytes, const char *what) {
+    return buf.reserve(bytes, b->stream) == hipSuccess ? ISINGMC_OK : rec_fail_alloc(b, what, bytes);
 }
 static int rec_range(isingmc_batch *b, uint32_t first, uint32_t count) {
     if (!b->rec) { b->err = "no sample record attached (isingmc_record_attach)"; return ISINGMC_EINVAL; }
@@ -45,12 +40,8 @@ static int rec_make_series(isingmc_batch *b, uint32_t ngroups, const uint32_t *g
                            uint32_t first, uint32_t count) {
     if (!ngroups || !group_start || !group_vars) { b->err = "sample record: no observable groups"; return ISINGMC_EINVAL; }
     if (const int rc = rec_range(b, first, count)) return rc;
-    if (group_start[0] != 0u) { b->err = "sample record: group_start[0] must be 0"; return ISINGMC_EINVAL; }
-    for (uint32_t g = 0; g < ngroups; ++g)
-        if (group_start[g + 1] <= group_start[g]) { b->err = "sample record: every observable group needs at least one variable"; return ISINGMC_EINVAL; }
+    if (const int rc = check_groups(b, "sample record", ngroups, group_start, group_vars, b->dev.N)) return rc;
     const uint32_t nv = group_start[ngroups];
-    for (uint32_t k = 0; k < nv; ++k)
-        if (group_vars[k] >= b->dev.N) { b->err = "sample record: group variable out of range"; return ISINGMC_EINVAL; }
     if (4 * obs_series_lds_words(b->dev.nwords) > 4 * b->lds_total_words) {
         b->err = "sample record: 64 state rows of this model exceed LDS (record_series_kernel stages them there)";
         return ISINGMC_ENOTIMPL;
@@ -58,16 +49,16 @@ static int rec_make_series(isingmc_batch *b, uint32_t ngroups, const uint32_t *g
     HIP_TRY(b, hipSetDevice(b->device));
     // groups: [ngroups + 1] starts, [nv] variables, [ngroups] flip bytes
     const size_t o_vars = (size_t)(ngroups + 1) * 4, o_flip = o_vars + (size_t)nv * 4;
-    if (const int rc = rec_grow(b, &b->obs_groups, &b->obs_groups_bytes, o_flip + ngroups, "observable groups")) return rc;
+    if (const int rc = rec_grow(b, b->obs_groups, o_flip + ngroups, "observable groups")) return rc;
     const size_t Tw = (count + 31u) / 32u;
-    if (const int rc = rec_grow(b, &b->obs_series, &b->obs_series_bytes, (size_t)b->dev.R * ngroups * Tw * 4, "bit series")) return rc;
-    char *gbuf = (char *)b->obs_groups;
+    if (const int rc = rec_grow(b, b->obs_series, (size_t)b->dev.R * ngroups * Tw * 4, "bit series")) return rc;
+    char *gbuf = b->obs_groups.as<char>();
     HIP_TRY(b, hipMemcpyAsync(gbuf, group_start, o_vars, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(b, hipMemcpyAsync(gbuf + o_vars, group_vars, (size_t)nv * 4, hipMemcpyHostToDevice, b->stream));
     if (group_flip) HIP_TRY(b, hipMemcpyAsync(gbuf + o_flip, group_flip, ngroups, hipMemcpyHostToDevice, b->stream));
     ObsGroups G{ngroups, (const uint32_t *)gbuf, (const uint32_t *)(gbuf + o_vars), group_flip ? (const uint8_t *)(gbuf + o_flip) : nullptr};
-    const uint32_t *rows = b->rec + (size_t)first * b->dev.R * b->dev.nwords;
-    const hipError_t e = launch_record_series(b->stream, rows, b->dev.R, b->dev.nwords, count, G, (uint32_t *)b->obs_series);
+    const uint32_t *rows = b->rec.as<uint32_t>() + (size_t)first * b->dev.R * b->dev.nwords;
+    const hipError_t e = launch_record_series(b->stream, rows, b->dev.R, b->dev.nwords, count, G, b->obs_series.as<uint32_t>());
     if (e != hipSuccess) { b->err = std::string("record_series launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
     return ISINGMC_OK;
 }
@@ -78,13 +69,12 @@ int isingmc_record_attach(isingmc_batch *b, uint32_t capacity) {
     if (!b) return ISINGMC_EINVAL;
     if (capacity > (1u << 20)) { b->err = "sample record: capacity above 2^20 samples"; return ISINGMC_EINVAL; }
     HIP_TRY(b, hipSetDevice(b->device));
-    if (b->rec) { HIP_TRY(b, hipStreamSynchronize(b->stream)); (void)hipFree(b->rec); b->rec = nullptr; }
+    if (b->rec) { HIP_TRY(b, hipStreamSynchronize(b->stream)); b->rec.reset(); }
     b->rec_cap = b->rec_count = 0;
     if (capacity == 0) return ISINGMC_OK;
     const size_t bytes = (size_t)capacity * b->dev.R * b->dev.nwords * sizeof(uint32_t);
-    void *q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) return rec_fail_alloc(b, "record", bytes);
-    b->rec = (uint32_t *)q; b->rec_cap = capacity;
+    if (b->rec.alloc(bytes) != hipSuccess) return rec_fail_alloc(b, "record", bytes);
+    b->rec_cap = capacity;
     return ISINGMC_OK;
 }
 int isingmc_record_count(const isingmc_batch *b, uint32_t *count, uint32_t *capacity) {
@@ -111,13 +101,10 @@ int isingmc_record_read(isingmc_batch *b, uint32_t first, uint32_t count, uint32
     std::vector<uint32_t> w(std::min<size_t>(piece, count) * per_row);
     for (uint32_t t0 = 0; t0 < count; t0 += piece) {
         const uint32_t nt = count - t0 < piece ? count - t0 : piece;
-        const uint32_t *src = b->rec + ((size_t)(first + t0) * R + r0) * nw;
+        const uint32_t *src = b->rec.as<uint32_t>() + ((size_t)(first + t0) * R + r0) * nw;
         HIP_TRY(b, hipMemcpy2DAsync(w.data(), per_row * 4, src, (size_t)R * nw * 4, per_row * 4, nt, hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(b, hipStreamSynchronize(b->stream));
-        for (size_t i = 0; i < (size_t)nt * cnt; ++i) {
-            uint8_t *o = out + ((size_t)t0 * cnt + i) * N;
-            for (uint32_t v = 0; v < N; ++v) o[v] = (w[i * nw + (v >> 5)] >> (v & 31)) & 1u;
-        }
+        unpack_bits(w.data(), (size_t)nt * cnt, N, nw, out + (size_t)t0 * cnt * N);
     }
     return ISINGMC_OK;
 }
@@ -128,7 +115,7 @@ int isingmc_record_series(isingmc_batch *b, uint32_t ngroups, const uint32_t *gr
     if (!out_bits) { b->err = "sample record: no output buffer"; return ISINGMC_EINVAL; }
     if (const int rc = rec_make_series(b, ngroups, group_start, group_vars, group_flip, first, count)) return rc;
     const size_t bytes = (size_t)b->dev.R * ngroups * ((count + 31u) / 32u) * 4;
-    HIP_TRY(b, hipMemcpyAsync(out_bits, b->obs_series, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipMemcpyAsync(out_bits, b->obs_series.as<void>(), bytes, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     return ISINGMC_OK;
 }
@@ -142,10 +129,10 @@ int isingmc_record_autocorrelation(isingmc_batch *b, uint32_t ngroups, const uin
     }
     if (const int rc = rec_make_series(b, ngroups, group_start, group_vars, nullptr, first, count)) return rc;
     const size_t bytes = (size_t)b->dev.R * count * sizeof(double);
-    if (const int rc = rec_grow(b, &b->obs_out, &b->obs_out_bytes, bytes, "autocorrelations")) return rc;
-    const hipError_t e = launch_bit_autocorr(b->stream, (const uint32_t *)b->obs_series, b->dev.R, ngroups, count, (double *)b->obs_out);
+    if (const int rc = rec_grow(b, b->obs_out, bytes, "autocorrelations")) return rc;
+    const hipError_t e = launch_bit_autocorr(b->stream, b->obs_series.as<uint32_t>(), b->dev.R, ngroups, count, b->obs_out.as<double>());
     if (e != hipSuccess) { b->err = std::string("bit_autocorr launch: ") + hipGetErrorString(e); return ISINGMC_ENODEVICE; }
-    HIP_TRY(b, hipMemcpyAsync(out, b->obs_out, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipMemcpyAsync(out, b->obs_out.as<void>(), bytes, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     return ISINGMC_OK;
 }

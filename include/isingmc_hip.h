@@ -569,6 +569,52 @@ int isingmc_classical_host_pt_run_overlaps(const isingmc_classical_config *cfg, 
                                            uint32_t *temp_of, uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts,
                                            double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl);
 
+/* ---- isoenergetic cluster moves (Houdayer moves) between the copies of a group; the rule is stated once in csrc/classical_icm_rule.h ----
+ * With a window t_first <= t < t_last of ladder indices attached, a round with cluster moves forms M = K / 2 disjoint pairs of copies in
+ * every group (pair m is the copies (o + 2 m) mod K and (o + 2 m + 1) mod K, o = pt_step mod K) and, at every temperature of the window,
+ * takes the two states that hold it, picks one of the variables in which they differ with one Philox draw (tag SSE_TAG_CLASSICAL_ICM),
+ * and flips in both states the connected component of that variable among the differing variables, over the entries of the edge list
+ * (any J).  The move is rejection-free and leaves E_A + E_B and both overlaps as they are.  It runs after the round's overlap
+ * measurement and before its tempering step, so the E and M series of such a round hold the values after the moves.
+ * Counts, uint64 [G][M][T] each, cumulative since attach or reset: moves, empty (the two states were equal) and size_sum (the sizes of
+ * the flipped clusters added up); zero outside the window.
+ * ISINGMC_EINVAL: overlaps (or tempering) not attached; t_last > T; an empty or reversed window; the other cluster-move calls before
+ * icm_attach.  ISINGMC_ENOTIMPL: the three bit sets of one item exceed the LDS of a workgroup (the message names the largest N). */
+/* Needs isingmc_classical_overlap_attach.  t_last == 0 means T; t_first == t_last == UINT32_MAX detaches.  Allocates and zeroes
+ * the counts.  isingmc_classical_pt_attach and isingmc_classical_overlap_attach detach the cluster moves. */
+int isingmc_classical_icm_attach(isingmc_classical *g, uint32_t t_first, uint32_t t_last);
+/* the window as attached (either may be NULL) */
+int isingmc_classical_icm_window(isingmc_classical *g, uint32_t *t_first, uint32_t *t_last);
+/* The loop of isingmc_classical_pt_run_overlaps with the cluster-move launch in front of the tempering launch of every round.
+ * measure != 0: the overlaps are measured as in pt_run_overlaps; measure == 0: they are not, and q_out and ql_out are ignored. */
+int isingmc_classical_pt_run_icm(isingmc_classical *g, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
+                                 double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out, uint32_t measure);
+/* read (each may be NULL), restore from a checkpoint (all non-NULL), zero */
+int isingmc_classical_icm_counts(isingmc_classical *g, uint64_t *moves, uint64_t *empty, uint64_t *size_sum);
+int isingmc_classical_icm_set_counts(isingmc_classical *g, const uint64_t *moves, const uint64_t *empty, const uint64_t *size_sum);
+int isingmc_classical_icm_reset(isingmc_classical *g);
+/* Host-only, device-free: the cluster-move launch of a model of nvars variables on a device whose workgroups have lds_bytes of LDS.
+ * out[0] waves per workgroup (4, 2 or 1), out[1] the dynamic LDS in words, out[2] the words of one wave's area (three bit sets),
+ * out[3] the most variables that launch takes at all.  isingmc_classical_icm_launch_plan: the same of an attached handle. */
+int isingmc_classical_icm_plan(uint32_t nvars, uint32_t lds_bytes, uint32_t out[4]);
+int isingmc_classical_icm_launch_plan(isingmc_classical *g, uint32_t out[4]);
+/* For tests and A-B timing: run the cluster-move launch with fewer waves per workgroup than planned (1, 2 or 4, at most the plan's;
+ * 0 restores the plan).  The moves do not depend on it. */
+int isingmc_classical_icm_force_waves(isingmc_classical *g, uint32_t waves);
+/* Host-only, a device-free test entry: isingmc_classical_host_pt_run_overlaps with cluster moves in the window [t_first, t_last) in
+ * every round, by the sequential rule on the CPU and with icm_attach's argument checks.  measure as in pt_run_icm; moves, empty and
+ * size_sum [G][M][T] are added to in place and may be NULL. */
+int isingmc_classical_host_pt_run_icm(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint32_t ncopies, uint64_t rounds, uint64_t steps,
+                                      uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
+                                      uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out,
+                                      int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl, uint32_t measure, uint32_t t_first, uint32_t t_last,
+                                      uint64_t *moves, uint64_t *empty, uint64_t *size_sum);
+/* Host-only, a device-free test entry: the cluster of one move.  state_a and state_b [N] bytes (of cfg's graph; its couplings are not
+ * read); the seed is the rank-th variable, in increasing order, in which they differ.  mask_out [N]: 1 on the cluster; *size_out its
+ * size.  ISINGMC_EINVAL when fewer than rank + 1 variables differ. */
+int isingmc_classical_host_icm_cluster(const isingmc_classical_config *cfg, const uint8_t *state_a, const uint8_t *state_b, uint32_t rank, uint8_t *mask_out,
+                                       uint32_t *size_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,10 @@ SSE_HD static inline int sse_op_is_diagonal(uint32_t w) { return sse_op_in(w) ==
  * strictly below (word / 2^32) * total weight (graph.rs:131-138). */
 #define SSE_TAG_CLASSICAL 8u
 #define SSE_TAG_CLASSICAL_WORM 9u
+/* Isoenergetic cluster moves between copies under classical tempering (csrc/classical_icm_rule.h): the counter is
+ * (index = m T + t, tempering step_lo, global group index, tag << 24 | step_hi24), keyed by the seed; word 0 picks the seed variable of
+ * pair m at temperature t, __umulhi(word, number of differing variables). */
+#define SSE_TAG_CLASSICAL_ICM 10u
 
 #ifdef __cplusplus
 }

@@ -199,6 +199,19 @@ SYMBOLS = {
     "isingmc_classical_host_pt_run_overlaps": (C.c_int, [_P(_ClassicalConfig), _u32, _P(_f64), _u32, _u64, _u64, _u32, _u32, _u32, _u32, _P(C.c_uint8),
                                                          _P(_u64), _P(_u32), _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_f64), _P(C.c_int32),
                                                          _P(C.c_int32), _P(C.c_int32), _P(_u64), _P(_u64)]),
+    "isingmc_classical_icm_attach": (C.c_int, [_vp, _u32, _u32]),
+    "isingmc_classical_icm_window": (C.c_int, [_vp, _P(_u32), _P(_u32)]),
+    "isingmc_classical_pt_run_icm": (C.c_int, [_vp, _u64, _u64, _u32, _u32, _u32, _u32, _P(_f64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _u32]),
+    "isingmc_classical_icm_counts": (C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    "isingmc_classical_icm_set_counts": (C.c_int, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+    "isingmc_classical_icm_reset": (C.c_int, [_vp]),
+    "isingmc_classical_icm_plan": (C.c_int, [_u32, _u32, _P(_u32)]),
+    "isingmc_classical_icm_launch_plan": (C.c_int, [_vp, _P(_u32)]),
+    "isingmc_classical_icm_force_waves": (C.c_int, [_vp, _u32]),
+    "isingmc_classical_host_pt_run_icm": (C.c_int, [_P(_ClassicalConfig), _u32, _P(_f64), _u32, _u64, _u64, _u32, _u32, _u32, _u32, _P(C.c_uint8),
+                                                    _P(_u64), _P(_u32), _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(_f64), _P(C.c_int32),
+                                                    _P(C.c_int32), _P(C.c_int32), _P(_u64), _P(_u64), _u32, _u32, _u32, _P(_u64), _P(_u64), _P(_u64)]),
+    "isingmc_classical_host_icm_cluster": (C.c_int, [_P(_ClassicalConfig), _P(C.c_uint8), _P(C.c_uint8), _u32, _P(C.c_uint8), _P(_u32)]),
 }
 
 _LIB = None

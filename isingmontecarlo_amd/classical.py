@@ -1,14 +1,15 @@
 """Classical Ising Monte Carlo on the device: `GraphState` (qmc::classical::GraphState, src/classical/graph.rs) for a batch of R
 replicas of one graph (with `couplings`: of R disorder realisations on one graph), over the isingmc_classical_* entry points of include/isingmc_hip.h.  All moves run in gfx950 kernels
 (csrc/sse_classical.hip.h), and so do replica exchange between the temperatures of a chain (csrc/sse_classical_pt.hip.h) and the overlaps between copies of a
-realisation (csrc/sse_classical_overlap.hip.h); there is no CPU fallback.  `host_steps`, `host_tempering_run` and `plan` are the device-free test entries of the C ABI."""
+realisation (csrc/sse_classical_overlap.hip.h) and the isoenergetic cluster moves between those copies (csrc/sse_classical_icm.hip.h); there is no CPU fallback.
+`host_steps`, `host_tempering_run`, `host_cluster`, `plan` and `icm_plan` are the device-free test entries of the C ABI."""
 import ctypes as C
 
 import numpy as np
 
 from . import ALL, IsingMcError, QmcIsingGraph, _ClassicalConfig, _ptr, load_library  # (imported at the end of the package's __init__)
 
-__all__ = ["GraphState", "new_qmc_from_graph", "host_steps", "host_tempering_run", "plan", "CFG_EDGE_IMPORTANCE", "CFG_GLOBAL_TABLES", "CFG_SERIAL_MOVES",
+__all__ = ["GraphState", "new_qmc_from_graph", "host_steps", "host_tempering_run", "host_cluster", "plan", "icm_plan", "CFG_EDGE_IMPORTANCE", "CFG_GLOBAL_TABLES", "CFG_SERIAL_MOVES",
            "CFG_PER_REPLICA_J", "CFG_GLOBAL_CODES",           "KINDS_ALL", "KINDS_BASIC", "KINDS_SPIN", "KINDS_EDGE", "KINDS_WORM", "KINDS_WORM_NO_DOUBLES", "COUNTERS"]
 
 CFG_EDGE_IMPORTANCE, CFG_GLOBAL_TABLES, CFG_SERIAL_MOVES, CFG_PER_REPLICA_J, CFG_GLOBAL_CODES = 1, 2, 4, 8, 16
@@ -71,6 +72,55 @@ def plan(edges, biases, lds_bytes=160 * 1024, flags=0, couplings=None):
     return _plan_dict(out)
 
 
+def icm_plan(nvars, lds_bytes=160 * 1024):
+    """isingmc_classical_icm_plan: the cluster-move launch of a model of `nvars` variables, without a device: {"waves": 4, 2 or 1,
+    "lds_words": the dynamic LDS, "wave_words": one wave's three bit sets, "max_vars": the most variables the launch takes}."""
+    lib = load_library()
+    out = (C.c_uint32 * 4)()
+    rc = lib.isingmc_classical_icm_plan(int(nvars), int(lds_bytes), out)
+    if rc:
+        raise IsingMcError(rc, lib.isingmc_classical_last_error(None).decode())
+    return _icm_plan_dict(out)
+
+
+def _icm_plan_dict(out):
+    return dict(waves=out[0], lds_words=out[1], wave_words=out[2], max_vars=out[3])
+
+
+def host_cluster(edges, biases, a, b, rank):
+    """isingmc_classical_host_icm_cluster: the cluster of one isoenergetic cluster move between the states `a` and `b` [N], seeded at
+    the `rank`-th variable (in increasing order) in which they differ: (mask uint8 [N], size)."""
+    lib = load_library()
+    ed, js, hs = _model(edges, biases)
+    sa, sb = (np.ascontiguousarray(np.array(x, dtype=np.uint8).reshape(-1)) for x in (a, b))
+    if len(sa) != len(hs) or len(sb) != len(hs):
+        raise IsingMcError(-1, "state has the wrong length")
+    mask, size = np.zeros(len(hs), dtype=np.uint8), C.c_uint32(0)
+    rc = lib.isingmc_classical_host_icm_cluster(C.byref(_config(ed, js, hs, 0, 1)), _ptr(sa, C.c_uint8), _ptr(sb, C.c_uint8), int(rank), _ptr(mask, C.c_uint8),
+                                                C.byref(size))
+    if rc:
+        raise IsingMcError(rc, lib.isingmc_classical_last_error(None).decode())
+    return mask, int(size.value)
+
+
+def _window(t_first, t_last):
+    """The window as the C ABI takes it: t_last None -> 0 (every temperature from t_first on)."""
+    return int(t_first), 0 if t_last is None else int(t_last)
+
+
+def _cluster_counts(counts, shape):
+    """Copies of (moves, empty, size_sum) as contiguous uint64 arrays of `shape`."""
+    out = tuple(np.ascontiguousarray(np.array(x, dtype=np.uint64)) for x in counts)
+    if len(out) != 3 or any(x.shape != tuple(shape) for x in out):
+        raise IsingMcError(-1, "cluster-move counts have the wrong shape")
+    return out
+
+
+def _counts_dict(moves, empty, size_sum):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return dict(moves=moves, empty=empty, size_sum=size_sum, mean_size=size_sum.astype(np.float64) / moves.astype(np.float64))
+
+
 def host_steps(edges, biases, seed, states, epochs, t, beta, nspinupdates=None, nedgeupdates=None, nwormupdates=None, only_basic_moves=None,
                kinds=None, replica_offset=0, flags=0, couplings=None):
     """isingmc_classical_host_steps: t time steps of the sequential rule on the CPU.  Returns (states, epochs, counters).
@@ -92,14 +142,19 @@ def host_steps(edges, biases, seed, states, epochs, t, beta, nspinupdates=None, 
 
 def host_tempering_run(edges, biases, seed, states, epochs, betas, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None,
                        only_basic_moves=None, kinds=None, temp_of=None, pt_step=0, replica_offset=0, flags=0, record=True, couplings=None, ncopies=None,
-                       histograms=None):
+                       histograms=None, cluster_moves=None, cluster_counts=None, measure=True):
     """isingmc_classical_host_pt_run: `rounds` rounds of (`steps` time steps, one tempering step) by the sequential rule on the CPU, for
     R = len(states) slots as chains of T = len(betas) temperatures.  Returns a dict: states [R][N], epochs [R], temp_of [R], pt_step,
     counters [R][8], attempts and accepts [C][T - 1], and with `record` energy and magnetization [rounds][C][T].  `couplings` [R][E]:
     the T rows of every chain must be equal (C realisations x T temperatures).
     With `ncopies` = K it is isingmc_classical_host_pt_run_overlaps: consecutive chains are G = C / K groups of K copies with
     P = K (K - 1) / 2 pairs, and the dict gains overlap_hist uint64 [G][P][T][N + 1] and link_hist [G][P][T][E + 1] (`histograms`:
-    the pair (hq, hl) they continue from) and, with `record`, overlap and link_overlap int32 [rounds][G][P][T]."""
+    the pair (hq, hl) they continue from) and, with `record`, overlap and link_overlap int32 [rounds][G][P][T].
+    With `cluster_moves` = (t_first, t_last) (t_last None: T) it is isingmc_classical_host_pt_run_icm: every round also makes the
+    isoenergetic cluster moves of csrc/classical_icm_rule.h at the temperatures of the window, after its measurement and before its
+    swaps (energy and magnetization are then the values after the moves), and the dict gains cluster_moves, cluster_empty and
+    cluster_size_sum, uint64 [G][K // 2][T] (`cluster_counts`: the triple they continue from).  `measure` = False leaves the overlaps
+    unmeasured in such a run."""
     lib = load_library()
     ed, js, hs = _model(edges, biases)
     st = np.ascontiguousarray(np.array(states, dtype=np.uint8).reshape(-1, len(hs)))
@@ -122,27 +177,36 @@ def host_tempering_run(edges, biases, seed, states, epochs, betas, rounds, steps
            _ptr(ep, C.c_uint64), _ptr(tof, C.c_uint32), C.byref(step), _ptr(ctr, C.c_uint64), _ptr(att, C.c_uint64), _ptr(acc, C.c_uint64),
            _ptr(energy, C.c_double) if record else None, _ptr(mag, C.c_int32) if record else None)
     betas_ptr = None if ladder is None else _ptr(ladder, C.c_double)
-    if ncopies is None:
+    icm = None
+    if ncopies is None and cluster_moves is None:
         rc = lib.isingmc_classical_host_pt_run(C.byref(cfg), ntemps, betas_ptr, *run)
     else:
-        k = int(ncopies)
+        k = 0 if ncopies is None else int(ncopies)
         groups, pairs = (chains // k, k * (k - 1) // 2) if k >= 2 and chains % k == 0 else (0, 0)  # (a shape the library refuses: empty outputs)
         shape = (groups, pairs, ntemps)
         q, ql = (np.zeros((int(rounds),) + shape, dtype=np.int32) if record else None for _ in range(2))
         hq, hl = np.zeros(shape + (len(hs) + 1,), dtype=np.uint64), np.zeros(shape + (len(ed) + 1,), dtype=np.uint64)
         if histograms is not None:
             hq, hl = _histograms(histograms, hq.shape, hl.shape)
-        rc = lib.isingmc_classical_host_pt_run_overlaps(C.byref(cfg), ntemps, betas_ptr, k, *run, _ptr(q, C.c_int32) if record else None,
-                                                        _ptr(ql, C.c_int32) if record else None, _ptr(hq, C.c_uint64), _ptr(hl, C.c_uint64))
+        tail = (_ptr(q, C.c_int32) if record else None, _ptr(ql, C.c_int32) if record else None, _ptr(hq, C.c_uint64), _ptr(hl, C.c_uint64))
+        if cluster_moves is None:
+            rc = lib.isingmc_classical_host_pt_run_overlaps(C.byref(cfg), ntemps, betas_ptr, k, *run, *tail)
+        else:
+            cshape = (groups, k // 2, ntemps)
+            icm = tuple(np.zeros(cshape, dtype=np.uint64) for _ in range(3)) if cluster_counts is None else _cluster_counts(cluster_counts, cshape)
+            rc = lib.isingmc_classical_host_pt_run_icm(C.byref(cfg), ntemps, betas_ptr, k, *run, *tail, 1 if measure else 0, *_window(*cluster_moves),
+                                                       *(_ptr(x, C.c_uint64) for x in icm))
     if rc:
         raise IsingMcError(rc, lib.isingmc_classical_last_error(None).decode())
     out = dict(states=st, epochs=ep, temp_of=tof, pt_step=int(step.value), counters=ctr, attempts=att, accepts=acc)
     if record:
         out.update(energy=energy, magnetization=mag)
-    if ncopies is not None:
+    if ncopies is not None and (measure or cluster_moves is None):
         out.update(overlap_hist=hq, link_hist=hl)
         if record:
             out.update(overlap=q, link_overlap=ql)
+    if icm is not None:
+        out.update(cluster_moves=icm[0], cluster_empty=icm[1], cluster_size_sum=icm[2])
     return out
 
 
@@ -172,6 +236,7 @@ class GraphState:
         self._counter_base = np.zeros((self.nreplicas, 8), dtype=np.uint64)
         self._ladder = None  # the ladder of attach_tempering
         self._ncopies = None  # the copies per group of attach_overlaps
+        self._icm_window = None  # (t_first, t_last) of attach_cluster_moves
         init = None
         if state is not None:
             st = np.asarray(state, dtype=np.uint8)
@@ -222,6 +287,7 @@ class GraphState:
         state, epoch, counters = self.state_ref(), self.get_epoch(), self.counters()
         tempering = self._tempering_state() if self._ladder is not None else None
         overlaps = (self._ncopies,) + self.overlap_histograms() if self._ncopies is not None else None
+        cluster = (self._icm_window, self._cluster_counts()) if self._icm_window is not None else None
         old, self._cfg_flags = self._cfg_flags, flags
         handle, self._h = self._h, None
         try:
@@ -236,14 +302,17 @@ class GraphState:
             self._restore_tempering(*tempering)
         if overlaps is not None:
             self._restore_overlaps(*overlaps)
+        if cluster is not None:
+            self._restore_cluster_moves(*cluster)
 
     # ---- parallel tempering (csrc/classical_pt_rule.h) ----
     def attach_tempering(self, betas):
         """The batch as C chains of T = len(betas) temperatures, slot r = c T + i starting at betas[i]; one ladder for all chains.
-        Attaching again resets the maps, the swap counters and the step number, and detaches the overlaps (attach_overlaps)."""
+        Attaching again resets the maps, the swap counters and the step number, and detaches the overlaps (attach_overlaps) and the
+        cluster moves (attach_cluster_moves)."""
         ladder = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).reshape(-1))
         self._check(self._lib.isingmc_classical_pt_attach(self._h, len(ladder), _ptr(ladder, C.c_double)))
-        self._ladder, self._ncopies = ladder, None
+        self._ladder, self._ncopies, self._icm_window = ladder, None, None
 
     def _chains(self):
         if self._ladder is None:
@@ -251,34 +320,47 @@ class GraphState:
         return self.nreplicas // len(self._ladder), len(self._ladder)
 
     def tempering_run(self, rounds, steps, nspinupdates=None, nedgeupdates=None, nwormupdates=None, only_basic_moves=None, kinds=None, record=True,
-                      overlaps=False):
+                      overlaps=False, cluster_moves=False):
         """`rounds` rounds of (`steps` time steps of every slot at its temperature, one tempering step of every chain), enqueued on the
         device with one synchronisation at the end.  With `record`: {"energy": float64 [rounds][C][T], "magnetization": int32
         [rounds][C][T]}, by temperature, the values before each round's swaps; otherwise None.
         `overlaps` (after attach_overlaps): every round also measures the overlaps between the copies of every group, after its steps
         and before its swaps.  The histograms accumulate, and with `record` the dict also holds "overlap" and "link_overlap", int32
-        [rounds][G][P][T].  Without `overlaps` nothing is measured and the histograms stay as they are (thermalisation)."""
+        [rounds][G][P][T].  Without `overlaps` nothing is measured and the histograms stay as they are (thermalisation).
+        `cluster_moves` (after attach_cluster_moves): every round also makes the isoenergetic cluster moves between the copies of every
+        group at the temperatures of the window, after its measurement and before its swaps; "energy" and "magnetization" are then the
+        values after the moves.  Without it no cluster move is made and their counts stay as they are."""
         c, t = self._chains()
         energy = np.zeros((int(rounds), c, t), dtype=np.float64) if record else None
         mag = np.zeros((int(rounds), c, t), dtype=np.int32) if record else None
         run = (self._h, int(rounds), int(steps), _count(nspinupdates), _count(nedgeupdates), _count(nwormupdates), _kinds(only_basic_moves, kinds),
                _ptr(energy, C.c_double) if record else None, _ptr(mag, C.c_int32) if record else None)
+        if cluster_moves and self._icm_window is None:
+            raise IsingMcError(-1, "cluster moves are not attached (attach_cluster_moves)")
         if not overlaps:
-            self._check(self._lib.isingmc_classical_pt_run(*run))
+            if cluster_moves:
+                self._check(self._lib.isingmc_classical_pt_run_icm(*run, None, None, 0))
+            else:
+                self._check(self._lib.isingmc_classical_pt_run(*run))
             return {"energy": energy, "magnetization": mag} if record else None
         shape = self._overlap_shape()
         q, ql = (np.zeros((int(rounds),) + shape, dtype=np.int32) if record else None for _ in range(2))
-        self._check(self._lib.isingmc_classical_pt_run_overlaps(*run, _ptr(q, C.c_int32) if record else None, _ptr(ql, C.c_int32) if record else None))
+        series = (_ptr(q, C.c_int32) if record else None, _ptr(ql, C.c_int32) if record else None)
+        if cluster_moves:
+            self._check(self._lib.isingmc_classical_pt_run_icm(*run, *series, 1))
+        else:
+            self._check(self._lib.isingmc_classical_pt_run_overlaps(*run, *series))
         return {"energy": energy, "magnetization": mag, "overlap": q, "link_overlap": ql} if record else None
 
     # ---- overlaps between copies of a realisation (csrc/classical_overlap_rule.h) ----
     def attach_overlaps(self, ncopies=2):
         """Consecutive chains as G = C / ncopies groups of `ncopies` independent copies of one realisation (with `couplings`: the chains
         of a group must hold the same rows); the P = K (K - 1) / 2 pairs of a group are (a, b), a < b, a-major.  Needs
-        attach_tempering.  The histograms start at zero; ncopies = 0 detaches."""
+        attach_tempering.  The histograms start at zero; ncopies = 0 detaches.  Either way the cluster moves are detached."""
         self._chains()
         self._check(self._lib.isingmc_classical_overlap_attach(self._h, int(ncopies)))
         self._ncopies = int(ncopies) if ncopies else None
+        self._icm_window = None
 
     def _overlap_shape(self):
         """(G, P, T)"""
@@ -315,6 +397,60 @@ class GraphState:
         shape = self._overlap_shape()
         hq, hl = _histograms((hq, hl), shape + (self.nvars + 1,), shape + (len(self.edges) + 1,))
         self._check(self._lib.isingmc_classical_overlap_set_histograms(self._h, _ptr(hq, C.c_uint64), _ptr(hl, C.c_uint64)))
+
+    # ---- isoenergetic cluster moves between the copies of a group (csrc/classical_icm_rule.h) ----
+    def attach_cluster_moves(self, t_first=0, t_last=None, waves=None):
+        """Houdayer / isoenergetic cluster moves at the ladder indices t_first <= t < t_last (None: T); needs attach_overlaps.  A round
+        of tempering_run(cluster_moves=True) pairs the copies of a group (K // 2 disjoint pairs that rotate with the tempering step
+        number) and, at every temperature of the window, flips in both states of a pair one connected cluster of the variables in which
+        they differ.  Keep the window away from temperatures where those clusters percolate.  The counts start at zero;
+        t_first = t_last = NONE detaches.  `waves` (1, 2 or 4, at most the launch plan's) runs the launch with fewer waves per workgroup
+        than planned, for tests and A-B timing; the moves do not depend on it."""
+        self._overlap_shape()
+        first, last = _window(t_first, t_last)
+        self._check(self._lib.isingmc_classical_icm_attach(self._h, first, last))
+        if first == NONE and last == NONE:
+            self._icm_window = None
+            return
+        lo, hi = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.isingmc_classical_icm_window(self._h, C.byref(lo), C.byref(hi)))
+        self._icm_window = (int(lo.value), int(hi.value))
+        if waves is not None:
+            self._check(self._lib.isingmc_classical_icm_force_waves(self._h, int(waves)))
+
+    def _cluster_shape(self):
+        """(G, M, T)"""
+        if self._icm_window is None:
+            raise IsingMcError(-1, "cluster moves are not attached (attach_cluster_moves)")
+        g, _, t = self._overlap_shape()
+        return g, self._ncopies // 2, t
+
+    def _cluster_counts(self):
+        out = tuple(np.zeros(self._cluster_shape(), dtype=np.uint64) for _ in range(3))
+        self._check(self._lib.isingmc_classical_icm_counts(self._h, *(_ptr(x, C.c_uint64) for x in out)))
+        return out
+
+    def cluster_move_counts(self):
+        """{"moves", "empty", "size_sum"}: uint64 [G][K // 2][T], cumulative since attach_cluster_moves or reset_cluster_moves: the moves
+        made, the items whose two states were equal, and the sizes of the flipped clusters added up (all zero outside the window);
+        "mean_size": size_sum / moves, float64, NaN where no move was made."""
+        return _counts_dict(*self._cluster_counts())
+
+    def reset_cluster_moves(self):
+        self._cluster_shape()
+        self._check(self._lib.isingmc_classical_icm_reset(self._h))
+
+    def cluster_move_plan(self):
+        """isingmc_classical_icm_launch_plan: the cluster-move launch of this batch on its device; the dict of icm_plan()."""
+        self._cluster_shape()
+        out = (C.c_uint32 * 4)()
+        self._check(self._lib.isingmc_classical_icm_launch_plan(self._h, out))
+        return _icm_plan_dict(out)
+
+    def _restore_cluster_moves(self, window, counts):
+        self.attach_cluster_moves(int(window[0]), int(window[1]))
+        counts = _cluster_counts(counts, self._cluster_shape())
+        self._check(self._lib.isingmc_classical_icm_set_counts(self._h, *(_ptr(x, C.c_uint64) for x in counts)))
 
     def temperature_of(self):
         """uint32 [R]: the index into the ladder of the temperature each slot holds."""
@@ -428,7 +564,8 @@ class GraphState:
         map of slots to temperatures, the tempering step number and both swap counters; without, it is the format-1 file.  A batch with
         per-replica couplings writes format 3: `couplings` [R][E] next to the keys of format 1, and those of format 2 when tempering is
         attached.  A batch with overlaps attached writes format 4: the keys it would otherwise write, and `ncopies`, `overlap_hist`,
-        `link_hist`."""
+        `link_hist`.  A batch with cluster moves attached writes format 5: the keys it would otherwise write, and `cluster_window`
+        (t_first, t_last), `cluster_moves`, `cluster_empty`, `cluster_size_sum`."""
         extra = {}
         if self._ladder is not None:
             ladder, temp_of, pt_step, attempts, accepts = self._tempering_state()
@@ -439,6 +576,9 @@ class GraphState:
         if self._ncopies is not None:
             hq, hl = self.overlap_histograms()
             fmt, extra = 4, dict(extra, ncopies=np.array([self._ncopies], dtype=np.uint32), overlap_hist=hq, link_hist=hl)
+        if self._icm_window is not None:
+            moves, empty, size_sum = self._cluster_counts()
+            fmt, extra = 5, dict(extra, cluster_window=np.array(self._icm_window, dtype=np.uint32), cluster_moves=moves, cluster_empty=empty, cluster_size_sum=size_sum)
         np.savez_compressed(path, format=np.array([fmt], dtype=np.uint32), edges=self.edges, J=self.J, biases=self.biases,
                             seed=np.array([self.seed], dtype=np.uint64), replica_offset=np.array([self.replica_offset], dtype=np.uint32),
                             importance=np.array([bool(self._cfg_flags & CFG_EDGE_IMPORTANCE)]), state=self.state_ref(), epoch=self.get_epoch(),
@@ -447,9 +587,9 @@ class GraphState:
     def load_checkpoint(self, path):
         z = np.load(path, allow_pickle=False)
         fmt = int(z["format"][0])
-        if fmt not in (1, 2, 3, 4):
+        if fmt not in (1, 2, 3, 4, 5):
             raise IsingMcError(-1, "unknown checkpoint format")
-        has_couplings = fmt == 3 or (fmt == 4 and "couplings" in z.files)
+        has_couplings = fmt == 3 or (fmt >= 4 and "couplings" in z.files)
         if not np.array_equal(z["edges"], self.edges) or not np.array_equal(z["J"], self.J) or not np.array_equal(z["biases"], self.biases):
             raise IsingMcError(-1, "checkpoint belongs to a different model")
         if has_couplings != (self.couplings is not None) or (has_couplings and not np.array_equal(z["couplings"].view(np.uint64), self.couplings.view(np.uint64))):
@@ -462,8 +602,10 @@ class GraphState:
         self._counter_base = z["counters"].astype(np.uint64) - (self.counters() - self._counter_base)
         if fmt == 2 or (fmt >= 3 and "ladder" in z.files):
             self._restore_tempering(z["ladder"], z["temp_of"], int(z["pt_step"][0]), z["swap_attempts"], z["swap_accepts"])
-        if fmt == 4:
+        if fmt >= 4:
             self._restore_overlaps(int(z["ncopies"][0]), z["overlap_hist"], z["link_hist"])
+        if fmt == 5:
+            self._restore_cluster_moves(z["cluster_window"], (z["cluster_moves"], z["cluster_empty"], z["cluster_size_sum"]))
 
     def edge_list(self, r=None):
         """The edges as they were given: [((a, b), J), ...]; with `r`, the edges of replica r's realisation (its row of `couplings`)."""

@@ -246,7 +246,7 @@ int isingmc_classical_create(const isingmc_classical_config *cfg, isingmc_classi
     int dev = 0, max_lds = 0;
     if (const char *why = probe_device(cfg->device, &dev, &max_lds)) return cmc_refuse(ISINGMC_ENODEVICE, why);
     isingmc_classical *g = new isingmc_classical();
-    g->device = dev; g->flags = cfg->flags;
+    g->device = dev; g->flags = cfg->flags; g->lds_bytes = (uint32_t)max_lds;
     if (const int rc = plan_config(cfg, (uint32_t)max_lds, g->host, g->carve)) { delete g; return rc; }
     if (const int rc = allocate_and_upload(g, cfg)) { g_classical_error = g->err; isingmc_classical_destroy(g); return rc; }
     *out = g;

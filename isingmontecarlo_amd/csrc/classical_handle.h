@@ -47,18 +47,28 @@ struct CmcOvHandle {
     size_t hq_count = 0, hl_count = 0; // entries of the two histograms
 };
 
+// cluster moves between copies (isingmc_classical_icm_attach): the counts live from attach to detach
+struct CmcIcmHandle {
+    bool attached = false;
+    sse::CmcIcmDev dev{};
+    DevBuf counts;    // the block behind dev.moves / dev.empty / dev.size_sum: [3][G][M][T]
+    size_t count = 0; // entries of one of the three, G M T
+};
+
 struct isingmc_classical {
     sse::CmcDev dev{};
     sse::CmcCarve carve{};
     CmcHostTables host;
     uint32_t flags = 0;
     int device = 0;
+    uint32_t lds_bytes = 0; // the LDS of one workgroup of the device
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     double *d_beta = nullptr, *d_energy = nullptr;
     CmcPtHandle pt;
     CmcOvHandle ov;
+    CmcIcmHandle icm;
     std::vector<DevBuf> allocs;
     mutable std::string err;
 };

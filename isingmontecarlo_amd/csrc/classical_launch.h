@@ -131,4 +131,38 @@ struct CmcOvDev {
 // one measurement of every item with the maps as they stand; q_row / ql_row: [G][P][T], or null.  The histograms gain one count each.
 hipError_t launch_classical_overlaps(hipStream_t stream, const CmcDev &D, const CmcPtDev &P, const CmcOvDev &O, int32_t *q_row, int32_t *ql_row);
 
+// The cluster-move launch (classical_icm_rule.h; sse_classical_icm.hip.h, unit sweep_classical_icm.hip): one wave per item (g, m, t)
+// of the window, W waves a workgroup.  The LDS of classical_icm_kernel in words: per wave, from word wave * wave_words, three bit sets
+// of nwords words each: d (the differing variables), the cluster, the frontier.  Nothing else lives in LDS: rows and entries are read
+// from global memory, where the batch shares them.
+struct CmcIcmCarve {
+    uint32_t W, nwords, wave_words; // waves a workgroup; words of one bit set; a wave's area (3 nwords)
+    uint32_t words;                 // the dynamic LDS of the launch
+};
+__host__ __device__ inline uint32_t cmc_icm_wave_words(uint32_t N) { return 3u * ((N + 31u) / 32u); }
+inline CmcIcmCarve cmc_icm_carve(uint32_t N, uint32_t W) { return CmcIcmCarve{W, (N + 31u) / 32u, cmc_icm_wave_words(N), W * cmc_icm_wave_words(N)}; }
+// the most waves a workgroup of 4, 2, 1 whose areas fit; W = 0: the area of a single wave exceeds LDS
+inline CmcIcmCarve cmc_icm_plan(uint32_t N, size_t total_words) {
+    const uint32_t counts[3] = {4, 2, 1};
+    for (uint32_t W : counts)
+        if ((size_t)W * cmc_icm_wave_words(N) <= total_words) return cmc_icm_carve(N, W);
+    return CmcIcmCarve{};
+}
+// the most variables whose single-wave area fits (what ISINGMC_ENOTIMPL names)
+inline uint32_t cmc_icm_max_vars(size_t total_words) {
+    uint32_t lo = 0, hi = CMC_MAX_VARS;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (cmc_icm_wave_words(mid) <= total_words) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+struct CmcIcmDev {
+    uint32_t t_first, t_last, M;        // the window of ladder indices; pairs a group, K / 2
+    CmcIcmCarve C;
+    uint64_t *moves, *empty, *size_sum; // [G][M][T] each
+};
+// the cluster moves of every item of the window at step number pt_step, with the maps as they stand
+hipError_t launch_classical_icm(hipStream_t stream, const CmcDev &D, const CmcPtDev &P, const CmcOvDev &O, const CmcIcmDev &I, uint64_t pt_step);
+
 } // namespace sse

@@ -2,8 +2,10 @@
 // rounds (steps launch, tempering launch) without a host synchronisation in between, the checkpoint accessors, and the same rounds by
 // the sequential rule on the CPU (isingmc_classical_host_pt_run).  The rule is classical_pt_rule.h.  The overlaps between copies of a
 // realisation (isingmc_classical_overlap_*, classical_overlap_rule.h) are measured inside those rounds, so they live here as well: one
-// round loop on the device and one on the host, with and without the measurement.
+// round loop on the device and one on the host, with and without the measurement.  The cluster moves between those copies
+// (isingmc_classical_icm_*, classical_icm_rule.h) are a third launch of the same rounds, so they live here too.
 #include "classical_handle.h"
+#include "classical_icm_rule.h"
 #include "classical_overlap_rule.h"
 #include "classical_pt_rule.h"
 
@@ -62,7 +64,27 @@ static int check_overlap_args(const CmcHostTables &H, uint32_t R, uint32_t repli
     return ISINGMC_OK;
 }
 
-static void detach_overlaps(isingmc_classical *g) { g->ov = CmcOvHandle{}; } // (frees the histograms)
+// (frees the histograms; the cluster moves pair the copies of the overlaps, so they go with them, and their counts are freed too)
+static void detach_overlaps(isingmc_classical *g) { g->ov = CmcOvHandle{}; g->icm = CmcIcmHandle{}; }
+
+// The window of cluster moves (classical_icm_rule.h): what icm_attach and the host entry ask.  t_last = 0 means T.
+static int check_icm_window(uint32_t T, uint32_t &t_first, uint32_t &t_last, std::string &why) {
+    if (t_last == 0u) t_last = T;
+    if (t_last > T) { why = "cluster moves: t_last = " + std::to_string(t_last) + " exceeds the " + std::to_string(T) + " temperatures of the ladder"; return ISINGMC_EINVAL; }
+    if (t_first >= t_last) { why = "cluster moves need a window t_first < t_last: [" + std::to_string(t_first) + ", " + std::to_string(t_last) + ") is empty or reversed"; return ISINGMC_EINVAL; }
+    return ISINGMC_OK;
+}
+// the refusal of a model whose bit sets exceed LDS
+static std::string icm_too_large(size_t total_words, uint32_t lds_bytes) {
+    return "model too large for cluster moves: the three bit sets of one item exceed LDS (at most " + std::to_string(cmc_icm_max_vars(total_words)) + " variables in " +
+           std::to_string(lds_bytes) + " bytes)";
+}
+
+static int need_icm(isingmc_classical *g, const char *who) {
+    if (g->icm.attached) return ISINGMC_OK;
+    g->err = std::string(who) + ": call isingmc_classical_icm_attach first";
+    return ISINGMC_EINVAL;
+}
 
 static int need_overlaps(isingmc_classical *g, const char *who) {
     if (g->ov.attached) return ISINGMC_OK;
@@ -95,9 +117,10 @@ struct CmcBytes { // a state as bytes, read only
     bool get(uint32_t v) const { return s[v] != 0; }
 };
 
-// rounds x (steps launch, [overlap launch,] tempering launch) enqueued back to back, one synchronisation at the end: the loop of
-// isingmc_classical_pt_run and isingmc_classical_pt_run_overlaps.  measure: the overlap launch runs between the two (the handle has overlaps attached)
-static int run_rounds(isingmc_classical *g, bool measure, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
+// rounds x (steps launch, [overlap launch,] [cluster-move launch,] tempering launch) enqueued back to back, one synchronisation at the
+// end: the loop of isingmc_classical_pt_run, isingmc_classical_pt_run_overlaps and isingmc_classical_pt_run_icm.  measure: the overlap
+// launch runs (the handle has overlaps attached); icm: the cluster-move launch runs behind it (the handle has cluster moves attached)
+static int run_rounds(isingmc_classical *g, bool measure, bool icm, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
                       double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out) {
     if (kinds >= CMC_KINDS_COUNT) { g->err = "kinds must be one of ISINGMC_CLASSICAL_KINDS_*"; return ISINGMC_EINVAL; }
     if (rounds == 0) return ISINGMC_OK;
@@ -118,6 +141,8 @@ static int run_rounds(isingmc_classical *g, bool measure, uint64_t rounds, uint6
         if (steps) e = launch_classical_steps(g->stream, g->dev, g->carve, A);
         if (e == hipSuccess && measure) // after the steps, before the swaps: the maps still say where every temperature is
             e = launch_classical_overlaps(g->stream, g->dev, g->pt.dev, g->ov.dev, reinterpret_cast<int32_t *>(row(2, i)), reinterpret_cast<int32_t *>(row(3, i)));
+        if (e == hipSuccess && icm) // the tempering launch computes E and M from the states the moves leave
+            e = launch_classical_icm(g->stream, g->dev, g->pt.dev, g->ov.dev, g->icm.dev, g->pt.step);
         if (e == hipSuccess) e = launch_classical_tempering(g->stream, g->dev, g->pt.dev, g->pt.step, reinterpret_cast<double *>(row(0, i)), reinterpret_cast<int32_t *>(row(1, i)));
         if (e == hipSuccess) g->pt.step++;
     }
@@ -151,7 +176,7 @@ int isingmc_classical_pt_attach(isingmc_classical *g, uint32_t ntemps, const dou
         P.dev.betas = P.d_betas;
     }
     P.attached = false;
-    detach_overlaps(g); // the shape of the batch changes: groups and histograms belong to the ladder they were attached under
+    detach_overlaps(g); // the shape of the batch changes: groups, histograms and cluster moves belong to the ladder they were attached under
     P.dev.T = ntemps; P.dev.C = R / ntemps;
     P.betas.assign(betas, betas + ntemps);
     P.step = 0;
@@ -169,7 +194,7 @@ int isingmc_classical_pt_run(isingmc_classical *g, uint64_t rounds, uint64_t ste
                              double *energy_out, int32_t *mag_out) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_attached(g, "isingmc_classical_pt_run")) return rc;
-    return run_rounds(g, false, rounds, steps, nspin, nedge, nworm, kinds, energy_out, mag_out, nullptr, nullptr);
+    return run_rounds(g, false, false, rounds, steps, nspin, nedge, nworm, kinds, energy_out, mag_out, nullptr, nullptr);
 }
 
 int isingmc_classical_pt_run_overlaps(isingmc_classical *g, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
@@ -177,7 +202,7 @@ int isingmc_classical_pt_run_overlaps(isingmc_classical *g, uint64_t rounds, uin
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_attached(g, "isingmc_classical_pt_run_overlaps")) return rc;
     if (const int rc = need_overlaps(g, "isingmc_classical_pt_run_overlaps")) return rc;
-    return run_rounds(g, true, rounds, steps, nspin, nedge, nworm, kinds, energy_out, mag_out, q_out, ql_out);
+    return run_rounds(g, true, false, rounds, steps, nspin, nedge, nworm, kinds, energy_out, mag_out, q_out, ql_out);
 }
 
 int isingmc_classical_overlap_attach(isingmc_classical *g, uint32_t ncopies) {
@@ -229,6 +254,109 @@ int isingmc_classical_overlap_reset(isingmc_classical *g) {
     return ISINGMC_OK;
 }
 
+int isingmc_classical_icm_plan(uint32_t nvars, uint32_t lds_bytes, uint32_t out[4]) {
+    if (!out) return cmc_refuse(ISINGMC_EINVAL, "null output");
+    if (nvars == 0u || nvars > CMC_MAX_VARS) return cmc_refuse(ISINGMC_EINVAL, "nvars must be 1 .. 2^24");
+    const CmcIcmCarve c = cmc_icm_plan(nvars, lds_bytes / 4u);
+    if (c.W == 0u) return cmc_refuse(ISINGMC_ENOTIMPL, icm_too_large(lds_bytes / 4u, lds_bytes));
+    out[0] = c.W; out[1] = c.words; out[2] = c.wave_words; out[3] = cmc_icm_max_vars(lds_bytes / 4u);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_icm_launch_plan(isingmc_classical *g, uint32_t out[4]) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_icm(g, "isingmc_classical_icm_launch_plan")) return rc;
+    if (!out) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    const CmcIcmCarve &c = g->icm.dev.C;
+    out[0] = c.W; out[1] = c.words; out[2] = c.wave_words; out[3] = cmc_icm_max_vars(g->lds_bytes / 4u);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_icm_attach(isingmc_classical *g, uint32_t t_first, uint32_t t_last) {
+    if (!g) return ISINGMC_EINVAL;
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    if (t_first == CMC_NONE && t_last == CMC_NONE) { g->icm = CmcIcmHandle{}; return ISINGMC_OK; }
+    if (const int rc = need_attached(g, "isingmc_classical_icm_attach")) return rc;
+    if (const int rc = need_overlaps(g, "isingmc_classical_icm_attach")) return rc;
+    if (const int rc = check_icm_window(g->pt.dev.T, t_first, t_last, g->err)) return rc;
+    const CmcIcmCarve c = cmc_icm_plan(g->host.N, g->lds_bytes / 4u);
+    if (c.W == 0u) { g->err = icm_too_large(g->lds_bytes / 4u, g->lds_bytes); return ISINGMC_ENOTIMPL; }
+    const uint32_t M = cmc_icm_pairs(g->ov.dev.K);
+    const size_t count = (size_t)g->ov.dev.G * M * g->pt.dev.T; // (at most the overlap items: they fit)
+    CmcIcmHandle fresh;
+    if (fresh.counts.alloc(3u * count * 8u) != hipSuccess) {
+        g->err = "hipMalloc of the cluster-move counts failed (" + std::to_string(3u * count * 8u) + " bytes)";
+        return ISINGMC_ENODEVICE;
+    }
+    HIP_TRY(g, hipMemset(fresh.counts.as<void>(), 0, 3u * count * 8u));
+    uint64_t *base = fresh.counts.as<uint64_t>();
+    fresh.dev = sse::CmcIcmDev{t_first, t_last, M, c, base, base + count, base + 2u * count};
+    fresh.count = count;
+    fresh.attached = true;
+    g->icm = std::move(fresh);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_icm_force_waves(isingmc_classical *g, uint32_t waves) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_icm(g, "isingmc_classical_icm_force_waves")) return rc;
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    const CmcIcmCarve plan = cmc_icm_plan(g->host.N, g->lds_bytes / 4u);
+    if (waves == 0u) { g->icm.dev.C = plan; return ISINGMC_OK; }
+    if ((waves != 1u && waves != 2u && waves != 4u) || waves > plan.W) {
+        g->err = "cluster moves: waves must be 1, 2 or 4 and at most the " + std::to_string(plan.W) + " that fit LDS (0: as planned)";
+        return ISINGMC_EINVAL;
+    }
+    g->icm.dev.C = cmc_icm_carve(g->host.N, waves);
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_pt_run_icm(isingmc_classical *g, uint64_t rounds, uint64_t steps, uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds,
+                                 double *energy_out, int32_t *mag_out, int32_t *q_out, int32_t *ql_out, uint32_t measure) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_attached(g, "isingmc_classical_pt_run_icm")) return rc;
+    if (const int rc = need_overlaps(g, "isingmc_classical_pt_run_icm")) return rc;
+    if (const int rc = need_icm(g, "isingmc_classical_pt_run_icm")) return rc;
+    return run_rounds(g, measure != 0u, true, rounds, steps, nspin, nedge, nworm, kinds, energy_out, mag_out, measure ? q_out : nullptr, measure ? ql_out : nullptr);
+}
+
+int isingmc_classical_icm_window(isingmc_classical *g, uint32_t *t_first, uint32_t *t_last) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_icm(g, "isingmc_classical_icm_window")) return rc;
+    if (t_first) *t_first = g->icm.dev.t_first;
+    if (t_last) *t_last = g->icm.dev.t_last;
+    return ISINGMC_OK;
+}
+
+int isingmc_classical_icm_counts(isingmc_classical *g, uint64_t *moves, uint64_t *empty, uint64_t *size_sum) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_icm(g, "isingmc_classical_icm_counts")) return rc;
+    if (const int rc = isingmc_classical_synchronize(g)) return rc;
+    if (moves) if (const int rc = copy_down(g, moves, g->icm.dev.moves, g->icm.count)) return rc;
+    if (empty) if (const int rc = copy_down(g, empty, g->icm.dev.empty, g->icm.count)) return rc;
+    return size_sum ? copy_down(g, size_sum, g->icm.dev.size_sum, g->icm.count) : ISINGMC_OK;
+}
+
+int isingmc_classical_icm_set_counts(isingmc_classical *g, const uint64_t *moves, const uint64_t *empty, const uint64_t *size_sum) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_icm(g, "isingmc_classical_icm_set_counts")) return rc;
+    if (!moves || !empty || !size_sum) { g->err = "null buffer"; return ISINGMC_EINVAL; }
+    if (const int rc = copy_up(g, g->icm.dev.moves, moves, g->icm.count, true)) return rc;
+    if (const int rc = copy_up(g, g->icm.dev.empty, empty, g->icm.count)) return rc;
+    return copy_up(g, g->icm.dev.size_sum, size_sum, g->icm.count);
+}
+
+int isingmc_classical_icm_reset(isingmc_classical *g) {
+    if (!g) return ISINGMC_EINVAL;
+    if (const int rc = need_icm(g, "isingmc_classical_icm_reset")) return rc;
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    HIP_TRY(g, hipMemset(g->icm.counts.as<void>(), 0, 3u * g->icm.count * 8u));
+    return ISINGMC_OK;
+}
+
 int isingmc_classical_pt_get(isingmc_classical *g, uint32_t *temp_of, uint64_t *pt_step) {
     if (!g) return ISINGMC_EINVAL;
     if (const int rc = need_attached(g, "isingmc_classical_pt_get")) return rc;
@@ -273,8 +401,26 @@ int isingmc_classical_pt_set_swap_counts(isingmc_classical *g, const uint64_t *a
 
 } // extern "C"
 
-// The rounds of isingmc_classical_host_pt_run and isingmc_classical_host_pt_run_overlaps: ncopies = 0 measures nothing
-static int host_rounds(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint32_t ncopies, uint64_t rounds, uint64_t steps,
+// the cluster moves of the host rounds: the window and the three counts (each may be null)
+struct CmcIcmHostArgs {
+    uint32_t t_first, t_last;
+    uint64_t *moves, *empty, *size_sum;
+};
+
+// The cluster of the rank-th differing variable of the states a and b ([N] bytes) into mark ([N], zeroed on entry); diff and stack
+// are [N] scratch.  Returns its size, or 0 when fewer than rank + 1 variables differ.
+static uint32_t host_cluster(const CmcGraphMem &g, const uint8_t *a, const uint8_t *b, bool draw, const uint32_t c[4], uint64_t seed, uint32_t rank, uint8_t *diff,
+                             uint8_t *mark, uint32_t *stack) {
+    uint32_t nq = 0;
+    for (uint32_t v = 0; v < g.N(); ++v) { diff[v] = (a[v] != 0) != (b[v] != 0) ? 1u : 0u; nq += diff[v]; }
+    if (draw && nq) rank = cmc_range(CmcHostDraw{(uint32_t)seed, (uint32_t)(seed >> 32), c[2], c[1], c[3] & 0xFFFFFFu}(c[3] >> 24, c[0], 0), nq);
+    return rank < nq ? cmc_icm_grow(g, diff, rank, mark, stack) : 0u;
+}
+
+// The rounds of isingmc_classical_host_pt_run, isingmc_classical_host_pt_run_overlaps and isingmc_classical_host_pt_run_icm: ncopies = 0
+// has no groups; measure: the overlaps are measured; icm: the cluster moves run (null: none)
+static int host_rounds(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint32_t ncopies, bool measure, const CmcIcmHostArgs *icm_in,
+                       uint64_t rounds, uint64_t steps,
                        uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
                        uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out,
                        int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl) {
@@ -292,7 +438,15 @@ static int host_rounds(const isingmc_classical_config *cfg, uint32_t ntemps, con
     CmcOvShape ov{};
     if (ncopies != 0u)
         if (const int rc = check_overlap_args(H, R, cfg->replica_offset, T, ncopies, ov, why)) return cmc_refuse(rc, why);
+    CmcIcmHostArgs icm{};
+    if (icm_in) {
+        icm = *icm_in;
+        if (ncopies == 0u) return cmc_refuse(ISINGMC_EINVAL, "cluster moves need ncopies >= 2 (they exchange clusters between the copies of a group)");
+        if (const int rc = check_icm_window(T, icm.t_first, icm.t_last, why)) return cmc_refuse(rc, why);
+    }
     const uint32_t N = H.N;
+    std::vector<uint8_t> diff(icm_in ? N : 0u), cluster(icm_in ? N : 0u, 0);
+    std::vector<uint32_t> stack(icm_in ? N : 0u);
     const CmcHostMoves m{cmc_default_moves(nspin, N / 2u), cmc_default_moves(nedge, H.E / 2u), cmc_default_moves(nworm, 1u), kinds};
     std::vector<uint8_t> mark(N, 0);
     std::vector<uint32_t> slot_at(R);
@@ -310,7 +464,7 @@ static int host_rounds(const isingmc_classical_config *cfg, uint32_t ntemps, con
             if (energy_out) energy_out[at] = energy[r];
             if (mag_out) mag_out[at] = cmc_pt_magnetization(g, s);
         }
-        for (uint64_t item = 0; item < ov.items; ++item) { // after the steps, before the swaps (ncopies = 0: no items)
+        for (uint64_t item = 0; measure && item < ov.items; ++item) { // after the steps, before the swaps (ncopies = 0: no items)
             uint32_t grp, p, t, a, b;
             cmc_ov_item(item, ov.P, T, grp, p, t);
             cmc_ov_pair(ov.K, p, a, b);
@@ -321,6 +475,30 @@ static int host_rounds(const isingmc_classical_config *cfg, uint32_t ntemps, con
             if (ql_out) ql_out[(size_t)round * ov.items + item] = cmc_ov_overlap(H.E, nl);
             if (hq) hq[(size_t)item * ((size_t)N + 1u) + nq] += 1u;
             if (hl) hl[(size_t)item * ((size_t)H.E + 1u) + nl] += 1u;
+        }
+        const uint32_t M = cmc_icm_pairs(ov.K);
+        for (uint64_t item = 0, items = icm_in ? (uint64_t)ov.G * M * (icm.t_last - icm.t_first) : 0u; item < items; ++item) { // behind the measurement
+            uint32_t grp, p, t, a, b, ctr[4];
+            cmc_icm_item(item, M, icm.t_first, icm.t_last, grp, p, t);
+            cmc_icm_pair(ov.K, *pt_step, p, a, b);
+            const uint32_t ra = cmc_ov_slot(slot_at.data(), T, grp * ov.K + a, t), rb = cmc_ov_slot(slot_at.data(), T, grp * ov.K + b, t);
+            uint8_t *A = states + (size_t)ra * N, *B = states + (size_t)rb * N;
+            cmc_icm_counter(T, *pt_step, (cfg->replica_offset / T + grp * ov.K) / ov.K, p, t, ctr);
+            const uint32_t size = host_cluster(cmc_graph_mem(H.view(), ra), A, B, true, ctr, cfg->seed, 0u, diff.data(), cluster.data(), stack.data());
+            const size_t at = cmc_icm_count_index(M, T, grp, p, t);
+            if (size == 0u) { if (icm.empty) icm.empty[at] += 1u; continue; }
+            if (icm.moves) icm.moves[at] += 1u;
+            if (icm.size_sum) icm.size_sum[at] += size;
+            for (uint32_t v = 0; v < N; ++v)
+                if (cluster[v]) { A[v] = A[v] ? 0u : 1u; B[v] = B[v] ? 0u : 1u; cluster[v] = 0u; }
+            for (const uint32_t r : {ra, rb}) { // E and M of the round are those the swaps see: after the moves
+                const CmcGraphMem g = cmc_graph_mem(H.view(), r);
+                const CmcBytes s{states + (size_t)r * N};
+                energy[r] = cmc_pt_energy(g, s);
+                const size_t row = (size_t)round * R + (r / T) * T + temp_of[r];
+                if (energy_out) energy_out[row] = energy[r];
+                if (mag_out) mag_out[row] = cmc_pt_magnetization(g, s);
+            }
         }
         for (uint32_t c = 0; c < C; ++c) {
             const size_t base = (size_t)c * T, cbase = (size_t)c * (T - 1u);
@@ -337,7 +515,7 @@ extern "C" {
 int isingmc_classical_host_pt_run(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint64_t rounds, uint64_t steps,
                                   uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
                                   uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out) {
-    return host_rounds(cfg, ntemps, betas, 0u, rounds, steps, nspin, nedge, nworm, kinds, states, epochs, temp_of, pt_step, counters, attempts, accepts, energy_out, mag_out,
+    return host_rounds(cfg, ntemps, betas, 0u, false, nullptr, rounds, steps, nspin, nedge, nworm, kinds, states, epochs, temp_of, pt_step, counters, attempts, accepts, energy_out, mag_out,
                        nullptr, nullptr, nullptr, nullptr);
 }
 
@@ -347,8 +525,35 @@ int isingmc_classical_host_pt_run_overlaps(const isingmc_classical_config *cfg, 
                                            int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl) {
     if (const int rc = cmc_check_config(cfg)) return rc;
     if (ncopies == 0u) return cmc_refuse(ISINGMC_EINVAL, kNeedCopies);
-    return host_rounds(cfg, ntemps, betas, ncopies, rounds, steps, nspin, nedge, nworm, kinds, states, epochs, temp_of, pt_step, counters, attempts, accepts, energy_out,
+    return host_rounds(cfg, ntemps, betas, ncopies, true, nullptr, rounds, steps, nspin, nedge, nworm, kinds, states, epochs, temp_of, pt_step, counters, attempts, accepts, energy_out,
                        mag_out, q_out, ql_out, hq, hl);
+}
+
+int isingmc_classical_host_pt_run_icm(const isingmc_classical_config *cfg, uint32_t ntemps, const double *betas, uint32_t ncopies, uint64_t rounds, uint64_t steps,
+                                      uint32_t nspin, uint32_t nedge, uint32_t nworm, uint32_t kinds, uint8_t *states, uint64_t *epochs, uint32_t *temp_of,
+                                      uint64_t *pt_step, uint64_t *counters, uint64_t *attempts, uint64_t *accepts, double *energy_out, int32_t *mag_out,
+                                      int32_t *q_out, int32_t *ql_out, uint64_t *hq, uint64_t *hl, uint32_t measure, uint32_t t_first, uint32_t t_last,
+                                      uint64_t *moves, uint64_t *empty, uint64_t *size_sum) {
+    if (const int rc = cmc_check_config(cfg)) return rc;
+    const CmcIcmHostArgs icm{t_first, t_last, moves, empty, size_sum};
+    return host_rounds(cfg, ntemps, betas, ncopies, measure != 0u, &icm, rounds, steps, nspin, nedge, nworm, kinds, states, epochs, temp_of, pt_step, counters, attempts,
+                       accepts, energy_out, mag_out, q_out, ql_out, hq, hl);
+}
+
+int isingmc_classical_host_icm_cluster(const isingmc_classical_config *cfg, const uint8_t *state_a, const uint8_t *state_b, uint32_t rank, uint8_t *mask_out,
+                                       uint32_t *size_out) {
+    if (const int rc = cmc_check_config(cfg)) return rc;
+    if (!state_a || !state_b || !mask_out) return cmc_refuse(ISINGMC_EINVAL, "state_a, state_b and mask_out must be non-null");
+    CmcHostTables H;
+    cmc_build_tables(cfg, H);
+    std::vector<uint8_t> diff(H.N);
+    std::vector<uint32_t> stack(H.N);
+    std::fill(mask_out, mask_out + H.N, (uint8_t)0);
+    const uint32_t none[4] = {0, 0, 0, 0};
+    const uint32_t size = host_cluster(cmc_graph_mem(H.view(), 0u), state_a, state_b, false, none, 0u, rank, diff.data(), mask_out, stack.data());
+    if (size == 0u) return cmc_refuse(ISINGMC_EINVAL, "rank must be below the number of variables in which the two states differ");
+    if (size_out) *size_out = size;
+    return ISINGMC_OK;
 }
 
 } // extern "C"

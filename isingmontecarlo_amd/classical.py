@@ -284,10 +284,7 @@ class GraphState:
         flags = (self._cfg_flags | CFG_EDGE_IMPORTANCE) if enable else (self._cfg_flags & ~CFG_EDGE_IMPORTANCE)
         if flags == self._cfg_flags:
             return
-        state, epoch, counters = self.state_ref(), self.get_epoch(), self.counters()
-        tempering = self._tempering_state() if self._ladder is not None else None
-        overlaps = (self._ncopies,) + self.overlap_histograms() if self._ncopies is not None else None
-        cluster = (self._icm_window, self._cluster_counts()) if self._icm_window is not None else None
+        state, epoch, counters, attached = self.state_ref(), self.get_epoch(), self.counters(), self._attachments()
         old, self._cfg_flags = self._cfg_flags, flags
         handle, self._h = self._h, None
         try:
@@ -298,12 +295,20 @@ class GraphState:
         self._lib.isingmc_classical_destroy(handle)
         self.set_epoch(epoch)
         self._counter_base = counters
-        if tempering is not None:
-            self._restore_tempering(*tempering)
-        if overlaps is not None:
-            self._restore_overlaps(*overlaps)
-        if cluster is not None:
-            self._restore_cluster_moves(*cluster)
+        self._restore_attachments(attached)
+
+    # ---- the attachments: the state of each is its checkpoint keys, as save_checkpoint writes them ----
+    def _attachments(self):
+        """The keys of whatever is attached, in one dict (nothing attached: empty)."""
+        parts = ((self._ladder, self._tempering_keys), (self._ncopies, self._overlap_keys), (self._icm_window, self._cluster_keys))
+        return {k: v for attached, keys in parts if attached is not None for k, v in keys().items()}
+
+    def _restore_attachments(self, z):
+        """Attaches and restores what the mapping `z` holds the keys of (each is marked by its first key), in the order they depend on
+        each other."""
+        for key, restore in (("ladder", self._restore_tempering), ("ncopies", self._restore_overlaps), ("cluster_window", self._restore_cluster_moves)):
+            if key in z:
+                restore(z)
 
     # ---- parallel tempering (csrc/classical_pt_rule.h) ----
     def attach_tempering(self, betas):
@@ -392,10 +397,14 @@ class GraphState:
             q2, q4 = (w * q ** 2).sum(axis=2), (w * q ** 4).sum(axis=2)
             return {"q2": q2, "q4": q4, "binder": 0.5 * (3.0 - q4 / q2 ** 2)}
 
-    def _restore_overlaps(self, ncopies, hq, hl):
-        self.attach_overlaps(int(ncopies))
+    def _overlap_keys(self):
+        hq, hl = self.overlap_histograms()
+        return dict(ncopies=np.array([self._ncopies], dtype=np.uint32), overlap_hist=hq, link_hist=hl)
+
+    def _restore_overlaps(self, z):
+        self.attach_overlaps(int(z["ncopies"][0]))
         shape = self._overlap_shape()
-        hq, hl = _histograms((hq, hl), shape + (self.nvars + 1,), shape + (len(self.edges) + 1,))
+        hq, hl = _histograms((z["overlap_hist"], z["link_hist"]), shape + (self.nvars + 1,), shape + (len(self.edges) + 1,))
         self._check(self._lib.isingmc_classical_overlap_set_histograms(self._h, _ptr(hq, C.c_uint64), _ptr(hl, C.c_uint64)))
 
     # ---- isoenergetic cluster moves between the copies of a group (csrc/classical_icm_rule.h) ----
@@ -447,9 +456,13 @@ class GraphState:
         self._check(self._lib.isingmc_classical_icm_launch_plan(self._h, out))
         return _icm_plan_dict(out)
 
-    def _restore_cluster_moves(self, window, counts):
-        self.attach_cluster_moves(int(window[0]), int(window[1]))
-        counts = _cluster_counts(counts, self._cluster_shape())
+    def _cluster_keys(self):
+        moves, empty, size_sum = self._cluster_counts()
+        return dict(cluster_window=np.array(self._icm_window, dtype=np.uint32), cluster_moves=moves, cluster_empty=empty, cluster_size_sum=size_sum)
+
+    def _restore_cluster_moves(self, z):
+        self.attach_cluster_moves(int(z["cluster_window"][0]), int(z["cluster_window"][1]))
+        counts = _cluster_counts((z["cluster_moves"], z["cluster_empty"], z["cluster_size_sum"]), self._cluster_shape())
         self._check(self._lib.isingmc_classical_icm_set_counts(self._h, *(_ptr(x, C.c_uint64) for x in counts)))
 
     def temperature_of(self):
@@ -485,16 +498,19 @@ class GraphState:
         self._check(self._lib.isingmc_classical_pt_swap_counts(self._h, _ptr(att, C.c_uint64), _ptr(acc, C.c_uint64)))
         return att, acc
 
-    def _tempering_state(self):
-        return (self._ladder.copy(), self.temperature_of(), self.tempering_step_number()) + self.swap_counts()
+    def _tempering_keys(self):
+        attempts, accepts = self.swap_counts()
+        return dict(ladder=self._ladder.copy(), temp_of=self.temperature_of(), pt_step=np.array([self.tempering_step_number()], dtype=np.uint64),
+                    swap_attempts=attempts, swap_accepts=accepts)
 
-    def _restore_tempering(self, ladder, temp_of, pt_step, attempts, accepts):
-        self.attach_tempering(ladder)
-        tof = np.ascontiguousarray(np.asarray(temp_of, dtype=np.uint32).reshape(-1))
-        att, acc = (np.ascontiguousarray(np.asarray(x, dtype=np.uint64)) for x in (attempts, accepts))
-        if len(tof) != self.nreplicas or att.shape != (self.nreplicas // len(ladder), len(ladder) - 1) or acc.shape != att.shape:
+    def _restore_tempering(self, z):
+        self.attach_tempering(z["ladder"])
+        tof = np.ascontiguousarray(np.asarray(z["temp_of"], dtype=np.uint32).reshape(-1))
+        att, acc = (np.ascontiguousarray(np.asarray(z[k], dtype=np.uint64)) for k in ("swap_attempts", "swap_accepts"))
+        c, t = self._chains()
+        if len(tof) != self.nreplicas or att.shape != (c, t - 1) or acc.shape != att.shape:
             raise IsingMcError(-1, "tempering state has the wrong shape")
-        self._check(self._lib.isingmc_classical_pt_set(self._h, _ptr(tof, C.c_uint32), int(pt_step)))
+        self._check(self._lib.isingmc_classical_pt_set(self._h, _ptr(tof, C.c_uint32), int(z["pt_step"][0])))
         self._check(self._lib.isingmc_classical_pt_set_swap_counts(self._h, _ptr(att, C.c_uint64), _ptr(acc, C.c_uint64)))
 
     def set_temperature_of(self, temp_of, pt_step=None):
@@ -566,30 +582,22 @@ class GraphState:
         attached.  A batch with overlaps attached writes format 4: the keys it would otherwise write, and `ncopies`, `overlap_hist`,
         `link_hist`.  A batch with cluster moves attached writes format 5: the keys it would otherwise write, and `cluster_window`
         (t_first, t_last), `cluster_moves`, `cluster_empty`, `cluster_size_sum`."""
-        extra = {}
-        if self._ladder is not None:
-            ladder, temp_of, pt_step, attempts, accepts = self._tempering_state()
-            extra = dict(ladder=ladder, temp_of=temp_of, pt_step=np.array([pt_step], dtype=np.uint64), swap_attempts=attempts, swap_accepts=accepts)
-        fmt = 2 if extra else 1
+        extra = self._attachments()
+        fmt = 5 if "cluster_window" in extra else 4 if "ncopies" in extra else 3 if self.couplings is not None else 2 if extra else 1
         if self.couplings is not None:
-            fmt, extra = 3, dict(extra, couplings=self.couplings)
-        if self._ncopies is not None:
-            hq, hl = self.overlap_histograms()
-            fmt, extra = 4, dict(extra, ncopies=np.array([self._ncopies], dtype=np.uint32), overlap_hist=hq, link_hist=hl)
-        if self._icm_window is not None:
-            moves, empty, size_sum = self._cluster_counts()
-            fmt, extra = 5, dict(extra, cluster_window=np.array(self._icm_window, dtype=np.uint32), cluster_moves=moves, cluster_empty=empty, cluster_size_sum=size_sum)
+            extra["couplings"] = self.couplings
         np.savez_compressed(path, format=np.array([fmt], dtype=np.uint32), edges=self.edges, J=self.J, biases=self.biases,
                             seed=np.array([self.seed], dtype=np.uint64), replica_offset=np.array([self.replica_offset], dtype=np.uint32),
                             importance=np.array([bool(self._cfg_flags & CFG_EDGE_IMPORTANCE)]), state=self.state_ref(), epoch=self.get_epoch(),
                             counters=self.counters(), **extra)
 
     def load_checkpoint(self, path):
-        z = np.load(path, allow_pickle=False)
+        with np.load(path, allow_pickle=False) as f:
+            z = {k: f[k] for k in f.files}
         fmt = int(z["format"][0])
         if fmt not in (1, 2, 3, 4, 5):
             raise IsingMcError(-1, "unknown checkpoint format")
-        has_couplings = fmt == 3 or (fmt >= 4 and "couplings" in z.files)
+        has_couplings = "couplings" in z
         if not np.array_equal(z["edges"], self.edges) or not np.array_equal(z["J"], self.J) or not np.array_equal(z["biases"], self.biases):
             raise IsingMcError(-1, "checkpoint belongs to a different model")
         if has_couplings != (self.couplings is not None) or (has_couplings and not np.array_equal(z["couplings"].view(np.uint64), self.couplings.view(np.uint64))):
@@ -600,12 +608,7 @@ class GraphState:
         self.set_state(z["state"])
         self.set_epoch(z["epoch"])
         self._counter_base = z["counters"].astype(np.uint64) - (self.counters() - self._counter_base)
-        if fmt == 2 or (fmt >= 3 and "ladder" in z.files):
-            self._restore_tempering(z["ladder"], z["temp_of"], int(z["pt_step"][0]), z["swap_attempts"], z["swap_accepts"])
-        if fmt >= 4:
-            self._restore_overlaps(int(z["ncopies"][0]), z["overlap_hist"], z["link_hist"])
-        if fmt == 5:
-            self._restore_cluster_moves(z["cluster_window"], (z["cluster_moves"], z["cluster_empty"], z["cluster_size_sum"]))
+        self._restore_attachments(z)
 
     def edge_list(self, r=None):
         """The edges as they were given: [((a, b), J), ...]; with `r`, the edges of replica r's realisation (its row of `couplings`)."""

@@ -1,34 +1,11 @@
-// classical_handle.h — what the two host files of classical Monte Carlo share (classical.hip: creation, time steps, accessors;
-// classical_pt.hip: tempering): the handle, the host form of the graph tables, the config check and the step loop of the sequential
-// rule.  Internal: the C ABI is include/isingmc_hip.h.
+// classical_handle.h — the handle of classical Monte Carlo and its device memory, for the two host files that call the HIP runtime
+// (classical.hip: creation, time steps, accessors; classical_pt.hip: the three attachments and the device rounds).  What needs no
+// device (tables, checks, plans, the sequential rule) is classical_host.h.  Internal: the C ABI is include/isingmc_hip.h.
 #pragma once
-#include "../../include/isingmc_hip.h"
-#include "classical_launch.h"
+#include "classical_host.h"
 #include "hip_host.h"
 
-#include <algorithm>
-#include <string>
 #include <utility>
-#include <vector>
-
-// the graph tables of classical_rule.h on the host
-struct CmcHostTables {
-    std::vector<uint32_t> row, ent, edges;
-    std::vector<double> jv, bias, cum;
-    std::vector<uint8_t> jcode;       // per-replica couplings: [R] rows of 4 cmc_code_words(E) bytes (codes) ...
-    std::vector<double> jr, totalw_r; // ... or [R][2E] doubles; [R] totals of the per-replica running sums
-    uint32_t N = 0, E = 0, flags = 0;
-    double totalw = 0.0;
-    CmcTables view() const {
-        return CmcTables{N, E, flags, (uint32_t)jv.size(), row.data(), ent.data(), jv.data(), bias.empty() ? nullptr : bias.data(), edges.data(),
-                         cum.empty() ? nullptr : cum.data(), totalw, jcode.empty() ? nullptr : jcode.data(), jr.empty() ? nullptr : jr.data(),
-                         totalw_r.empty() ? nullptr : totalw_r.data()};
-    }
-    // 0: the batch shares its couplings, 1: per-replica codes into a batch-wide dictionary, 2: per-replica doubles
-    uint32_t coupling_format() const { return !(flags & CMC_T_PER_REPLICA) ? 0u : (flags & CMC_T_COMPACT) ? 1u : 2u; }
-    // the first chain of T slots (of R) whose coupling rows are not all bitwise equal, or CMC_NONE
-    uint32_t first_mixed_chain(uint32_t R, uint32_t T) const;
-};
 
 // tempering (isingmc_classical_pt_attach): every array is allocated once at its largest size, R entries
 struct CmcPtHandle {
@@ -94,23 +71,3 @@ static int cmc_upload(isingmc_classical *g, const T **p, const std::vector<T> &v
     g->allocs.push_back(std::move(q));
     return ISINGMC_OK;
 }
-
-// a replica's state as bytes on the host, with the marks of the worm next to them
-struct CmcHostState {
-    uint8_t *s, *mark;
-    bool get(uint32_t v) const { return s[v] != 0; }
-    void flip(uint32_t v) { s[v] ^= 1u; mark[v] ^= 1u; }
-    bool marked(uint32_t v) const { return mark[v] != 0; }
-    void unmark(uint32_t v) { mark[v] = 0; }
-};
-// the move counts of a step as the launches resolve them
-struct CmcHostMoves { uint32_t nspin, nedge, nworm, kinds; };
-
-// classical.hip
-int cmc_refuse(int rc, const std::string &why); // the error text of a call without a handle
-int cmc_check_config(const isingmc_classical_config *cfg);
-void cmc_build_tables(const isingmc_classical_config *cfg, CmcHostTables &H);
-// t time steps of replica `replica` (its global index; g is the view of its local index) by the sequential rule: state [N] bytes,
-// mark [N] zeroed scratch, *epoch advanced, ctr [8] added to
-void cmc_host_replica_steps(const CmcGraphMem &g, uint64_t seed, uint32_t replica, uint64_t t, double beta, const CmcHostMoves &m, uint8_t *state,
-                            uint8_t *mark, uint64_t *epoch, uint64_t *ctr);

@@ -22,7 +22,7 @@
 // Counts per item, uint64 [G][M][T] each, cumulative: moves, empty, size_sum (cluster sizes added up).
 // Place in a round: the steps, then the overlap measurement when it is on, then the cluster moves, then the tempering step, whose E
 // and M are therefore those after the moves.
-// Three consumers: classical_icm_kernel (sse_classical_icm.hip.h), isingmc_classical_host_pt_run_icm (classical_pt.hip) and the tests.
+// Three consumers: classical_icm_kernel (sse_classical_icm.hip.h), isingmc_classical_host_pt_run_icm (classical_host.hip) and the tests.
 // Plain inline functions, no device code: hipcc compiles them for the kernel, a host C++ compiler takes the header as it is.
 #pragma once
 #include <stdint.h>

@@ -18,7 +18,7 @@
 // Outputs: the series overlap[round][g][p][t] = Q and link_overlap[round][g][p][t] = QL (int32), and the histograms
 // hq[g][p][t][nq] (N + 1 bins) and hl[g][p][t][nl] (E + 1 bins) (uint64), +1 per measured round.  Sticky error flags of slots do not
 // alter the measurement.  Everything is an integer.
-// Three consumers: classical_overlap_kernel (sse_classical_overlap.hip.h), isingmc_classical_host_pt_run_overlaps (classical_pt.hip)
+// Three consumers: classical_overlap_kernel (sse_classical_overlap.hip.h), isingmc_classical_host_pt_run_overlaps (classical_host.hip)
 // and the tests.  Plain inline functions, no device code: hipcc compiles them for the kernel, a host C++ compiler takes the header as
 // it is.
 #pragma once

@@ -16,7 +16,7 @@
 // One round: every slot takes `steps` time steps at betas[temp_of[r]]; E and M of every slot are computed (a recorded series holds
 // them by temperature, series[round][c][temp_of[r]], before the round's swaps); every chain takes one tempering step at the handle's
 // step number pt_step; pt_step increments.
-// Three consumers: classical_tempering_kernel (sse_classical_pt.hip.h), isingmc_classical_host_pt_run (classical_pt.hip) and the tests.
+// Three consumers: classical_tempering_kernel (sse_classical_pt.hip.h), isingmc_classical_host_pt_run (classical_host.hip) and the tests.
 // Plain inline functions, no device code: hipcc compiles them for the kernel, a host C++ compiler takes the header as it is.
 #pragma once
 #include <math.h>

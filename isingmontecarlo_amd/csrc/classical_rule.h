@@ -2,7 +2,7 @@
 // random stream of a time step, the energy differences, the acceptance test, the edge choice and the whole worm move.
 //
 // Three consumers: classical_steps_kernel (sse_classical.hip.h: one wave per replica, graph tables in LDS or in global memory),
-// isingmc_classical_host_steps (classical.hip: the sequential rule on the CPU) and the table builder of isingmc_classical_create.  The
+// isingmc_classical_host_steps (classical_host.hip: the sequential rule on the CPU) and the table builder of isingmc_classical_create.  The
 // functions are templates over a graph accessor G and a state accessor S, so the same arithmetic reads plain arrays on the host and LDS
 // on the device:
 //   G: N(), E(), row(v) (start of v's row; row(N) = entries), nbr(k), J(k) (neighbour and coupling of row entry k), bias(v),

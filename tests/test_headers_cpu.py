@@ -36,7 +36,8 @@ def test_the_tempering_rule_header_is_plain_cpp():
 
 
 KERNEL_HEADERS = {"sse_fast.hip.h", "sse_rvb.hip.h", "sse_rvb_split.hip.h", "sse_cluster.hip.h", "sse_sweep.hip.h",
-                  "sse_diag.hip.h", "sse_cluster_pass.hip.h", "sse_unionfind.hip.h", "sse_loop.hip.h"}  # the last four: the passes behind sse_sweep.hip.h
+                  "sse_diag.hip.h", "sse_cluster_pass.hip.h", "sse_unionfind.hip.h", "sse_loop.hip.h",  # these four: the passes behind sse_sweep.hip.h
+                  "sse_classical.hip.h", "sse_classical_pt.hip.h", "sse_classical_overlap.hip.h", "sse_classical_icm.hip.h"}
 
 
 def _includes(path, seen=None):

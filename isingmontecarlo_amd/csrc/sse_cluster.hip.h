@@ -160,6 +160,28 @@ __device__ __forceinline__ uint32_t cl_union_wave(const UFA<false> &uf, uint32_t
     }
 }
 
+// Behind the scan (see "join the ranges" and "flatten" in the kernel)
+#ifndef SSE_CL_JOIN_ROTATE
+#define SSE_CL_JOIN_ROTATE 1 // wave wv joins the range boundaries in the order (k + wv) & 15 (0: every wave in the order 0 .. 15)
+#endif
+#ifndef SSE_CL_FLATTEN_BATCH
+#define SSE_CL_FLATTEN_BATCH 4 // ids a thread of the flatten pass walks to their roots together
+#endif
+// link the trees of two DIFFERENT roots as the caller's finds left them, on trees that other waves link at the same time: the
+// compare-and-swap loop of uf_union, entered behind its first pair of finds.  att / lost count the attempts and the lost ones
+// (diagnostic builds read them, elsewhere they are dead)
+__device__ __forceinline__ void cl_link_roots(const UFA<false> &uf, uint32_t a, uint32_t b, uint32_t &att, uint32_t &lost) {
+    for (;;) {
+        if (a > b) { const uint32_t t = a; a = b; b = t; }
+        att++;
+        if (uf.cas(b, b, a) == b) return;
+        lost++;
+        a = uf_find(uf, a);
+        b = uf_find(uf, b);
+        if (a == b) return;
+    }
+}
+
 // One launch = the cluster update (+ free spins + sampling) of every replica: the second launch of a split timestep.
 // PHASE only tags the symbol (see sweep_kernel).
 #ifndef SSE_CL_FIND_LEVELS
@@ -385,7 +407,11 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
                     // no link of this batch can be undone by that)
                     const uint32_t xa = cl_par_addr<HAS_LONG>(par_b, ua[j]), xc = cl_par_addr<HAS_LONG>(par_b, uc[j]); // (each parent address: one instruction)
                     const uint32_t pa = lds_ld16(xa), pc = lds_ld16(xc);
+#if SSE_CL_FIND_LEVELS >= 3
                     uint32_t ga = lds_ld16(par_b + 2u * pa), gc = lds_ld16(par_b + 2u * pc);
+#else // (two hops, timed in round 17 and slower: the parent is the candidate root, "found" below is ga == pa, nothing is re-pointed)
+                    uint32_t ga = pa, gc = pc;
+#endif
                     uint32_t ta = lds_ld16(par_b + 2u * ga), tc = lds_ld16(par_b + 2u * gc);
 #pragma unroll
                     for (int lv = 3; lv < SSE_CL_FIND_LEVELS; ++lv) { // (further levels: the candidate root moves one hop up)
@@ -456,17 +482,41 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
 
     // ---- join the ranges (the segment a worldline is in when range w ends continues into the placeholder of range w + 1; the
     // last range wraps into [0, N): cluster.rs:223-242), collect the touched bits ----
-    for (uint32_t v = tid; v < N; v += NT) {
-        uint32_t t = 0;
+    // One thread per variable, 16 joins each: two finds and, where the roots differ, the compare-and-swap loop (what uf_union does,
+    // with the finds in front so that a diagnostic build can count them).  Wave wv takes the boundaries in the order (k + wv) & 15:
+    // at any moment the 16 waves then work on 16 different boundaries instead of meeting at the same pairs of roots, where all but
+    // one of the threads that try a link lose it and find again (at the headline size 62 % of the attempts were lost, now 25 %).
+    // The partition a set of unions leaves and its smallest-id roots do not depend on the order of the unions.
+    {
+#ifdef SSE_CL_JOIN_COUNTERS // (a diagnostic build of its own) per replica: joins, joins whose first finds agree, compare-and-swap attempts, lost ones
+        uint32_t jc_joins = 0, jc_agree = 0;
+#endif
+        uint32_t jc_att = 0, jc_lost = 0; // (dead without SSE_CL_JOIN_COUNTERS)
+        for (uint32_t v = tid; v < N; v += NT) {
+            uint32_t t = 0;
 #pragma unroll 4
-        for (uint32_t w2 = 0; w2 < (uint32_t)W; ++w2) {
-            const uint32_t x = LDSW(L.o_ent, w2 * (N + 1u) + v);
-            t |= x;
-            const uint32_t seg_end = x & 0xFFFFu;
-            const uint32_t nxt = (w2 + 1u == (uint32_t)W) ? v : N + C + w2 * N + v;
-            if (seg_end != nxt) uf_union(uf, seg_end, nxt);
+            for (uint32_t k = 0; k < (uint32_t)W; ++k) {
+                const uint32_t w2 = SSE_CL_JOIN_ROTATE ? ((k + (uint32_t)wave) & (uint32_t)(W - 1)) : k;
+                const uint32_t x = LDSW(L.o_ent, w2 * (N + 1u) + v);
+                t |= x;
+                const uint32_t seg_end = x & 0xFFFFu;
+                const uint32_t nxt = (w2 + 1u == (uint32_t)W) ? v : N + C + w2 * N + v;
+                if (seg_end != nxt) {
+                    const uint32_t a = uf_find(uf, seg_end), b = uf_find(uf, nxt);
+                    if (a != b) cl_link_roots(uf, a, b, jc_att, jc_lost);
+#ifdef SSE_CL_JOIN_COUNTERS
+                    jc_joins++; jc_agree += a == b;
+#endif
+                }
+            }
+            if (t >> 24) atomicOr(&LDSW(L.o_touch, v >> 5), 1u << (v & 31));
         }
-        if (t >> 24) atomicOr(&LDSW(L.o_touch, v >> 5), 1u << (v & 31));
+#ifdef SSE_CL_JOIN_COUNTERS
+        if (jc_joins) atomicAdd(&B.dbg[(size_t)r * 16 + 8], (unsigned long long)jc_joins);
+        if (jc_agree) atomicAdd(&B.dbg[(size_t)r * 16 + 9], (unsigned long long)jc_agree);
+        if (jc_att) atomicAdd(&B.dbg[(size_t)r * 16 + 10], (unsigned long long)jc_att);
+        if (jc_lost) atomicAdd(&B.dbg[(size_t)r * 16 + 12], (unsigned long long)jc_lost);
+#endif
     }
     __syncthreads();
     SSE_STAMP(2);
@@ -477,28 +527,57 @@ __global__ __launch_bounds__(SSE_CLW * 64, 4) void cluster_kernel(DevBatch B, Sw
     const uint32_t o_bits = L.o_ent, o_list = L.o_ent + (S + 31u) / 32u;
     const uint32_t list_cap = cl_list_cap(N, S);
     uint32_t myclusters = 0;
-    for (uint32_t i0 = 0; i0 < S; i0 += NT) { // whole waves iterate together (ballot below)
-        const uint32_t i = i0 + tid;
-        const bool inr = i < S;
-        bool isroot = false;
-        if (inr) {
-            const uint32_t root = uf_find_ro(uf, i);
-            uf.set(i, root);
-            if constexpr (HAS_LONG)
-                if ((uf.frozen_get(i >> 5) >> (i & 31)) & 1u) { uf.froot_or(root >> 5, 1u << (root & 31)); LDSW(L.o_misc, MISC_ANYFROZEN) = 1u; }
-            isroot = root == i;
-            if (isroot & (i < N + C)) {
-                const bool touched = (i >= N) || ((LDSW(L.o_touch, i >> 5) >> (i & 31)) & 1u);
-                if (touched) myclusters++;
-            }
+    // A thread walks SSE_CL_FLATTEN_BATCH ids to their roots together: the walks are chains of dependent LDS reads, and with four
+    // waves per SIMD nothing else hides their latency
+    constexpr int FB = SSE_CL_FLATTEN_BATCH;
+    for (uint32_t i0 = 0; i0 < S; i0 += NT * FB) { // whole waves iterate together (ballot below)
+        uint32_t fx[FB], fp[FB];
+#pragma unroll
+        for (int f = 0; f < FB; ++f) {
+            const uint32_t i = i0 + (uint32_t)(f * NT + tid);
+            fx[f] = i < S ? i : 0u; // (beyond the ids: id 0, a root)
+            fp[f] = lds_ld16(par_b + 2u * fx[f]);
         }
-        const uint64_t m = sse_ballot(isroot);
-        if (m) {
+        for (;;) { // read-only, as uf_find_ro
+            bool more = false;
+#pragma unroll
+            for (int f = 0; f < FB; ++f) { more |= fp[f] != fx[f]; fx[f] = fp[f]; }
+            if (!more) break;
+#pragma unroll
+            for (int f = 0; f < FB; ++f) fp[f] = lds_ld16(par_b + 2u * fx[f]);
+        }
+        uint64_t m[FB];
+        bool isr[FB];
+        uint32_t nroot = 0; // roots of the wave in this batch: one append to the list for all of them
+#pragma unroll
+        for (int f = 0; f < FB; ++f) {
+            const uint32_t i = i0 + (uint32_t)(f * NT + tid);
+            bool isroot = false;
+            if (i < S) {
+                const uint32_t root = fx[f];
+                uf.set(i, root);
+                if constexpr (HAS_LONG)
+                    if ((uf.frozen_get(i >> 5) >> (i & 31)) & 1u) { uf.froot_or(root >> 5, 1u << (root & 31)); LDSW(L.o_misc, MISC_ANYFROZEN) = 1u; }
+                isroot = root == i;
+                if (isroot & (i < N + C)) {
+                    const bool touched = (i >= N) || ((LDSW(L.o_touch, i >> 5) >> (i & 31)) & 1u);
+                    if (touched) myclusters++;
+                }
+            }
+            isr[f] = isroot;
+            m[f] = sse_ballot(isroot);
+            nroot += (uint32_t)popc64(m[f]);
+        }
+        if (nroot) {
             uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&LDSW(L.o_misc, MISC_LOOP_A), (uint32_t)popc64(m));
+            if (lane == 0) base = atomicAdd(&LDSW(L.o_misc, MISC_LOOP_A), nroot);
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            const uint32_t pos = base + popc64(m & lanemask_lt(lane));
-            if (isroot && pos < list_cap) LDSH(o_list, pos) = (uint16_t)i;
+#pragma unroll
+            for (int f = 0; f < FB; ++f) {
+                const uint32_t pos = base + popc64(m[f] & lanemask_lt(lane));
+                if (isr[f] && pos < list_cap) LDSH(o_list, pos) = (uint16_t)(i0 + (uint32_t)(f * NT + tid));
+                base += (uint32_t)popc64(m[f]);
+            }
         }
     }
     for (uint32_t i = tid; i < (S + 31u) / 32u; i += NT) LDSW(o_bits, i) = 0u;
